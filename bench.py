@@ -3,7 +3,7 @@
 [RCCL all-reduce] + Adam) on synthetic int32 MIDI-event sequences, BASELINE.json's metric:
 "MIDI-event tokens/sec (train, seq=1024)".
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4] [--full] [--dump-outputs DIR]
 
 With --gpus N > 1 and no launcher environment, this process starts `python -m torch.distributed.run` with N ranks of
 itself (before anything touches the GPU), forwards rank 0's JSON line and exits with the launcher's status; under a
@@ -12,15 +12,20 @@ launcher (RANK/WORLD_SIZE set) it is one of the ranks.
 Workloads: c2 (default; BASELINE configs 2/3) 6L/8H/d512, window 1024, B=128 sequences per GPU;
 c4 (BASELINE config 4) 12L/12H/d768, window 2048, B=32 per GPU.  Weak scaling (--batch is per GPU).  bf16 activations
 with fp32 master weights/accumulation, dropout 0.1 (default_config.yml:39-40), Adam lr 1e-3.
-Inputs are generated up front and live in HBM before the timed region.
+Inputs are generated up front (fixed seeds: the same arguments give the same inputs in every run) and live in HBM before
+the timed region.
 
-One JSON line on rank 0 with `roofline` (live HIP-event timing of the dominant kernel class inside the timed
+A plain run is lean: set up, W warm-up steps, K timed steps, the JSON line (`metric`, `value` in tokens/s, `ms_per_step` = the
+wall time of the K timed steps / K, `final_loss`, ...; `roofline` and `cpu_baseline` are null).  --dump-outputs DIR also writes what
+the last timed step computed as .npy files (dump_outputs).  Everything else below is measured only with --full, which adds to
+the same line `roofline` (live HIP-event timing of the dominant kernel class inside the timed
 region), `cpu_baseline` (the CPU restatement of the reference path on the host cores, bounded sample; N=1 only),
 `decode` (BASELINE config 5, with its own memory roofline) and, at N=1, more driver-timed objects: `classes` (the live
 roofline of EVERY kernel class of the step, three extra steps each; every entry carries `algorithmic_bytes` and, when
 profiles/hbm_traffic.json covers the run, the PMC-measured in-step `traffic`), `b32` (SURVEY's C2 batch, 32 sequences, with its
 own `classes`) and `c4` (BASELINE config 4), each `{ms_per_step, value, model_mfma_frac}` from 5 warm-up + 20 timed steps, and
-`forward` (the north-star quantity: the inference forward pass of C2 and C4 as a fraction of the bf16 MFMA peak).
+`forward` (the north-star quantity: the inference forward pass of C2 and C4 as a fraction of the bf16 MFMA peak); --no-extras,
+--no-cpu-baseline and --no-decode leave parts of it out again.
 Under a launcher (any N, also 1) the line carries `comm`: the gradient exchange's exposed (non-overlapped) time per step, `ranks`
 (every rank's own ms/step and exposed ms, gathered over gloo -- a straggler shows up by rank) and `runtime` (RCCL version and the
 paths of the RCCL / HIP runtime this process is bound to); RCCL's own diagnostics (NCCL_DEBUG, default WARN) go to stderr: under
@@ -197,6 +202,31 @@ class stdout_to_stderr:
 def flops_per_token_train(E, L, T):
     fwd = L * (24 * E * E + 2 * E * T) + 2 * E * V          # causal attention counted on the unmasked half
     return 3 * fwd
+
+
+DUMP_SAMPLE = 1 << 17           # elements --dump-outputs keeps of a larger parameter
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(model, out_dir, loss, acc):
+    """--dump-outputs DIR: what the timed train step hands its caller after the LAST timed step, for comparing two builds output by
+    output: `loss.npy` and `accuracy.npy` (float32, shape [1]: that step's metrics) and the fp32 master weights after that step's
+    Adam update, `param.<name, / -> .>.npy` each.  A parameter of more than DUMP_SAMPLE elements is stored as its flattened values
+    at DUMP_SAMPLE positions drawn without replacement with seed 0 from its element count (sorted; the same positions in every
+    run): 13 MB in all at C2, 25 MB at C4.  The inputs are the same in every run with the same arguments; the default step's split-K
+    weight gradients add in float atomics, so two runs of one build agree to rounding (~3e-5 on the weights at C2), not bit for bit."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.array([loss], np.float32), "accuracy": np.array([acc], np.float32)}
+    for name in model.parameter_names:
+        v = model.get_parameter(name).reshape(-1)
+        if v.size > DUMP_SAMPLE:
+            v = v[np.sort(np.random.default_rng(0).choice(v.size, DUMP_SAMPLE, replace=False))]
+        arrays["param." + name.replace("/", ".")] = v
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes, more than %d" % (total, DUMP_LIMIT))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(cf, seconds_budget=24.0):
@@ -381,7 +411,7 @@ def dp1_child(args):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.abspath(__file__), "--gpus", "1", "--steps", "10", "--warmup", "3", "--no-extras",
+           "--master-port", str(port), os.path.abspath(__file__), "--gpus", "1", "--steps", "10", "--warmup", "3", "--full", "--no-extras",
            "--no-cpu-baseline", "--no-decode", "--config", args.config, "--dropout", str(args.dropout)] + \
           (["--batch", str(args.batch)] if args.batch else [])
     env = dict(os.environ)
@@ -423,9 +453,13 @@ def main():
     ap.add_argument("--roofline-kernel", type=int, default=0, help="kernel class timed live (see KERNEL_CLASSES)")
     ap.add_argument("--roofline-every", type=int, default=5, help="the live HIP-event timing of the roofline class covers every n-th "
                                                                     "step of the timed region (two events per launch cost 0.24 ms per step at n = 1: 26.60 vs 26.37 ms)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-decode", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per-class roofline table and the b32 / c4 side runs")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure: the live roofline in the timed "
+                                                         "region, cpu_baseline, decode and (N=1) the per-class table and the side runs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy "
+                                                                         "(see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-decode", action="store_true", help="with --full: skip the decode run")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the per-class roofline table and the side runs")
     ap.add_argument("--dropout", type=float, default=0.1)
     ap.add_argument("--allreduce-only", action="store_true", help="time the step's gradient-exchange message pattern alone (no compute) and "
                                                                    "print its algorithm / bus bandwidth; --steps = repetitions")
@@ -535,23 +569,29 @@ def main():
     if under_launcher:
         model.dp_stats(reset=True)
     lib = _lib.load()
-    lib.cmp_prof_begin(args.roofline_kernel)
+    ms, n_launch, work, abytes = C.c_double(), C.c_int64(), C.c_double(), C.c_double()
+    live = args.full                                 # the live roofline's HIP events in the timed region: --full only
+    if live:
+        lib.cmp_prof_begin(args.roofline_kernel)
     every = max(1, args.roofline_every)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        if every > 1:
+        if live and every > 1:
             (lib.cmp_prof_resume if i % every == 0 else lib.cmp_prof_pause)()
         step(args.warmup + i)
-    lib.cmp_prof_resume()
+    if live:
+        lib.cmp_prof_resume()
     fence()
     dt = time.perf_counter() - t0
-    ms, n_launch, work, abytes = C.c_double(), C.c_int64(), C.c_double(), C.c_double()
-    lib.cmp_prof_end2(C.byref(ms), C.byref(n_launch), C.byref(work), C.byref(abytes))
+    if live:
+        lib.cmp_prof_end2(C.byref(ms), C.byref(n_launch), C.byref(work), C.byref(abytes))
     loss, acc = model.last_metrics()
     comm = model.dp_stats() if under_launcher else None          # the timed steps' exposed gradient-exchange time
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs, loss, acc)         # before any further step changes the weights
     # the live roofline of every kernel class of the step (outside the timed region: three more steps per class)
     classes = None
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         classes = class_table(lib, step, Bq * T, args.config)
     ranks = None
     if dist.is_initialized():
@@ -598,7 +638,7 @@ def main():
             "final_loss": loss,
             "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cf)
         else:
             out["cpu_baseline"] = None
@@ -614,7 +654,7 @@ def main():
             out["runtime"] = _lib.runtime_info()
     model.close()
     if rank == 0:
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             if not (args.config == "c2" and Bq == 32):
                 out["b32"] = side_config("c2", 32, local_rank, args.dropout, classes=True)
             if args.config != "c4":
@@ -626,7 +666,7 @@ def main():
                 if "ms_per_step" in d1:
                     d1["vs_plain_step"] = d1["ms_per_step"] / out["ms_per_step"]
                 out["dp1"] = d1
-        if world == 1 and not args.no_decode:
+        if world == 1 and args.full and not args.no_decode:
             out["decode"] = decode_bench(local_rank)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -101,7 +101,9 @@ def rel(a, b):
 
 
 def check_golden(tf, name, tol, report):
-    g = np.load(os.path.join(ROOT, "tests", "golden", "transformer_%s.npz" % name))
+    sys.path.insert(0, ROOT)
+    from oracle import golden
+    g = golden.load(os.path.join(ROOT, "tests", "golden", "transformer_%s.npz" % name))
     cfg = g["cfg"]
     V, E, H, L, W, T, B = [int(v) for v in cfg]
     params = golden_params(g)

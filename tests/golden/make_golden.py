@@ -11,7 +11,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-from oracle import transformer_oracle as O
+from oracle import golden, transformer_oracle as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LR = 1e-3
@@ -75,7 +75,7 @@ def make(name, V, E, H, L, W, T, B, seed, full_grads):
         ids.append(int(t))
     out["greedy_kv_margin"] = np.array(margins)
     print(name, "min greedy margin", min(margins), "distinct", len(set(out["greedy_kv"].tolist())))
-    np.savez_compressed(os.path.join(HERE, "transformer_%s.npz" % name), **out)
+    golden.save(os.path.join(HERE, "transformer_%s.npz" % name), out)          # in parts of < 1 MiB
     print(name, "losses", np.round(losses, 5), "greedy_kv", out["greedy_kv"][:8])
 
 

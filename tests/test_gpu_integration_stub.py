@@ -85,3 +85,48 @@ def test_bench_allreduce_only_times_the_products_bucket_pattern():
     assert doc["n_gpus"] == 1 and doc["messages"] == 6 + 2 + 1 and doc["reps"] == 5
     assert doc["bytes"] == 4 * 19639296 + 12                                  # C2 has 19 639 296 parameters
     assert doc["ms_per_pattern"] > 0 and doc["value"] > 1.0 and doc["runtime"]["rccl_version"] >= 20000
+
+
+def test_bench_plain_run_times_the_given_steps_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run measures the headline only (`roofline` / `cpu_baseline` null, no side runs) over exactly --steps timed
+    steps, and --dump-outputs writes the last timed step's loss, accuracy and weights as float .npy files: the weights are those
+    after the LAST timed step's Adam update -- a run with one timed step fewer (same inputs) ends one update earlier."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
+        env.pop(k, None)
+
+    def run(steps, out):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                            "--batch", "8", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-1500:])
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    out, out2 = tmp_path / "outputs", tmp_path / "outputs_2"
+    doc = run(3, out)
+    assert doc["steps"] == 3 and doc["warmup"] == 1 and doc["ms_per_step"] > 0 and doc["unit"] == "tokens/s"
+    assert abs(doc["value"] - 8 * 1024 * 1000.0 / doc["ms_per_step"]) <= 1e-6 * doc["value"]
+    assert doc["roofline"] is None and doc["cpu_baseline"] is None
+    assert not {"classes", "b32", "c4", "forward", "default_cfg", "dp1", "decode"} & set(doc)
+    names = sorted(os.listdir(out))
+    assert "loss.npy" in names and "accuracy.npy" in names and len([n for n in names if n.startswith("param.")]) == 6 * 12 + 4
+    loss = np.load(out / "loss.npy")
+    assert loss.dtype == np.float32 and abs(float(loss[0]) - doc["final_loss"]) <= 1e-6 * abs(doc["final_loss"])
+    total = 0
+    for n in names:
+        a = np.load(out / n)
+        assert a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    # ln_f/gamma (512 values, not sampled) starts at ones; one Adam update moves its elements by up to about lr = 1e-3, far more than
+    # two runs of the same steps differ by (float atomics: under 1e-6 here): the dump is taken after the 4th update, not the 3rd
+    g3 = np.load(out / "param.ln_f.gamma.npy")
+    assert g3.shape == (512,) and np.abs(g3 - 1).max() > 1e-4
+    doc2 = run(2, out2)
+    assert doc2["steps"] == 2
+    g2 = np.load(out2 / "param.ln_f.gamma.npy")
+    d = np.abs(g3 - g2)
+    assert d.max() > 3e-4 and np.median(d) > 5e-5, (d.max(), np.median(d))

@@ -9,14 +9,14 @@ import os
 import numpy as np
 import pytest
 
-from oracle import transformer_oracle as O
+from oracle import golden, transformer_oracle as O
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def load_golden(name):
-    g = np.load(os.path.join(HERE, "golden", "transformer_%s.npz" % name))
+    g = golden.load(os.path.join(HERE, "golden", "transformer_%s.npz" % name))
     V, E, H, L, W, T, B = [int(v) for v in g["cfg"]]
     params = {k[6:]: g[k] for k in g.files if k.startswith("param:")}
     return g, (V, E, H, L, W, T, B), params

@@ -125,3 +125,32 @@ def test_bench_self_launches_n_ranks_and_fails_cleanly_without_gpus():
     assert r.returncode != 0
     assert "rank 0 needs GPU 0" in r.stderr and "rank 1 needs GPU 1" in r.stderr
     assert r.stdout.strip() == ""
+
+
+def test_bench_dump_outputs_writes_float_arrays_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: loss, accuracy and every parameter as float32 .npy; a parameter above DUMP_SAMPLE elements is the
+    same fixed sample of its values in every run (stand-in model: no GPU needed)."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = np.arange(bench.DUMP_SAMPLE * 3, dtype=np.float32).reshape(-1, 3)
+
+    class Stub:
+        parameter_names = ["wte/weight", "ln_f/gamma"]
+
+        def get_parameter(self, name):
+            return big if name == "wte/weight" else np.ones(7, np.float32)
+
+    for d in ("a", "b"):
+        bench.dump_outputs(Stub(), str(tmp_path / d), 1.5, 0.25)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["accuracy.npy", "loss.npy", "param.ln_f.gamma.npy", "param.wte.weight.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    w = np.load(tmp_path / "a" / "param.wte.weight.npy")
+    assert w.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(w) > 0) and set(w.tolist()) <= set(big.reshape(-1).tolist())
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [1.5]
+    assert np.load(tmp_path / "a" / "param.ln_f.gamma.npy").tolist() == [1.0] * 7

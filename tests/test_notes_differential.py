@@ -1,10 +1,9 @@
-"""CPU only, build container only: `composer_amd.notes` and the id codec of `composer_amd.dataset` against the REFERENCE's own
-composer/dataset/sequence.py imported live (the same import shims as tests/golden/make_notes_golden.py) on a few thousand seeded
-random note sequences -- the committed `notes.npz` holds 96 cases of this generator; where /root/reference does not exist (the GPU
-box) the test is skipped and the committed vectors stand alone."""
+"""CPU only: `composer_amd.notes` and the id codec of `composer_amd.dataset` against the answers of the REFERENCE's own
+composer/dataset/sequence.py on a few thousand seeded random note sequences and 60 `.data` files.  The reference's answers are
+recorded in tests/golden/notes_differential_s{1,2,3}.npz and tests/golden/codec_files.npz by
+tests/golden/make_notes_differential_golden.py, which imports that module (the same import shims as make_notes_golden.py) on
+exactly the cases this file generates; the committed `notes.npz` holds 96 further cases of this generator."""
 import os
-import sys
-import types
 
 import numpy as np
 import pytest
@@ -12,38 +11,10 @@ import pytest
 from composer_amd import dataset as ds
 from composer_amd.notes import Note, NoteSequence, SustainPeriod
 
-REF = "/root/reference/composer"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only present in the build container")
-
-
-def _reference_module():
-    # the reference predates numpy 1.24: `np.int` / `np.float` appear as DEFAULT ARGUMENTS (sequence.py:1347,1643,1733,1795), i.e.
-    # they are read once, while the module is imported -- the aliases exist for that import only and are taken away again
-    # so that no other test of the session can lean on them
-    missing = object()
-    np_saved = {k: np.__dict__.get(k, missing) for k in ("int", "float")}
-    np.int, np.float = int, float
-    saved = {k: sys.modules.get(k) for k in ("pretty_midi", "composer", "composer.dataset", "composer.dataset.sequence")}
-    pm = types.ModuleType("pretty_midi")
-    for n in ("PrettyMIDI", "Instrument", "Note", "ControlChange"):
-        setattr(pm, n, type(n, (), {}))
-    sys.modules["pretty_midi"] = pm
-    pkg = types.ModuleType("composer"); pkg.__path__ = [REF]
-    sys.modules["composer"] = pkg
-    try:
-        import composer.dataset.sequence as S
-        return S
-    finally:
-        for k, v in np_saved.items():
-            if v is missing:
-                np.__dict__.pop(k, None)
-            else:
-                setattr(np, k, v)
-        for k, v in saved.items():                     # leave no stand-in behind for other tests
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+SEEDS = (1, 2, 3)
+CASES = 400
+COMBOS = (("events", True), ("events", False), ("none", True), ("extend", True))     # (sustain mode, clean), in this order
 
 
 def _random_case(rng):
@@ -65,37 +36,58 @@ def _random_case(rng):
     return settings, notes, periods
 
 
+class _Recorded:
+    """The reference's answers for one seed, read back in the order they were recorded (one entry per case and combination)."""
+    def __init__(self, seed):
+        with np.load(os.path.join(GOLDEN, "notes_differential_s%d.npz" % seed)) as z:
+            self.g = {k: z[k] for k in z.files}
+        self.at = {k: 0 for k in ("trimmed", "events", "back_notes", "back_periods")}
+        self.i = 0
+
+    def _take(self, key, n):
+        a = self.g[key][self.at[key]:self.at[key] + n]
+        self.at[key] += n
+        return a
+
+    def next(self):
+        g, i = self.g, self.i
+        self.i += 1
+        ev = self._take("events", int(g["n_events"][i]))
+        ids = self.g["ids"][self.at["events"] - len(ev):self.at["events"]]
+        return dict(trimmed=[tuple(r) for r in self._take("trimmed", int(g["n_trimmed"][i])).tolist()],
+                    events=[(int(t), None if v == -1 else int(v)) for t, v in ev.tolist()], ids=[int(v) for v in ids],
+                    vocab=int(g["vocab"][i]), back_notes=[tuple(r) for r in self._take("back_notes", int(g["n_back_notes"][i])).tolist()],
+                    back_periods=[tuple(r) for r in self._take("back_periods", int(g["n_back_periods"][i])).tolist()])
+
+
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_notes_and_ids_equal_the_reference_module_on_random_sequences(seed):
-    S = _reference_module()
-    modes = {"events": S.NoteSequence.SustainPeriodEncodeMode.EVENTS, "none": S.NoteSequence.SustainPeriodEncodeMode.NONE,
-             "extend": S.NoteSequence.SustainPeriodEncodeMode.EXTEND}
+    rec = _Recorded(seed)
     rng = np.random.default_rng(seed)
     events_checked = 0
-    for case in range(400):
+    for case in range(CASES):
         (tsi, mts, vb), notes, periods = _random_case(rng)
         trim = bool(rng.integers(0, 2)) and len(notes) > 0
-        for mode in ("events", "none", "extend"):
-            for clean in ((True, False) if mode == "events" else (True,)):
-                ref = S.NoteSequence([S.Note(*n) for n in notes], [S.SustainPeriod(*p) for p in periods])
-                mine = NoteSequence([Note(*n) for n in notes], [SustainPeriod(*p) for p in periods])
-                if trim:
-                    ref.trim_start(); mine.trim_start()
-                    assert [(n.start, n.end) for n in mine.notes] == [(n.start, n.end) for n in ref.notes]
-                es = ref.to_event_sequence(tsi, mts, vb, modes[mode], clean)
-                want = [(int(e.type), None if e.value is None else int(e.value)) for e in es.events]
-                got = mine.to_events(tsi, mts, vb, sustain=mode, clean=clean)
-                assert got == want, (seed, case, mode, clean)
-                vr = ds.event_value_ranges(tsi, mts, vb); rg = ds.event_ranges(vr)
-                ids = [ds.event_to_id(t, v, rg, vr) for t, v in got]
-                assert ids == [S.IntegerEncodedEventSequence.event_to_id(e.type, e.value, es.event_ranges, es.event_value_ranges) for e in es.events]
-                assert [ds.id_to_event(i, rg, vr) for i in ids] == got
-                assert ds.vocab_size(tsi, mts, vb) == max(r.stop for r in es.event_ranges.values())
-                back_ref = es.to_note_sequence()
-                back = NoteSequence.from_events(got, tsi, vb)
-                assert [(n.start, n.end, n.pitch, n.velocity) for n in back.notes] == [(n.start, n.end, n.pitch, n.velocity) for n in back_ref.notes]
-                assert [(s.start, s.end) for s in back.sustain_periods] == [(s.start, s.end) for s in back_ref.sustain_periods]
-                events_checked += len(got)
+        assert trim == bool(rec.g["trim"][case]), (seed, case)                   # the recorded cases are these cases
+        for mode, clean in COMBOS:
+            ref = rec.next()
+            mine = NoteSequence([Note(*n) for n in notes], [SustainPeriod(*p) for p in periods])
+            if trim:
+                mine.trim_start()
+                assert [(n.start, n.end) for n in mine.notes] == ref["trimmed"]
+            want = ref["events"]
+            got = mine.to_events(tsi, mts, vb, sustain=mode, clean=clean)
+            assert got == want, (seed, case, mode, clean)
+            vr = ds.event_value_ranges(tsi, mts, vb); rg = ds.event_ranges(vr)
+            ids = [ds.event_to_id(t, v, rg, vr) for t, v in got]
+            assert ids == ref["ids"]
+            assert [ds.id_to_event(i, rg, vr) for i in ids] == got
+            assert ds.vocab_size(tsi, mts, vb) == ref["vocab"]
+            back = NoteSequence.from_events(got, tsi, vb)
+            assert [(n.start, n.end, n.pitch, n.velocity) for n in back.notes] == ref["back_notes"]
+            assert [(s.start, s.end) for s in back.sustain_periods] == ref["back_periods"]
+            events_checked += len(got)
+    assert rec.i == len(rec.g["n_events"])
     assert events_checked > 100_000
 
 
@@ -103,23 +95,19 @@ def test_data_files_equal_the_reference_writer_and_reader(tmp_path):
     """`.data` files (sequence.py:1500-1560): for random codec settings and event lists, the bytes written by `write_data_file` equal
     the reference's `IntegerEncodedEventSequence.to_file`, and `read_data_file` returns the ids of its `event_ids_from_file` -- 60
     files incl. an empty one, beyond the two whose bytes are committed in tests/golden/codec.npz."""
-    S = _reference_module()
-    rng = np.random.default_rng(11)
-    for k in range(60):
-        settings = (int(rng.choice([1, 2, 5, 10, 20])), int(rng.choice([50, 100, 200, 1000])), int(rng.choice([4, 8, 32, 64, 128])))
-        if settings[1] % settings[0]:
-            continue
-        vr = S.EventSequence._compute_event_value_ranges(*settings)
-        types_ = list(vr.keys())
-        events = []
-        for _ in range(0 if k == 7 else int(rng.integers(1, 400))):
-            t = types_[int(rng.integers(0, len(types_)))]
-            v = S.Event.NONE_VALUE if vr[t] is None else int(rng.integers(vr[t].start, vr[t].stop))
-            events.append((int(t), v))
-        ref_path, my_path = str(tmp_path / ("r%d.data" % k)), str(tmp_path / ("m%d.data" % k))
-        S.IntegerEncodedEventSequence(settings[0], settings[1], settings[2], events).to_file(ref_path)
-        ds.write_data_file(my_path, [(t, None if v == S.Event.NONE_VALUE else v) for t, v in events], *settings)
-        assert open(my_path, "rb").read() == open(ref_path, "rb").read(), (k, settings)
-        ids_ref, _, _, st = S.IntegerEncodedEventSequence.event_ids_from_file(ref_path)
+    with np.load(os.path.join(GOLDEN, "codec_files.npz")) as z:
+        g = {k: z[k] for k in z.files}
+    none_value = int(g["none_value"])
+    keys = sorted(n[:-len("bytes")] for n in g if n.endswith("_bytes"))
+    assert len(keys) > 40 and any(len(g[p + "events"]) == 0 for p in keys)
+    for p in keys:
+        settings = tuple(g[p + "settings"].tolist())
+        events = [(int(t), int(v)) for t, v in g[p + "events"].tolist()]
+        ref_path, my_path = str(tmp_path / ("r_%s.data" % p)), str(tmp_path / ("m_%s.data" % p))
+        with open(ref_path, "wb") as f:
+            f.write(g[p + "bytes"].tobytes())
+        ds.write_data_file(my_path, [(t, None if v == none_value else v) for t, v in events], *settings)
+        assert open(my_path, "rb").read() == open(ref_path, "rb").read(), (p, settings)
+        ids_ref, st = g[p + "ids"].tolist(), tuple(g[p + "read_settings"].tolist())
         ids, st_mine = ds.read_data_file(ref_path)
-        assert list(ids) == list(ids_ref) and tuple(st_mine) == tuple(st), (k, settings)
+        assert list(ids) == list(ids_ref) and tuple(st_mine) == tuple(st), (p, settings)

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import transformer_oracle as O
+from oracle import golden, transformer_oracle as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -126,7 +126,7 @@ def test_param_count_matches_survey():
 
 
 def load_golden(name):
-    g = np.load(os.path.join(HERE, "golden", "transformer_%s.npz" % name))
+    g = golden.load(os.path.join(HERE, "golden", "transformer_%s.npz" % name))
     V, E, H, L, W, T, B = [int(v) for v in g["cfg"]]
     params = {k[6:]: g[k].astype(np.float64) for k in g.files if k.startswith("param:")}
     return g, O.Config(V, E, W, L, H), params

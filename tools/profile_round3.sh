@@ -6,7 +6,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -x -q -m gpu > $out/pytest_gpu.log 2>&1; grep -E "passed|failed" $out/pytest_gpu.log | tail -1
-timeout 600 python bench.py > $out/bench_c2.json 2> $out/bench_c2.err; cut -c1-200 $out/bench_c2.json
+timeout 600 python bench.py --full > $out/bench_c2.json 2> $out/bench_c2.err; cut -c1-200 $out/bench_c2.json
 # (bench.py's default line now carries C2 at B=32, C4 and the per-class roofline table: no separate runs)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_c2 -o k -- python3 bench.py --no-cpu-baseline --no-decode --no-extras --steps 10 --warmup 3 > $out/stats_c2.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_c4 -o k -- python3 bench.py --config c4 --no-cpu-baseline --no-decode --no-extras --steps 6 --warmup 2 > $out/stats_c4.log 2>&1

@@ -35,7 +35,7 @@ done
 # run's traffic only while its build key is the loaded library's)
 cp $out/hbm_traffic.json profiles/hbm_traffic.json
 # 3. the default bench line (driver form)
-timeout 900 python3 bench.py > $out/bench_c2.json 2> $out/bench_c2.err
+timeout 900 python3 bench.py --full > $out/bench_c2.json 2> $out/bench_c2.err
 # 4. MFMA-pipe busy cycles per kernel at C4 (north_star: "rocprof MFMA util"): SQ counters, their own run
 timeout 600 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE --output-format csv -d $out/pmc_c4 -o k -- $BENCH --config c4 --steps 3 --warmup 1 > $out/pmc_c4.log 2>&1
 python3 tools/pmc_summary.py $out/pmc_c4 > $out/pmc_c4_sq_summary.txt

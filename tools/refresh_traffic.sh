@@ -15,7 +15,7 @@ for cfg in "c2 128 131072" "c2 32 32768" "c4 32 65536"; do
   python3 tools/make_traffic_json.py $1_tokens$3 $out/pmc_$1_$2_FETCH_SIZE $out/pmc_$1_$2_WRITE_SIZE $out/hbm_traffic.json
 done
 cp $out/hbm_traffic.json profiles/hbm_traffic.json
-timeout 900 python3 bench.py > $out/bench_c2.json 2> $out/bench_c2.err
+timeout 900 python3 bench.py --full > $out/bench_c2.json 2> $out/bench_c2.err
 find $out -name "*.db" -delete
 find $out -name "k_kernel_trace.csv" -delete
 find $out -name "k_counter_collection.csv" -delete
