@@ -278,10 +278,14 @@ def evaluate(model_type, dataset_path, restoredir, use_generator, max_files):
 @click.option('--decode-mode', type=click.Choice(['reference-literal', 'kv-cache']), default=None,
               help='kv-cache: model(x, past=presents); reference-literal: the reference\'s loop as written (no past). '
                    'Default: kv-cache when prompt + length fits window_size, else reference-literal.')
+@click.option('--num-samples', default=1, type=click.IntRange(1, 256),
+              help='Number of sequences to generate from the prompt, decoded together; sample i uses seed + i and goes to '
+                   'OUTPUT-i.mid (or OUTPUT-i.data). Defaults to 1.')
 def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt_data, prompt_length, generate_length,
-             temperature, decode_mode):
+             temperature, decode_mode, num_samples):
     """Generate a MIDI file (cli.py:617-680): MIDI prompt -> event ids -> model -> event ids -> MIDI.  An output path
-    ending in `.data` gets the event ids in the dataset's binary format instead of a MIDI file."""
+    ending in `.data` gets the event ids in the dataset's binary format instead of a MIDI file.  With --num-samples N > 1
+    the N sequences are decoded as one batch and written to OUTPUT-0 ... OUTPUT-{N-1} (same suffix)."""
     from composer_amd import notes as nt
     config = get_config_from_restoredir(restoredir)
     model, _ = create_model(model_type, config, dtype='fp32')
@@ -316,18 +320,28 @@ def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt
                        'decode loop (--decode-mode reference-literal). With the KV cache at most --length {} fits.'.format(
                            len(x), generate_length, window, window - len(x) + 1), err=True)
     click.echo('decode-mode: {}'.format(decode_mode), err=True)
-    ids = model.generate(x, generate_length, temperature=temperature, mode=decode_mode)
-    all_ids = list(x) + ids.tolist()                             # prompt + generated (cli.py:676)
     out = Path(output_filepath)
     out.parent.mkdir(parents=True, exist_ok=True)
+    if num_samples == 1:
+        ids = model.generate(x, generate_length, temperature=temperature, mode=decode_mode)
+        _write_generated(list(x) + ids.tolist(), out, d)         # prompt + generated (cli.py:676)
+        click.echo(','.join(str(int(i)) for i in ids))
+        return
+    batch = model.generate_batch([x] * num_samples, generate_length, temperature=temperature, mode=decode_mode)
+    for i, ids in enumerate(batch):
+        _write_generated(list(x) + ids.tolist(), out.with_name('{}-{}{}'.format(out.stem, i, out.suffix)), d)
+        click.echo(','.join(str(int(t)) for t in ids))
+
+
+def _write_generated(all_ids, out, d):
     if out.suffix == '.data':
         vr = ds.event_value_ranges(d.time_step_increment, d.max_time_steps, d.velocity_bins)
         rg = ds.event_ranges(vr)
         events = [ds.id_to_event(int(i), rg, vr) for i in all_ids]
         ds.write_data_file(out, events, d.time_step_increment, d.max_time_steps, d.velocity_bins)
     else:                                                        # cli.py:678-680
+        from composer_amd import notes as nt
         nt.ids_to_midi(all_ids, out, d.time_step_increment, d.max_time_steps, d.velocity_bins)
-    click.echo(','.join(str(int(i)) for i in ids))
 
 
 if __name__ == '__main__':

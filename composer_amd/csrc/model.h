@@ -7,6 +7,7 @@
 #include <map>
 
 struct DecodeState;
+struct DecodeBatchState;
 
 struct Metrics {
     double loss_sum;
@@ -188,6 +189,7 @@ struct cmp_model {
     std::vector<char> reload_seen;     // while poisoned: which parameters cmp_param_set has replaced since (all of them clears the flag)
     int ln_fused_mode = -1;            // COMPOSER_LN_FUSED as read when the model was created (-1 unset, 0 off, 2 training passes too)
     DecodeState* dec = nullptr;
+    DecodeBatchState* decb = nullptr;  // batched decode (decode_batch.hip): its own buffers, KV caches and captured chains
     int gemm_role = -1;                // profiler class of the GEMMs being enqueued (0 while the forward pass is)
 
     // dropout seed of this replica: the model seed with the data-parallel rank folded in (rank 0: the seed itself)
@@ -242,3 +244,5 @@ int ensure_workspace(cmp_model* m, int B, int T);
 int model_forward(cmp_model* m, const int32_t* x_dev, int B, int T, bool training, int64_t step, int past_len = 0);
 // decode.hip
 void decode_state_free(DecodeState* d);
+// decode_batch.hip
+void decode_batch_state_free(DecodeBatchState* d);

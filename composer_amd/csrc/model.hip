@@ -403,6 +403,7 @@ extern "C" int cmp_model_destroy(cmp_model* m) {
     hipStreamSynchronize(m->ctx->comm_stream);
     if (m->ctx->copy_stream) hipStreamSynchronize(m->ctx->copy_stream);
     if (m->dec) decode_state_free(m->dec);
+    if (m->decb) decode_batch_state_free(m->decb);
     for (void* p : m->allocs) if (p) hipFree(p);
     for (auto& wg : m->wgrad_groups) wgrad_group_free(&wg);
     wgrad_ws_free(&m->wgrad_ws);

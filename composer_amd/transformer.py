@@ -459,6 +459,35 @@ class Transformer:
         _lib.check(self._lib.cmp_decode_steps(self._h, int(length), out.ctypes.data_as(C.c_void_p)), 'cmp_decode_steps')
         return out
 
+    def generate_batch(self, prompts, length, temperature=1.0, mode='kv', seed=None):
+        """B independent sequences decoded together: returns int32 [B, length].  `prompts` is a list of id sequences (ragged
+        rows allowed); row b samples with seed + b, so it equals `generate(prompts[b], length, seed=seed + b)` in its first id
+        and depends on nothing but its own prompt and seed.  Modes and temperature as in `generate`."""
+        rows = [np.asarray(p, dtype=np.int64).reshape(-1) for p in prompts]
+        m = {'literal': _lib.DECODE_LITERAL, 'reference-literal': _lib.DECODE_LITERAL, 'kv': _lib.DECODE_KV,
+             'kv-cache': _lib.DECODE_KV}[mode]
+        if not 1 <= len(rows) <= 256:
+            raise ValueError('generate_batch: %d rows; 1 to 256 rows are supported' % len(rows))
+        for b, r in enumerate(rows):
+            if len(r) == 0:
+                raise ValueError('generate_batch: row %d is empty' % b)
+            if r.min() < 0 or r.max() >= self.vocab_size:
+                raise ValueError('generate_batch: row %d holds an id outside [0, %d)' % (b, self.vocab_size))
+            if m == _lib.DECODE_KV and len(r) + length - 1 > self.window_size:
+                raise IndexError('generate_batch: row %d: prompt_len + length - 1 = %d exceeds window_size %d (wpe rows, '
+                                 'transformer.py:675-679,786)' % (b, len(r) + length - 1, self.window_size))
+        B, ld = len(rows), max(len(r) for r in rows)
+        buf = np.zeros((B, ld), np.int32)
+        for b, r in enumerate(rows):
+            buf[b, :len(r)] = r
+        lens = np.array([len(r) for r in rows], np.int32)
+        _lib.check(self._lib.cmp_decode_batch_begin(self._h, buf.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B, ld,
+                                                    m, float(temperature), int(self.seed if seed is None else seed)),
+                   'cmp_decode_batch_begin')
+        out = np.empty((B, length), np.int32)
+        _lib.check(self._lib.cmp_decode_batch_steps(self._h, int(length), out.ctypes.data_as(C.c_void_p)), 'cmp_decode_batch_steps')
+        return out
+
     # ------------------------------------------------------------------ checkpoints
     def state_dict(self):
         sd = {}

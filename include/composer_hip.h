@@ -213,6 +213,19 @@ int cmp_decode_steps(cmp_model* m, int n, int32_t* ids_out);
 int cmp_k_sample(void* stream, const float* logits, int V, float temperature, uint64_t seed, uint32_t counter0, int n,
                  int32_t* ids_out);
 
+/* ---- batched decode: B independent sequences per step (1 <= B <= 256), state apart from cmp_decode_begin's ----------------
+ * prompts: host int32 [B][ld], row b holds lens[b] ids (1 <= lens[b] <= window_size).  Row b samples with seed (uint32)(seed + b);
+ * its i-th generated id uses draw counter i, as cmp_decode_begin does, so its first id equals cmp_decode_begin's on that prompt
+ * with seed + b.  A row's ids depend on (weights, its prompt, seed + b, mode, temperature) only, never on B or the other rows.
+ * Steps before begin: CMP_ERR_STATE.  kv mode: a call that would take a row past window_size is refused, naming the row,
+ * before any step runs. */
+int cmp_decode_batch_begin(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int mode,
+                           float temperature, uint64_t seed);
+int cmp_decode_batch_steps(cmp_model* m, int n, int32_t* ids_out);      /* host int32 [B][n], row-major */
+/* The batched sampler on its own (dev pointers): row b of logits [B][ldz] -> ids_out[b], seed + b, draw counter `counter`. */
+int cmp_k_sample_rows(void* stream, const float* logits, int ldz, int B, int V, float temperature, uint64_t seed,
+                      uint32_t counter, int32_t* ids_out);
+
 /* ---- live kernel timing (bench.py roofline): HIP events around every launch of ONE kernel class on the
  * stream it is launched on.  cls: 0 gemm forward (A[M,K].B[K,N]), 1 gemm dgrad (B stored [N,K]), 2 gemm wgrad
  * (A stored [K,M]), 3 attention forward, 4 attention dQ, 5 attention dK/dV, 6 layernorm fwd, 7 adam.
