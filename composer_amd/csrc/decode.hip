@@ -534,7 +534,8 @@ static int launch_attn2(hipStream_t s, cmp_model* m, DecodeState* d, const DecLa
         case 16: dec_attn2_kernel<16><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
         case 32: dec_attn2_kernel<32><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
         case 64: dec_attn2_kernel<64><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
-        default: dec_attn2_kernel<128><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
+        case 128: dec_attn2_kernel<128><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
+        default: CMP_REQUIRE(false, "decode attention: head size %d has no kernel (16, 32, 64, 128)", m->D);
     }
     KERNEL_CHECK();
     return CMP_OK;
@@ -716,5 +717,25 @@ extern "C" int cmp_decode_steps(cmp_model* m, int n, int32_t* ids_out) {
     HIP_CHECK(hipMemcpyAsync(ids_out, d->ids + d->returned, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     d->returned = need;
+    return CMP_OK;
+}
+
+// The logits the most recent per-token step drew its id from (d->logits, ldz padding stripped): host fp32 [V].  Read-only, outside
+// the per-token chain.  The first id of a decode comes from the prefill's logits (cmp_forward_logits shows those), so there is
+// nothing to read before the first step has run.
+extern "C" int cmp_decode_logits_get(cmp_model* m, float* host_out) {
+    CMP_REQUIRE(m && host_out, "decode_logits_get: null argument");
+    DecodeState* d = m->dec;
+    if (!d || !d->begun) {
+        cmp_set_error("decode_logits_get: call cmp_decode_begin first");
+        return CMP_ERR_STATE;
+    }
+    if (d->produced < 2) {
+        cmp_set_error("decode_logits_get: no per-token step has run yet (the first id is drawn from the prefill's logits)");
+        return CMP_ERR_STATE;
+    }
+    HIP_CHECK(hipSetDevice(m->ctx->device));
+    HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+    HIP_CHECK(hipMemcpy(host_out, d->logits, (size_t)m->V * 4, hipMemcpyDeviceToHost));
     return CMP_OK;
 }

@@ -404,7 +404,8 @@ static int launch_attn(hipStream_t s, cmp_model* m, DecodeBatchState* d, const D
         case 16: decb_attn_kernel<16><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
         case 32: decb_attn_kernel<32><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
         case 64: decb_attn_kernel<64><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
-        default: decb_attn_kernel<128><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
+        case 128: decb_attn_kernel<128><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
+        default: CMP_REQUIRE(false, "decode_batch attention: head size %d has no kernel (16, 32, 64, 128)", m->D);
     }
     KERNEL_CHECK();
     return CMP_OK;
@@ -614,5 +615,24 @@ extern "C" int cmp_decode_batch_steps(cmp_model* m, int n, int32_t* ids_out) {
                                    hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     d->returned = need;
+    return CMP_OK;
+}
+
+// The logits the most recent per-token step drew every row's id from (d->logits [B][ldz], padding stripped): host fp32 [B][V].
+// Read-only, outside the per-token chain; nothing to read before the first step has run (the first ids come from the prefills).
+extern "C" int cmp_decode_batch_logits_get(cmp_model* m, float* host_out) {
+    CMP_REQUIRE(m && host_out, "decode_batch_logits_get: null argument");
+    DecodeBatchState* d = m->decb;
+    if (!d || !d->begun) {
+        cmp_set_error("decode_batch_logits_get: call cmp_decode_batch_begin first");
+        return CMP_ERR_STATE;
+    }
+    if (d->produced < 2) {
+        cmp_set_error("decode_batch_logits_get: no per-token step has run yet (the first ids are drawn from the prefills' logits)");
+        return CMP_ERR_STATE;
+    }
+    HIP_CHECK(hipSetDevice(m->ctx->device));
+    HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+    HIP_CHECK(hipMemcpy2D(host_out, (size_t)m->V * 4, d->logits, (size_t)m->ldz * 4, (size_t)m->V * 4, d->B, hipMemcpyDeviceToHost));
     return CMP_OK;
 }

@@ -484,8 +484,25 @@ class Transformer:
         _lib.check(self._lib.cmp_decode_batch_begin(self._h, buf.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B, ld,
                                                     m, float(temperature), int(self.seed if seed is None else seed)),
                    'cmp_decode_batch_begin')
+        self._decode_batch_rows = B
         out = np.empty((B, length), np.int32)
         _lib.check(self._lib.cmp_decode_batch_steps(self._h, int(length), out.ctypes.data_as(C.c_void_p)), 'cmp_decode_batch_steps')
+        return out
+
+    def decode_logits(self):
+        """float32 [V]: the logits the latest per-token step of the batch-1 decode drew its id from (cmp_decode_logits_get)."""
+        out = np.empty(self.vocab_size, np.float32)
+        _lib.check(self._lib.cmp_decode_logits_get(self._h, out.ctypes.data_as(C.c_void_p)), 'cmp_decode_logits_get')
+        return out
+
+    def decode_batch_logits(self):
+        """float32 [B, V] after `generate_batch`: the logits its last per-token step drew every row's id from
+        (cmp_decode_batch_logits_get)."""
+        B = getattr(self, '_decode_batch_rows', 0)
+        if not B:
+            raise _lib.HipLibraryError('decode_batch_logits: call generate_batch first')
+        out = np.empty((B, self.vocab_size), np.float32)
+        _lib.check(self._lib.cmp_decode_batch_logits_get(self._h, out.ctypes.data_as(C.c_void_p)), 'cmp_decode_batch_logits_get')
         return out
 
     # ------------------------------------------------------------------ checkpoints

@@ -208,6 +208,11 @@ int cmp_hidden_get_at(cmp_model* m, int index, int B, int T, int64_t generation,
  * temperature <= 0 => argmax with lowest-index tie-break (the tau->0 limit; cli.py:671 divides). */
 int cmp_decode_begin(cmp_model* m, const int32_t* prompt, int P, int mode, float temperature, uint64_t seed);
 int cmp_decode_steps(cmp_model* m, int n, int32_t* ids_out);
+/* The logits the most recent per-token step drew its id from: host fp32 [V], copied after a stream synchronise; read-only, not
+ * part of the per-token chain.  A steps(n) call leaves the last step's logits, so step one id at a time between reads.
+ * CMP_ERR_STATE before begin and before the first per-token step (the first id is drawn from the prefill's logits, which
+ * cmp_forward_logits shows). */
+int cmp_decode_logits_get(cmp_model* m, float* host_out);
 /* The sampler of the decode chain on its own (dev pointers): n independent draws from ONE logits row [V] with draw counters
  * counter0 .. counter0+n-1 -> ids_out[n].  tf.random.categorical(logits / temperature), cli.py:671-673. */
 int cmp_k_sample(void* stream, const float* logits, int V, float temperature, uint64_t seed, uint32_t counter0, int n,
@@ -222,6 +227,8 @@ int cmp_k_sample(void* stream, const float* logits, int V, float temperature, ui
 int cmp_decode_batch_begin(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int mode,
                            float temperature, uint64_t seed);
 int cmp_decode_batch_steps(cmp_model* m, int n, int32_t* ids_out);      /* host int32 [B][n], row-major */
+/* cmp_decode_logits_get for the batched chain: host fp32 [B][V], row b = the logits row b's latest id was drawn from. */
+int cmp_decode_batch_logits_get(cmp_model* m, float* host_out);
 /* The batched sampler on its own (dev pointers): row b of logits [B][ldz] -> ids_out[b], seed + b, draw counter `counter`. */
 int cmp_k_sample_rows(void* stream, const float* logits, int ldz, int B, int V, float temperature, uint64_t seed,
                       uint32_t counter, int32_t* ids_out);
