@@ -80,6 +80,9 @@ SIGNATURES = {
     "cmp_decode_begin": (_i, [_P, _P, _i, _i, _f, _u64]),
     "cmp_decode_steps": (_i, [_P, _i, _P]),
     "cmp_decode_logits_get": (_i, [_P, _P]),
+    "cmp_decode_begin_slide": (_i, [_P, _P, _i, _i, _f, _u64]),
+    "cmp_decode_batch_begin_slide": (_i, [_P, _P, _P, _i, _i, _i, _f, _u64]),
+    "cmp_decode_slide_stats": (_i, [_P, _i, _P, _P]),
     "cmp_k_sample": (_i, [_P, _P, _i, _f, _u64, _u32, _i, _P]),
     "cmp_decode_batch_begin": (_i, [_P, _P, _P, _i, _i, _i, _f, _u64]),
     "cmp_decode_batch_steps": (_i, [_P, _i, _P]),

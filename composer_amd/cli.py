@@ -275,19 +275,30 @@ def evaluate(model_type, dataset_path, restoredir, use_generator, max_files):
 @click.option('--prompt-length', default=10, help='Number of events to take from the start of the prompt. Defaults to 10.')
 @click.option('--length', '-l', 'generate_length', default=1024, help='The length of the generated event sequence. Defaults to 1024')
 @click.option('--temperature', default=1.0, help='Sampling temperature; 0 = greedy argmax. Defaults to 1.0.')
-@click.option('--decode-mode', type=click.Choice(['reference-literal', 'kv-cache']), default=None,
-              help='kv-cache: model(x, past=presents); reference-literal: the reference\'s loop as written (no past). '
+@click.option('--decode-mode', type=click.Choice(['reference-literal', 'kv-cache', 'kv-slide']), default=None,
+              help='kv-cache: model(x, past=presents); reference-literal: the reference\'s loop as written (no past); '
+                   'kv-slide: kv-cache that goes on past window_size by re-encoding the last --slide-keep events when the '
+                   'window is full (any length). '
                    'Default: kv-cache when prompt + length fits window_size, else reference-literal.')
+@click.option('--slide-keep', default=None, type=int,
+              help='kv-slide: events kept (re-encoded from position 0) when the window is full, 1 .. window_size - 1. '
+                   'Defaults to window_size // 2.')
 @click.option('--num-samples', default=1, type=click.IntRange(1, 256),
               help='Number of sequences to generate from the prompt, decoded together; sample i uses seed + i and goes to '
                    'OUTPUT-i.mid (or OUTPUT-i.data). Defaults to 1.')
 def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt_data, prompt_length, generate_length,
-             temperature, decode_mode, num_samples):
+             temperature, decode_mode, slide_keep, num_samples):
     """Generate a MIDI file (cli.py:617-680): MIDI prompt -> event ids -> model -> event ids -> MIDI.  An output path
     ending in `.data` gets the event ids in the dataset's binary format instead of a MIDI file.  With --num-samples N > 1
     the N sequences are decoded as one batch and written to OUTPUT-0 ... OUTPUT-{N-1} (same suffix)."""
     from composer_amd import notes as nt
     config = get_config_from_restoredir(restoredir)
+    if slide_keep is not None:                                   # refused from the restored config, before any device use
+        if decode_mode != 'kv-slide':
+            raise click.UsageError('--slide-keep goes with --decode-mode kv-slide.')
+        if not 1 <= slide_keep <= config.transformer.model.window_size - 1:
+            raise click.UsageError('--slide-keep {}: must be in [1, window_size - 1 = {}].'.format(
+                slide_keep, config.transformer.model.window_size - 1))
     model, _ = create_model(model_type, config, dtype='fp32')
     model.load_from_checkpoint(restoredir)
     model.compile(config.transformer.train.learning_rate)
@@ -322,12 +333,13 @@ def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt
     click.echo('decode-mode: {}'.format(decode_mode), err=True)
     out = Path(output_filepath)
     out.parent.mkdir(parents=True, exist_ok=True)
+    slide = {'slide_keep': slide_keep} if decode_mode == 'kv-slide' else {}
     if num_samples == 1:
-        ids = model.generate(x, generate_length, temperature=temperature, mode=decode_mode)
+        ids = model.generate(x, generate_length, temperature=temperature, mode=decode_mode, **slide)
         _write_generated(list(x) + ids.tolist(), out, d)         # prompt + generated (cli.py:676)
         click.echo(','.join(str(int(i)) for i in ids))
         return
-    batch = model.generate_batch([x] * num_samples, generate_length, temperature=temperature, mode=decode_mode)
+    batch = model.generate_batch([x] * num_samples, generate_length, temperature=temperature, mode=decode_mode, **slide)
     for i, ids in enumerate(batch):
         _write_generated(list(x) + ids.tolist(), out.with_name('{}-{}{}'.format(out.stem, i, out.suffix)), d)
         click.echo(','.join(str(int(t)) for t in ids))

@@ -6,6 +6,9 @@
 //   CMP_DECODE_KV      : model(x, past=presents) (transformer.py:735-765, 423-426): one new token per step at
 //                        position P+i attending to a preallocated KV cache (the reference's tf.concat
 //                        re-allocates the cache every step).
+// cmp_decode_begin_slide is CMP_DECODE_KV that goes on past the window: when the cache is full, the step is a SLIDE instead of a
+// graph launch -- the last `keep` tokens (prompt and ids both live on the device) are re-encoded at positions 0 .. keep - 1
+// through the same prefill path and the id is drawn from that pass's last row (composer_hip.h: c(n)).
 // The prompt goes through the batched forward of model.hip (prefill); each later token is a fixed chain of
 // 5L+2 small kernels whose only varying inputs (position, current token, RNG counter, output slot) live in
 // device memory, so the chain is captured ONCE into a hipGraph and replayed per token.
@@ -50,6 +53,11 @@ struct DecodeState {
     bool built = false;                 // buffers allocated, chain captured (reused by later cmp_decode_begin calls)
     int64_t weights_version = -1;       // cmp_model::param_version the transposed decode weights were made from
     bool graph_on = false;
+    // sliding-window mode (cmp_decode_begin_slide): the prompt stays on the device beside the generated ids, so that the tail a
+    // slide re-encodes is gathered without a host round trip
+    int32_t* prompt = nullptr;          // [W]
+    int P = 0, keep = 0;                // keep == 0: plain kv / literal decode
+    int64_t row_slides = 0, fwd_calls = 0;
 };
 
 void decode_state_free(DecodeState* d) {
@@ -490,6 +498,41 @@ extern "C" int cmp_k_sample(void* stream, const float* logits, int V, float temp
     return CMP_OK;
 }
 
+// Sliding window (cmp_decode_begin_slide).  The re-encode input of a slide: the last `keep` tokens of prompt ++ ids, t0 = the
+// index of the first of them in that sequence.
+__global__ void dec_slide_gather_kernel(const int32_t* __restrict__ prompt, int P, const int32_t* __restrict__ ids, int t0, int keep,
+                                        int32_t* __restrict__ out) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= keep) return;
+    const int j = t0 + g;
+    out[g] = j < P ? prompt[j] : ids[j - P];
+}
+
+// The draw of a slide: from the re-encode's last logits row, as cmp_decode_begin draws its first id from the prompt's last row --
+// but the draw counter, the produced count and the seed carry on.  The token drawn is consumed next at position `keep`; the row
+// is copied to where cmp_decode_logits_get reads.
+__global__ __launch_bounds__(256) void dec_slide_sample_kernel(const float* __restrict__ z, int V, DecState* __restrict__ st,
+                                                               int32_t* __restrict__ ids, const float* __restrict__ wte,
+                                                               const float* __restrict__ wpe, float* __restrict__ x, int E, int keep,
+                                                               float* __restrict__ zout) {
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    const int tid = threadIdx.x;
+    const unsigned ctr = st->rng;
+    const int nprod = st->produced, capI = st->cap;
+    const int id = sample_block(z, V, st->temperature, st->seed, ctr, bv, bi);
+    __syncthreads();                    // every thread has read the state before thread 0 moves it on
+    if (tid == 0) {
+        if (nprod < capI) ids[nprod] = id;
+        st->produced = nprod + 1;
+        st->rng = ctr + 1;
+        st->token = id;
+        st->pos = keep;
+    }
+    for (int e = tid; e < E; e += 256) x[e] = wte[(int64_t)id * E + e] + wpe[(int64_t)keep * E + e];
+    for (int c = tid; c < V; c += 256) zout[c] = z[c];
+}
+
 // -------------------------------------------------------------------------------------------------
 static int launch_gemv(hipStream_t s, int act, int in_mode, const float* x, const float* g, const float* b, float eps,
                        const float* Wt, const float* bias, const float* resid, float* y, float* u_out, int K, int N, int D,
@@ -569,7 +612,8 @@ static int enqueue_token_step2(cmp_model* m, DecodeState* d) {
 // one token: consumes d->x (embedding of st->token at st->pos), produces the next id and the next d->x
 static int enqueue_token_step(cmp_model* m, DecodeState* d) { return enqueue_token_step2(m, d); }
 
-extern "C" int cmp_decode_begin(cmp_model* m, const int32_t* prompt, int P, int mode, float temperature, uint64_t seed) {
+// keep > 0: sliding-window mode (cmp_decode_begin_slide), kv mode otherwise unchanged
+static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mode, float temperature, uint64_t seed, int keep) {
     CMP_REQUIRE(m && prompt && P > 0, "decode_begin: prompt must hold at least one id");
     CMP_REQUIRE(mode == CMP_DECODE_LITERAL || mode == CMP_DECODE_KV, "decode_begin: bad mode %d", mode);
     CMP_REQUIRE(P <= m->W, "decode_begin: prompt length %d exceeds window_size %d", P, m->W);
@@ -577,6 +621,9 @@ extern "C" int cmp_decode_begin(cmp_model* m, const int32_t* prompt, int P, int 
         CMP_REQUIRE(prompt[i] >= 0 && prompt[i] < m->V, "decode_begin: prompt id %d out of range [0,%d)", prompt[i], m->V);
     HIP_CHECK(hipSetDevice(m->ctx->device));
     hipStream_t s = m->ctx->stream;
+    // the workspace never grows after its first sizing: a slide re-encodes `keep` tokens through it, so it is sized (or found too
+    // small) here, before any id is produced
+    if (keep > 0) CHECK_RC(ensure_workspace(m, 1, std::max(P, keep)));
     // The decode state (buffers, KV caches, transposed fp32 weights, the captured per-token chain) is built once per model
     // and reused by later calls: of the 7.6 ms a call used to spend here before the first token (45 hipMalloc / hipFree, 24
     // transposes, capture + instantiate: 6 % of a 1024-token generate) what is left is the prefill.  The transposes are
@@ -625,6 +672,10 @@ extern "C" int cmp_decode_begin(cmp_model* m, const int32_t* prompt, int P, int 
             CHECK_RC(dalloc(d, &w.vc, (size_t)W * Ea * 4));
         }
     }
+    d->keep = keep;
+    d->P = P;
+    d->row_slides = d->fwd_calls = 0;
+    if (keep > 0 && !d->prompt) CHECK_RC(dalloc(d, &d->prompt, (size_t)W * 4));
     if (d->weights_version != m->param_version) {
         for (int i = 0; i < L; i++) {
             const LayerOff& o = m->lo[i];
@@ -644,6 +695,7 @@ extern "C" int cmp_decode_begin(cmp_model* m, const int32_t* prompt, int P, int 
     // prefill: the whole prompt through the batched forward (Transformer.call with past=None)
     CHECK_RC(ensure_workspace(m, 1, P));
     HIP_CHECK(hipMemcpyAsync(m->x_dev, prompt, (size_t)P * 4, hipMemcpyHostToDevice, s));
+    if (keep > 0) HIP_CHECK(hipMemcpyAsync(d->prompt, m->x_dev, (size_t)P * 4, hipMemcpyDeviceToDevice, s));
     CHECK_RC(model_forward(m, m->x_dev, 1, P, false, 0));
     if (mode == CMP_DECODE_KV) {
         for (int i = 0; i < L; i++) {
@@ -694,6 +746,57 @@ extern "C" int cmp_decode_begin(cmp_model* m, const int32_t* prompt, int P, int 
     return CMP_OK;
 }
 
+extern "C" int cmp_decode_begin(cmp_model* m, const int32_t* prompt, int P, int mode, float temperature, uint64_t seed) {
+    return decode_begin_impl(m, prompt, P, mode, temperature, seed, 0);
+}
+
+// kv mode that goes on past the window: when the cache is full the last `keep` tokens are re-encoded at positions 0 .. keep - 1
+// and the next id is drawn from that pass (composer_hip.h: the contract c(n))
+extern "C" int cmp_decode_begin_slide(cmp_model* m, const int32_t* prompt, int P, int keep, float temperature, uint64_t seed) {
+    CMP_REQUIRE(m, "decode_begin_slide: null model");
+    CMP_REQUIRE(keep >= 1 && keep <= m->W - 1, "decode_begin_slide: keep=%d outside [1, window_size - 1 = %d]", keep, m->W - 1);
+    return decode_begin_impl(m, prompt, P, CMP_DECODE_KV, temperature, seed, keep);
+}
+
+// One slide INSTEAD of a per-token step (the captured chain is not touched): gather the tail, re-encode it, refill the caches,
+// draw.  d->produced ids exist; the sequence so far is prompt ++ ids[0 .. produced).
+static int enqueue_slide(cmp_model* m, DecodeState* d) {
+    hipStream_t s = m->ctx->stream;
+    const int keep = d->keep, Ea = m->Ea, W = m->W;
+    dec_slide_gather_kernel<<<cdiv(keep, 256), 256, 0, s>>>(d->prompt, d->P, d->ids, d->P + d->produced - keep, keep, m->x_dev);
+    KERNEL_CHECK();
+    CHECK_RC(model_forward(m, m->x_dev, 1, keep, false, 0));
+    for (int i = 0; i < m->L; i++) {
+        const int grid = cdiv(keep * Ea, 256);
+        if (m->dtype == CMP_BF16)
+            cache_fill2_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)m->act[i].qkv, d->lw[i].kc, d->lw[i].vc, keep, Ea, m->H, m->D, W);
+        else
+            cache_fill2_kernel<float><<<grid, 256, 0, s>>>((const float*)m->act[i].qkv, d->lw[i].kc, d->lw[i].vc, keep, Ea, m->H, m->D, W);
+        KERNEL_CHECK();
+    }
+    dec_slide_sample_kernel<<<1, 256, 0, s>>>(m->logits + (int64_t)(keep - 1) * m->ldz, m->V, d->st, d->ids, m->P + m->off_wte,
+                                              m->P + m->off_wpe, d->x, m->E, keep, d->logits);
+    KERNEL_CHECK();
+    d->row_slides++;
+    d->fwd_calls++;
+    return CMP_OK;
+}
+
+int decode_slide_stats(DecodeState* d, int64_t* row_slides, int64_t* forward_calls) {
+    if (!d || !d->begun) {
+        cmp_set_error("decode_slide_stats: call cmp_decode_begin first");
+        return CMP_ERR_STATE;
+    }
+    *row_slides = d->row_slides;
+    *forward_calls = d->fwd_calls;
+    return CMP_OK;
+}
+
+extern "C" int cmp_decode_slide_stats(cmp_model* m, int batched, int64_t* row_slides, int64_t* forward_calls) {
+    CMP_REQUIRE(m && row_slides && forward_calls, "decode_slide_stats: null argument");
+    return batched ? decode_batch_slide_stats(m->decb, row_slides, forward_calls) : decode_slide_stats(m->dec, row_slides, forward_calls);
+}
+
 extern "C" int cmp_decode_steps(cmp_model* m, int n, int32_t* ids_out) {
     CMP_REQUIRE(m && ids_out && n >= 0, "decode_steps: bad arguments");
     DecodeState* d = m->dec;
@@ -706,6 +809,12 @@ extern "C" int cmp_decode_steps(cmp_model* m, int n, int32_t* ids_out) {
     const int need = d->returned + n;
     CMP_REQUIRE(need <= d->cap, "decode_steps: more than %d ids per decode_begin", d->cap);
     while (d->produced < need) {
+        if (d->keep > 0 && d->pos >= m->W) {        // the window is full: this id comes from a re-encode of the tail
+            CHECK_RC(enqueue_slide(m, d));
+            d->produced++;
+            d->pos = d->keep;
+            continue;
+        }
         if (d->mode == CMP_DECODE_KV)
             CMP_REQUIRE(d->pos < m->W, "decode_steps: position %d outside the wpe table (window_size %d): "
                         "prompt_len + length - 1 must be <= window_size in kv-cache mode", d->pos, m->W);

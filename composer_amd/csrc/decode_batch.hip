@@ -11,6 +11,9 @@
 // and never stored; the attention key split is a function of the row's own position; the LayerNorm statistics are per row.
 // A row's ids are therefore a function of (weights, prompt, seed + b, mode, temperature) only.
 //
+// Sliding-window mode (cmp_decode_batch_begin_slide): a row whose cache is full sits out the replay (DecRow::hold) and draws
+// that step's id from a re-encode of its last `keep` tokens; rows that slide at the same step share forward calls.
+//
 // State lives apart from the batch-1 DecodeState (m->dec): own transposed weights, buffers, KV caches and captured chains.
 #include "model.h"
 #include "decode_common.h"
@@ -27,7 +30,12 @@ struct DecRow {          // device-resident per-row loop state (the captured cha
     unsigned rng;        // sampling counter
     unsigned seed;       // (uint32)(seed + b)
     float temperature;   // <= 0: greedy
-    int pad;
+    int hold;            // sliding-window mode: 1 while the row sits out a replay (its cache is full, pos == W): attention neither
+                         // appends nor reads, the sampler leaves the row alone; the row's slide, run after the replay, clears it
+};
+
+struct DecRowList {      // rows of one slide, by value in the kernel arguments: no host buffer has to outlive an enqueued step
+    unsigned char row[DECB_MAX_ROWS];
 };
 
 struct DecBatchLayerW {
@@ -49,8 +57,13 @@ struct DecodeBatchState {
     int64_t weights_version = -1;
     int B = 0, mode = 0;
     int produced = 0, returned = 0;
-    std::vector<int> pos;               // host mirror of each row's position (kv-mode window check)
+    std::vector<int> pos;               // host mirror of each row's position (kv-mode window check; which rows slide at which step)
     bool begun = false;
+    // sliding-window mode (cmp_decode_batch_begin_slide): every row's prompt and its length stay on the device beside its ids
+    int32_t* prompts = nullptr;         // [capB][W]
+    int32_t* plen = nullptr;            // [capB]
+    int keep = 0;                       // 0: plain kv / literal decode
+    int64_t row_slides = 0, fwd_calls = 0;
 };
 
 static void decb_drop_graphs(DecodeBatchState* d) {
@@ -250,7 +263,7 @@ __global__ __launch_bounds__(256) void decb_attn_kernel(const float* __restrict_
     const int j0 = sp * chunk, j1 = min(pos + 1, j0 + chunk);
     const int nk = j1 - j0;
     float* out = part + (((size_t)b * H + h) * ATT_SPLITS + sp) * PSTRIDE(D);
-    if (nk <= 0) {
+    if (nk <= 0 || st[b].hold || pos >= W) {        // a held row (pos == W) has no cache slot left: it must not append
         if (tid < D) out[tid] = 0.f;
         if (tid == 0) { out[D] = -INFINITY; out[D + 1] = 0.f; }
         return;
@@ -347,6 +360,7 @@ __global__ __launch_bounds__(256) void decb_sample_kernel(const float* __restric
     const int tid = threadIdx.x, b = row0 + blockIdx.x;
     const float* z = logits + (int64_t)blockIdx.x * ldz;
     DecRow* rs = st + b;
+    if (rs->hold) return;                  // the row's slide draws this step's id (workgroup-uniform)
     const unsigned ctr = rs->rng;
     const float temperature = rs->temperature;
     const unsigned seed = rs->seed;
@@ -363,6 +377,71 @@ __global__ __launch_bounds__(256) void decb_sample_kernel(const float* __restric
         rs->pos = pos;
     }
     for (int e = tid; e < E; e += 256) xr[e] = wte[(int64_t)id * E + e] + wpe[(int64_t)posc * E + e];
+}
+
+// ---- sliding window (cmp_decode_batch_begin_slide) ----
+// rows rl.row[0 .. nb) sit out the next replay
+__global__ void decb_hold_kernel(DecRow* __restrict__ st, DecRowList rl, int nb) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nb) st[rl.row[i]].hold = 1;
+}
+
+// The re-encode input [nb][keep] of the rows rl.row[r0 + blockIdx.y]: the last `keep` tokens of the row's prompt ++ ids, of which
+// `produced` ids exist (the same count for every row of the batch).
+__global__ void decb_slide_gather_kernel(const int32_t* __restrict__ prompts, const int32_t* __restrict__ plen,
+                                         const int32_t* __restrict__ ids, int cap, int W, int produced, int keep, DecRowList rl,
+                                         int r0, int32_t* __restrict__ out) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= keep) return;
+    const int b = rl.row[r0 + blockIdx.y];
+    const int P = plen[b];
+    const int j = P + produced - keep + g;
+    out[(int64_t)blockIdx.y * keep + g] = j < P ? prompts[(int64_t)b * W + j] : ids[(int64_t)b * cap + (j - P)];
+}
+
+// decb_cache_fill_kernel for the nb rows of one re-encode: qkv [nb][keep][3E], row blockIdx.y into the caches of rl.row[r0 + blockIdx.y]
+template <typename T>
+__global__ void decb_slide_fill_kernel(const T* __restrict__ qkv, float* __restrict__ kcT, float* __restrict__ vc, int keep, int E,
+                                       int D, int W, DecRowList rl, int r0) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= keep * E) return;
+    const int b = rl.row[r0 + blockIdx.y];
+    const T* q = qkv + (int64_t)blockIdx.y * keep * 3 * E;
+    float* kr = kcT + (int64_t)b * W * E;
+    float* vr = vc + (int64_t)b * W * E;
+    const int t = i / E, e = i % E, h = e / D, d = e % D;
+    kr[(((int64_t)h * (D / 4) + (d >> 2)) * W + t) * 4 + (d & 3)] = to_f32<T>(q[(int64_t)t * 3 * E + E + e]);
+    vr[((int64_t)h * W + t) * D + d] = to_f32<T>(q[(int64_t)t * 3 * E + 2 * E + e]);
+}
+
+// The draw of a slide for row b = rl.row[r0 + blockIdx.x], from the last row of its re-encode (logits [nb][keep][ldz]): as the
+// first id of a begin, but the row's draw counter, produced count and seed carry on.  The token is consumed next at position
+// `keep`; the logits row goes to where cmp_decode_batch_logits_get reads; the hold is over.
+__global__ __launch_bounds__(256) void decb_slide_sample_kernel(const float* __restrict__ logits, int ldz, int V, DecRow* __restrict__ st,
+                                                                DecRowList rl, int r0, int32_t* __restrict__ ids, int cap,
+                                                                const float* __restrict__ wte, const float* __restrict__ wpe,
+                                                                float* __restrict__ x, int E, int keep, float* __restrict__ zout) {
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    const int tid = threadIdx.x, b = rl.row[r0 + blockIdx.x];
+    const float* z = logits + ((int64_t)blockIdx.x * keep + keep - 1) * ldz;
+    DecRow* rs = st + b;
+    const unsigned ctr = rs->rng;
+    const int nprod = rs->produced;
+    const int id = sample_block(z, V, rs->temperature, rs->seed, ctr, bv, bi);
+    __syncthreads();                       // every thread has read the state before thread 0 moves it on
+    if (tid == 0) {
+        if (nprod < cap) ids[(int64_t)b * cap + nprod] = id;
+        rs->produced = nprod + 1;
+        rs->rng = ctr + 1;
+        rs->token = id;
+        rs->pos = keep;
+        rs->hold = 0;
+    }
+    float* xr = x + (int64_t)b * E;
+    for (int e = tid; e < E; e += 256) xr[e] = wte[(int64_t)id * E + e] + wpe[(int64_t)keep * E + e];
+    float* zo = zout + (int64_t)b * ldz;
+    for (int c = tid; c < V; c += 256) zo[c] = z[c];
 }
 
 // row b of logits [B][ldz] -> ids_out[b], seed (uint32)(seed + b), draw counter `counter`
@@ -453,6 +532,8 @@ static int decb_alloc_rows(cmp_model* m, DecodeBatchState* d, int B) {
     CHECK_RC(balloc(al, &d->r, Bz * E * 4));
     CHECK_RC(balloc(al, &d->g, Bz * 4 * E * 4));
     CHECK_RC(balloc(al, &d->logits, Bz * m->ldz * 4));
+    CHECK_RC(balloc(al, &d->prompts, Bz * W * 4));
+    CHECK_RC(balloc(al, &d->plen, Bz * 4));
     for (auto& w : d->lw) {
         CHECK_RC(balloc(al, &w.kc, Bz * W * Ea * 4));
         CHECK_RC(balloc(al, &w.vc, Bz * W * Ea * 4));
@@ -461,8 +542,9 @@ static int decb_alloc_rows(cmp_model* m, DecodeBatchState* d, int B) {
     return CMP_OK;
 }
 
-extern "C" int cmp_decode_batch_begin(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int mode,
-                                      float temperature, uint64_t seed) {
+// keep > 0: sliding-window mode (cmp_decode_batch_begin_slide), kv mode otherwise unchanged
+static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int mode,
+                                   float temperature, uint64_t seed, int keep) {
     CMP_REQUIRE(m && prompts && lens, "decode_batch_begin: null argument");
     CMP_REQUIRE(B >= 1 && B <= DECB_MAX_ROWS, "decode_batch_begin: B=%d rows; 1 <= B <= %d", B, DECB_MAX_ROWS);
     CMP_REQUIRE(mode == CMP_DECODE_LITERAL || mode == CMP_DECODE_KV, "decode_batch_begin: bad mode %d", mode);
@@ -478,6 +560,13 @@ extern "C" int cmp_decode_batch_begin(cmp_model* m, const int32_t* prompts, cons
     }
     HIP_CHECK(hipSetDevice(m->ctx->device));
     hipStream_t s = m->ctx->stream;
+    if (keep > 0) {
+        // the workspace never grows after its first sizing: a slide re-encodes `keep` tokens per row through it, so it is sized
+        // (or found too small) here, before any id is produced
+        int maxP = 1;
+        for (int b = 0; b < B; b++) maxP = std::max(maxP, lens[b]);
+        CHECK_RC(ensure_workspace(m, 1, std::max(maxP, keep)));
+    }
     const bool graph_on = [] { const char* e = getenv("COMPOSER_NO_GRAPH"); return !(e && e[0] == '1'); }();
     DecodeBatchState* d = m->decb;
     if (!d) {
@@ -533,16 +622,20 @@ extern "C" int cmp_decode_batch_begin(cmp_model* m, const int32_t* prompts, cons
         h[b].rng = 0;
         h[b].seed = (unsigned)(seed + (uint64_t)b);
         h[b].temperature = temperature;
-        h[b].pad = 0;
+        h[b].hold = 0;
         d->pos[b] = h[b].pos;
     }
+    d->keep = keep;
+    d->row_slides = d->fwd_calls = 0;
     HIP_CHECK(hipMemcpyAsync(d->st, h.data(), (size_t)B * sizeof(DecRow), hipMemcpyHostToDevice, s));
+    if (keep > 0) HIP_CHECK(hipMemcpyAsync(d->plen, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
     // prefill, one row at a time through the batch-1 path's forward call; the host prompt upload is stream-ordered, so the
     // stream is drained before the next row's ids overwrite the staging buffer
     for (int b = 0; b < B; b++) {
         const int P = lens[b];
         CHECK_RC(ensure_workspace(m, 1, P));
         HIP_CHECK(hipMemcpyAsync(m->x_dev, prompts + (int64_t)b * ld, (size_t)P * 4, hipMemcpyHostToDevice, s));
+        if (keep > 0) HIP_CHECK(hipMemcpyAsync(d->prompts + (int64_t)b * W, m->x_dev, (size_t)P * 4, hipMemcpyDeviceToDevice, s));
         CHECK_RC(model_forward(m, m->x_dev, 1, P, false, 0));
         if (mode == CMP_DECODE_KV) {
             for (int i = 0; i < L; i++) {
@@ -583,6 +676,60 @@ extern "C" int cmp_decode_batch_begin(cmp_model* m, const int32_t* prompts, cons
     return CMP_OK;
 }
 
+extern "C" int cmp_decode_batch_begin(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int mode,
+                                      float temperature, uint64_t seed) {
+    return decode_batch_begin_impl(m, prompts, lens, B, ld, mode, temperature, seed, 0);
+}
+
+extern "C" int cmp_decode_batch_begin_slide(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int keep,
+                                            float temperature, uint64_t seed) {
+    CMP_REQUIRE(m, "decode_batch_begin_slide: null model");
+    CMP_REQUIRE(keep >= 1 && keep <= m->W - 1, "decode_batch_begin_slide: keep=%d outside [1, window_size - 1 = %d]", keep, m->W - 1);
+    return decode_batch_begin_impl(m, prompts, lens, B, ld, CMP_DECODE_KV, temperature, seed, keep);
+}
+
+// The slide of the nb rows of rl (all at pos == W, held during the replay just enqueued): their tails go through the forward pass
+// together, as many rows per call as the workspace holds.  An fp32 forward is the same arithmetic per row whatever rows share the
+// call (one GEMM kernel, no split-K, per-row attention and LayerNorm); the bf16 forward picks its GEMM kernels by the token
+// count, so a bf16 model re-encodes one row per call, as its prefill does, and a row stays independent of its neighbours.
+static int enqueue_batch_slide(cmp_model* m, DecodeBatchState* d, const DecRowList& rl, int nb) {
+    hipStream_t s = m->ctx->stream;
+    const int keep = d->keep, Ea = m->Ea, W = m->W;
+    const int64_t ws_rows = ((int64_t)m->capB * m->capT) / keep;
+    const int per = m->dtype == CMP_BF16 ? 1 : (int)std::max<int64_t>(1, std::min<int64_t>(ws_rows, nb));
+    for (int r0 = 0; r0 < nb; r0 += per) {
+        const int nc = std::min(per, nb - r0);
+        decb_slide_gather_kernel<<<dim3(cdiv(keep, 256), nc), 256, 0, s>>>(d->prompts, d->plen, d->ids, d->cap, W, d->produced, keep, rl,
+                                                                          r0, m->x_dev);
+        KERNEL_CHECK();
+        CHECK_RC(model_forward(m, m->x_dev, nc, keep, false, 0));
+        for (int i = 0; i < m->L; i++) {
+            const dim3 grid(cdiv(keep * Ea, 256), nc);
+            if (m->dtype == CMP_BF16)
+                decb_slide_fill_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)m->act[i].qkv, d->lw[i].kc, d->lw[i].vc, keep, Ea, m->D, W, rl, r0);
+            else
+                decb_slide_fill_kernel<float><<<grid, 256, 0, s>>>((const float*)m->act[i].qkv, d->lw[i].kc, d->lw[i].vc, keep, Ea, m->D, W, rl, r0);
+            KERNEL_CHECK();
+        }
+        decb_slide_sample_kernel<<<nc, 256, 0, s>>>(m->logits, m->ldz, m->V, d->st, rl, r0, d->ids, d->cap, m->P + m->off_wte,
+                                                    m->P + m->off_wpe, d->x, m->E, keep, d->logits);
+        KERNEL_CHECK();
+        d->fwd_calls++;
+    }
+    d->row_slides += nb;
+    return CMP_OK;
+}
+
+int decode_batch_slide_stats(DecodeBatchState* d, int64_t* row_slides, int64_t* forward_calls) {
+    if (!d || !d->begun) {
+        cmp_set_error("decode_slide_stats: call cmp_decode_batch_begin first");
+        return CMP_ERR_STATE;
+    }
+    *row_slides = d->row_slides;
+    *forward_calls = d->fwd_calls;
+    return CMP_OK;
+}
+
 extern "C" int cmp_decode_batch_steps(cmp_model* m, int n, int32_t* ids_out) {
     CMP_REQUIRE(m && n >= 0 && (ids_out || n == 0), "decode_batch_steps: bad arguments");
     DecodeBatchState* d = m->decb;
@@ -599,11 +746,32 @@ extern "C" int cmp_decode_batch_steps(cmp_model* m, int n, int32_t* ids_out) {
     hipGraphExec_t ex = (d->graph_on && it != d->graphs.end()) ? it->second.second : nullptr;
     // kv mode: refused before any step runs, so a refused call consumes nothing (the last step consumes position pos + todo - 1)
     const int todo = std::max(0, need - d->produced);
-    if (d->mode == CMP_DECODE_KV && todo > 0)
+    if (d->mode == CMP_DECODE_KV && d->keep == 0 && todo > 0)
         for (int b = 0; b < B; b++)
             CMP_REQUIRE(d->pos[b] + todo - 1 < m->W, "decode_batch_steps: row %d: position %d outside the wpe table (window_size %d): "
                         "prompt_len + length - 1 must be <= window_size in kv-cache mode", b, d->pos[b] + todo - 1, m->W);
     while (d->produced < need) {
+        if (d->keep > 0) {
+            // rows whose cache is full draw this step's id from a re-encode of their tail; they sit out the replay, which
+            // still runs all B rows (one capture per B).  When every row slides there is nothing to replay.
+            DecRowList rl = {};
+            int nb = 0;
+            for (int b = 0; b < B; b++)
+                if (d->pos[b] >= m->W) rl.row[nb++] = (unsigned char)b;
+            if (nb > 0) {
+                if (nb < B) {
+                    decb_hold_kernel<<<1, DECB_MAX_ROWS, 0, s>>>(d->st, rl, nb);
+                    KERNEL_CHECK();
+                    if (ex) HIP_CHECK(hipGraphLaunch(ex, s));
+                    else CHECK_RC(enqueue_batch_step(m, d, B));
+                }
+                CHECK_RC(enqueue_batch_slide(m, d, rl, nb));
+                for (int b = 0; b < B; b++) d->pos[b]++;
+                for (int i = 0; i < nb; i++) d->pos[rl.row[i]] = d->keep;
+                d->produced++;
+                continue;
+            }
+        }
         if (ex) HIP_CHECK(hipGraphLaunch(ex, s));
         else CHECK_RC(enqueue_batch_step(m, d, B));
         d->produced++;

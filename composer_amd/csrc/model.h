@@ -246,3 +246,4 @@ int model_forward(cmp_model* m, const int32_t* x_dev, int B, int T, bool trainin
 void decode_state_free(DecodeState* d);
 // decode_batch.hip
 void decode_batch_state_free(DecodeBatchState* d);
+int decode_batch_slide_stats(DecodeBatchState* d, int64_t* row_slides, int64_t* forward_calls);

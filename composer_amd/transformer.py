@@ -19,6 +19,20 @@ from . import _lib
 from . import checkpoint as ckpt
 
 
+def slide_context_length(n, window, keep):
+    """c(n): the number of tokens the sliding-window decode ('kv-slide') draws the next id from, when prompt ++ generated ids
+    holds n tokens.  The context grows to `window`; the draw after that re-encodes the last `keep` tokens (1 <= keep <= window - 1)
+    from position 0, then the context grows to `window` again: a period of window - keep + 1 draws."""
+    n, window, keep = int(n), int(window), int(keep)
+    if not 1 <= keep <= window - 1:
+        raise ValueError('slide keep = %d outside [1, window_size - 1 = %d]' % (keep, window - 1))
+    if n < 1:
+        raise ValueError('n = %d: the sequence holds at least one token' % n)
+    if n <= window:
+        return n
+    return keep + (n - window - 1) % (window - keep + 1)
+
+
 class ModelSaveFrequencyMode(enum.Enum):
     """reference composer/models/__init__.py:92-107"""
     EPOCH = 'epoch'
@@ -444,10 +458,26 @@ class Transformer:
         return tot / cnt, cor / cnt
 
     # ------------------------------------------------------------------ decode (cli.py:659-676)
-    def generate(self, prompt_ids, length, temperature=1.0, mode='kv', seed=None):
+    def _slide_keep(self, slide_keep):
+        keep = self.window_size // 2 if slide_keep is None else int(slide_keep)
+        slide_context_length(self.window_size + 1, self.window_size, keep)       # the range check
+        return keep
+
+    def generate(self, prompt_ids, length, temperature=1.0, mode='kv', seed=None, slide_keep=None):
         """Returns `length` generated ids.  mode 'literal' restates cli.py:663-676 as written (no `past`),
-        mode 'kv' is model(x, past=presents).  temperature <= 0 -> greedy argmax."""
+        mode 'kv' is model(x, past=presents).  temperature <= 0 -> greedy argmax.  mode 'kv-slide' is 'kv' that goes on past
+        window_size: when the cache is full the last `slide_keep` tokens (default window_size // 2) are re-encoded from position 0
+        and decoding continues on them (`slide_context_length` is the context every id is drawn from)."""
         p = np.ascontiguousarray(np.asarray(prompt_ids, dtype=np.int32).reshape(-1))
+        if mode == 'kv-slide':
+            keep = self._slide_keep(slide_keep)
+            _lib.check(self._lib.cmp_decode_begin_slide(self._h, p.ctypes.data_as(C.c_void_p), len(p), keep, float(temperature),
+                                                        int(self.seed if seed is None else seed)), 'cmp_decode_begin_slide')
+            out = np.empty(length, np.int32)
+            _lib.check(self._lib.cmp_decode_steps(self._h, int(length), out.ctypes.data_as(C.c_void_p)), 'cmp_decode_steps')
+            return out
+        if slide_keep is not None:
+            raise ValueError("slide_keep goes with mode='kv-slide'")
         m = {'literal': _lib.DECODE_LITERAL, 'reference-literal': _lib.DECODE_LITERAL, 'kv': _lib.DECODE_KV,
              'kv-cache': _lib.DECODE_KV}[mode]
         if m == _lib.DECODE_KV and len(p) + length - 1 > self.window_size:
@@ -459,13 +489,19 @@ class Transformer:
         _lib.check(self._lib.cmp_decode_steps(self._h, int(length), out.ctypes.data_as(C.c_void_p)), 'cmp_decode_steps')
         return out
 
-    def generate_batch(self, prompts, length, temperature=1.0, mode='kv', seed=None):
+    def generate_batch(self, prompts, length, temperature=1.0, mode='kv', seed=None, slide_keep=None):
         """B independent sequences decoded together: returns int32 [B, length].  `prompts` is a list of id sequences (ragged
         rows allowed); row b samples with seed + b, so it equals `generate(prompts[b], length, seed=seed + b)` in its first id
-        and depends on nothing but its own prompt and seed.  Modes and temperature as in `generate`."""
+        and depends on nothing but its own prompt and seed.  Modes, temperature and slide_keep as in `generate`; in 'kv-slide'
+        every row slides on its own length."""
         rows = [np.asarray(p, dtype=np.int64).reshape(-1) for p in prompts]
+        slide = mode == 'kv-slide'
+        if slide:
+            keep = self._slide_keep(slide_keep)
+        elif slide_keep is not None:
+            raise ValueError("slide_keep goes with mode='kv-slide'")
         m = {'literal': _lib.DECODE_LITERAL, 'reference-literal': _lib.DECODE_LITERAL, 'kv': _lib.DECODE_KV,
-             'kv-cache': _lib.DECODE_KV}[mode]
+             'kv-cache': _lib.DECODE_KV, 'kv-slide': _lib.DECODE_KV}[mode]
         if not 1 <= len(rows) <= 256:
             raise ValueError('generate_batch: %d rows; 1 to 256 rows are supported' % len(rows))
         for b, r in enumerate(rows):
@@ -473,7 +509,7 @@ class Transformer:
                 raise ValueError('generate_batch: row %d is empty' % b)
             if r.min() < 0 or r.max() >= self.vocab_size:
                 raise ValueError('generate_batch: row %d holds an id outside [0, %d)' % (b, self.vocab_size))
-            if m == _lib.DECODE_KV and len(r) + length - 1 > self.window_size:
+            if m == _lib.DECODE_KV and not slide and len(r) + length - 1 > self.window_size:
                 raise IndexError('generate_batch: row %d: prompt_len + length - 1 = %d exceeds window_size %d (wpe rows, '
                                  'transformer.py:675-679,786)' % (b, len(r) + length - 1, self.window_size))
         B, ld = len(rows), max(len(r) for r in rows)
@@ -481,13 +517,25 @@ class Transformer:
         for b, r in enumerate(rows):
             buf[b, :len(r)] = r
         lens = np.array([len(r) for r in rows], np.int32)
-        _lib.check(self._lib.cmp_decode_batch_begin(self._h, buf.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B, ld,
-                                                    m, float(temperature), int(self.seed if seed is None else seed)),
-                   'cmp_decode_batch_begin')
+        if slide:
+            _lib.check(self._lib.cmp_decode_batch_begin_slide(self._h, buf.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
+                                                              B, ld, keep, float(temperature),
+                                                              int(self.seed if seed is None else seed)),
+                       'cmp_decode_batch_begin_slide')
+        else:
+            _lib.check(self._lib.cmp_decode_batch_begin(self._h, buf.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B,
+                                                        ld, m, float(temperature), int(self.seed if seed is None else seed)),
+                       'cmp_decode_batch_begin')
         self._decode_batch_rows = B
         out = np.empty((B, length), np.int32)
         _lib.check(self._lib.cmp_decode_batch_steps(self._h, int(length), out.ctypes.data_as(C.c_void_p)), 'cmp_decode_batch_steps')
         return out
+
+    def decode_slide_stats(self, batched=False):
+        """(rows re-encoded by slides, forward passes run for them) since the chain's last begin (cmp_decode_slide_stats)."""
+        rs, fc = C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.cmp_decode_slide_stats(self._h, 1 if batched else 0, C.byref(rs), C.byref(fc)), 'cmp_decode_slide_stats')
+        return rs.value, fc.value
 
     def decode_logits(self):
         """float32 [V]: the logits the latest per-token step of the batch-1 decode drew its id from (cmp_decode_logits_get)."""

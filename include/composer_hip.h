@@ -194,7 +194,8 @@ int cmp_forward_ex(cmp_model* m, const int32_t* x, int B, int T, int past_len, c
  * host fp32 [2, B, H, T, D] = stack([key, value]) after split_heads.  B, T must be that pass's shape (T = past + new). */
 int cmp_present_get(cmp_model* m, int layer, int B, int T, float* host_out);
 /* The activations a `presents` is read from live until the NEXT forward pass of the model (any of: cmp_forward*, a train or
- * eval step, cmp_decode_begin's prefill).  cmp_forward_generation returns the id of the pass just run; cmp_present_get_at
+ * eval step, cmp_decode_begin's prefill, a slide's re-encode inside cmp_decode_steps / cmp_decode_batch_steps in the
+ * sliding-window mode).  cmp_forward_generation returns the id of the pass just run; cmp_present_get_at
  * refuses (CMP_ERR_INVALID) when a later pass has replaced it -- the reference returns real tensors (transformer.py:820-821),
  * so a stale read must be an error, never another pass's keys/values. */
 int cmp_forward_generation(cmp_model* m, int64_t* generation);
@@ -213,6 +214,22 @@ int cmp_decode_steps(cmp_model* m, int n, int32_t* ids_out);
  * CMP_ERR_STATE before begin and before the first per-token step (the first id is drawn from the prefill's logits, which
  * cmp_forward_logits shows). */
 int cmp_decode_logits_get(cmp_model* m, float* host_out);
+/* Sliding-window decode: kv mode that goes on past window_size.  W = window_size, 1 <= keep <= W - 1 (else CMP_ERR_INVALID).
+ * With s = prompt ++ ids so far and n = len(s), the next id is drawn from the last position of a plain forward pass over
+ * s[n - c(n) : n] at positions 0 .. c(n) - 1,
+ *     c(n) = n                                          if n <= W
+ *     c(n) = keep + ((n - W - 1) mod (W - keep + 1))    otherwise:
+ * the context grows to W; the next draw re-encodes the last `keep` tokens (the newest included) from position 0 -- the position
+ * table is absolute, cached keys cannot be shifted -- and draws from that pass's last row as cmp_decode_begin draws its first id
+ * from the prompt; then the context grows again.  The i-th id uses draw counter i, slides or not.  While n <= W the mode is
+ * CMP_DECODE_KV itself (same kernels, same bits).  cmp_decode_steps enqueues slides like steps (one synchronise at its end);
+ * cmp_decode_logits_get shows the logits the latest id was drawn from, slide steps included.  The re-encode runs through the
+ * model's workspace, which never grows: begin sizes it for max(P, keep) tokens, or refuses before any id is produced when an
+ * earlier call sized it smaller (create the model with max_batch / max_seq covering it). */
+int cmp_decode_begin_slide(cmp_model* m, const int32_t* prompt, int P, int keep, float temperature, uint64_t seed);
+/* Since the chain's last begin (batched != 0: the batched chain's): rows re-encoded by slides, and forward passes run for them
+ * (the batched chain packs the rows that slide at the same step into as few passes as the workspace allows). */
+int cmp_decode_slide_stats(cmp_model* m, int batched, int64_t* row_slides, int64_t* forward_calls);
 /* The sampler of the decode chain on its own (dev pointers): n independent draws from ONE logits row [V] with draw counters
  * counter0 .. counter0+n-1 -> ids_out[n].  tf.random.categorical(logits / temperature), cli.py:671-673. */
 int cmp_k_sample(void* stream, const float* logits, int V, float temperature, uint64_t seed, uint32_t counter0, int n,
@@ -226,6 +243,10 @@ int cmp_k_sample(void* stream, const float* logits, int V, float temperature, ui
  * before any step runs. */
 int cmp_decode_batch_begin(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int mode,
                            float temperature, uint64_t seed);
+/* cmp_decode_begin_slide for B rows: every row slides on its own length (rows that reach the window at the same step are
+ * re-encoded together); a row's ids and logits depend on (weights, its prompt, seed + b, temperature, keep) only. */
+int cmp_decode_batch_begin_slide(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int keep,
+                                 float temperature, uint64_t seed);
 int cmp_decode_batch_steps(cmp_model* m, int n, int32_t* ids_out);      /* host int32 [B][n], row-major */
 /* cmp_decode_logits_get for the batched chain: host fp32 [B][V], row b = the logits row b's latest id was drawn from. */
 int cmp_decode_batch_logits_get(cmp_model* m, float* host_out);
