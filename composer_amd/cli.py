@@ -283,15 +283,25 @@ def evaluate(model_type, dataset_path, restoredir, use_generator, max_files):
 @click.option('--slide-keep', default=None, type=int,
               help='kv-slide: events kept (re-encoded from position 0) when the window is full, 1 .. window_size - 1. '
                    'Defaults to window_size // 2.')
+@click.option('--top-k', default=0, type=int,
+              help='Sample from the K most likely events only (ties to the lower id); 0 = off. Defaults to 0.')
+@click.option('--top-p', default=1.0, type=float,
+              help='Nucleus sampling: sample from the smallest set of most likely events whose probability (after --temperature '
+                   'and --top-k) reaches P, in (0, 1]; 1 = off. Defaults to 1.')
 @click.option('--num-samples', default=1, type=click.IntRange(1, 256),
               help='Number of sequences to generate from the prompt, decoded together; sample i uses seed + i and goes to '
                    'OUTPUT-i.mid (or OUTPUT-i.data). Defaults to 1.')
 def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt_data, prompt_length, generate_length,
-             temperature, decode_mode, slide_keep, num_samples):
+             temperature, decode_mode, slide_keep, top_k, top_p, num_samples):
     """Generate a MIDI file (cli.py:617-680): MIDI prompt -> event ids -> model -> event ids -> MIDI.  An output path
     ending in `.data` gets the event ids in the dataset's binary format instead of a MIDI file.  With --num-samples N > 1
-    the N sequences are decoded as one batch and written to OUTPUT-0 ... OUTPUT-{N-1} (same suffix)."""
+    the N sequences are decoded as one batch and written to OUTPUT-0 ... OUTPUT-{N-1} (same suffix); --top-k / --top-p apply
+    to every sample."""
     from composer_amd import notes as nt
+    if top_k < 0:                                                # refused from the arguments, before any device use
+        raise click.UsageError('--top-k {}: must be >= 0 (0 = off).'.format(top_k))
+    if not 0.0 < top_p <= 1.0:
+        raise click.UsageError('--top-p {}: must be in (0, 1] (1 = off).'.format(top_p))
     config = get_config_from_restoredir(restoredir)
     if slide_keep is not None:                                   # refused from the restored config, before any device use
         if decode_mode != 'kv-slide':
@@ -331,9 +341,13 @@ def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt
                        'decode loop (--decode-mode reference-literal). With the KV cache at most --length {} fits.'.format(
                            len(x), generate_length, window, window - len(x) + 1), err=True)
     click.echo('decode-mode: {}'.format(decode_mode), err=True)
+    click.echo('sampling: temperature {} top-k {} top-p {}'.format(
+        temperature, top_k if top_k else 'off', top_p if top_p < 1.0 else 'off'), err=True)
     out = Path(output_filepath)
     out.parent.mkdir(parents=True, exist_ok=True)
     slide = {'slide_keep': slide_keep} if decode_mode == 'kv-slide' else {}
+    if top_k or top_p < 1.0:
+        slide.update(top_k=top_k, top_p=top_p)
     if num_samples == 1:
         ids = model.generate(x, generate_length, temperature=temperature, mode=decode_mode, **slide)
         _write_generated(list(x) + ids.tolist(), out, d)         # prompt + generated (cli.py:676)

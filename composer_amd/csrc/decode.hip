@@ -30,6 +30,8 @@ struct DecState {        // device-resident loop state
     int W;               // wpe rows
     float temperature;   // <= 0: greedy.  Temperature and seed live here (not in kernel arguments) so that the captured per-token
     unsigned seed;       // graph does not depend on them and survives from one cmp_decode_begin to the next
+    int top_k;           // truncated sampling (decode_common.h): 0 or >= V: off
+    float top_p;         // 1: off
 };
 
 struct DecLayerW {
@@ -47,6 +49,8 @@ struct DecodeState {
     hipGraphExec_t exec = nullptr;
     int mode = 0;
     float temperature = 0.f;
+    int top_k = 0;
+    float top_p = 1.f;
     uint64_t seed = 0;
     int produced = 0, returned = 0, cap = 0, pos = 0;
     bool begun = false;
@@ -453,12 +457,15 @@ __global__ __launch_bounds__(256) void dec_sample2_kernel(const float* __restric
                                                           int32_t* __restrict__ ids, const float* __restrict__ wte,
                                                           const float* __restrict__ wpe, float* __restrict__ x, int E,
                                                           int first) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
     __shared__ int bi[4];
     const int tid = threadIdx.x;
     const float* z = logits + ldz_row_off;
     const unsigned ctr = st->rng;
     const float temperature = st->temperature;
+    const int top_k = st->top_k;
+    const float top_p = st->top_p;
     const unsigned seed = st->seed;
     const int pos0 = st->pos, adv = st->advance, nprod = st->produced, capI = st->cap, Wn = st->W;
     int pos = first ? pos0 : (adv ? pos0 + 1 : 0);
@@ -467,7 +474,7 @@ __global__ __launch_bounds__(256) void dec_sample2_kernel(const float* __restric
     float pe[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) { const int e = tid + 256 * i; pe[i] = e < E ? wpe[(int64_t)posc * E + e] : 0.f; }
-    const int id = sample_block(z, V, temperature, seed, ctr, bv, bi);
+    const int id = sample_block_any(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, trunc_lds);
     if (tid == 0) {
         if (nprod < capI) ids[nprod] = id;
         st->produced = nprod + 1;
@@ -482,20 +489,29 @@ __global__ __launch_bounds__(256) void dec_sample2_kernel(const float* __restric
 
 // n independent draws from ONE logits row with counters counter0 .. counter0+n-1: the sampler of the decode chain exposed for
 // the distribution test against the oracle's softmax(z / temperature)
-__global__ __launch_bounds__(256) void sample_many_kernel(const float* __restrict__ z, int V, float temperature, unsigned seed,
-                                                          unsigned counter0, int32_t* __restrict__ ids) {
+__global__ __launch_bounds__(256) void sample_many_kernel(const float* __restrict__ z, int V, float temperature, int top_k,
+                                                          float top_p, unsigned seed, unsigned counter0,
+                                                          int32_t* __restrict__ ids) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
     __shared__ int bi[4];
-    const int id = sample_block(z, V, temperature, seed, counter0 + blockIdx.x, bv, bi);
+    const int id = sample_block_any(z, V, temperature, top_k, top_p, seed, counter0 + blockIdx.x, bv, bi, trunc_lds);
     if (threadIdx.x == 0) ids[blockIdx.x] = id;
+}
+
+extern "C" int cmp_k_sample_ex(void* stream, const float* logits, int V, float temperature, int top_k, float top_p, uint64_t seed,
+                               uint32_t counter0, int n, int32_t* ids_out) {
+    CMP_REQUIRE(logits && ids_out && V > 0 && n >= 0, "k_sample: bad arguments");
+    CHECK_RC(sampling_check("k_sample", V, temperature, top_k, top_p));
+    if (n == 0) return CMP_OK;
+    sample_many_kernel<<<n, 256, trunc_lds_bytes(V), (hipStream_t)stream>>>(logits, V, temperature, top_k, top_p, (unsigned)seed,
+                                                                            counter0, ids_out);
+    KERNEL_CHECK();
+    return CMP_OK;
 }
 extern "C" int cmp_k_sample(void* stream, const float* logits, int V, float temperature, uint64_t seed, uint32_t counter0, int n,
                             int32_t* ids_out) {
-    CMP_REQUIRE(logits && ids_out && V > 0 && n >= 0, "k_sample: bad arguments");
-    if (n == 0) return CMP_OK;
-    sample_many_kernel<<<n, 256, 0, (hipStream_t)stream>>>(logits, V, temperature, (unsigned)seed, counter0, ids_out);
-    KERNEL_CHECK();
-    return CMP_OK;
+    return cmp_k_sample_ex(stream, logits, V, temperature, 0, 1.0f, seed, counter0, n, ids_out);
 }
 
 // Sliding window (cmp_decode_begin_slide).  The re-encode input of a slide: the last `keep` tokens of prompt ++ ids, t0 = the
@@ -515,12 +531,13 @@ __global__ __launch_bounds__(256) void dec_slide_sample_kernel(const float* __re
                                                                int32_t* __restrict__ ids, const float* __restrict__ wte,
                                                                const float* __restrict__ wpe, float* __restrict__ x, int E, int keep,
                                                                float* __restrict__ zout) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
     __shared__ int bi[4];
     const int tid = threadIdx.x;
     const unsigned ctr = st->rng;
     const int nprod = st->produced, capI = st->cap;
-    const int id = sample_block(z, V, st->temperature, st->seed, ctr, bv, bi);
+    const int id = sample_block_any(z, V, st->temperature, st->top_k, st->top_p, st->seed, ctr, bv, bi, trunc_lds);
     __syncthreads();                    // every thread has read the state before thread 0 moves it on
     if (tid == 0) {
         if (nprod < capI) ids[nprod] = id;
@@ -603,8 +620,8 @@ static int enqueue_token_step2(cmp_model* m, DecodeState* d) {
     }
     CHECK_RC(launch_gemv2(s, 0, 1, d->x, m->P + m->off_lnf_g, m->P + m->off_lnf_b, eps, m->P + m->off_wte, nullptr, nullptr,
                           d->logits, nullptr, E, m->V, m->D));
-    dec_sample2_kernel<<<1, 256, 0, s>>>(d->logits, 0, m->V, d->st, d->ids, m->P + m->off_wte,
-                                         m->P + m->off_wpe, d->x, E, 0);
+    dec_sample2_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(d->logits, 0, m->V, d->st, d->ids, m->P + m->off_wte,
+                                                             m->P + m->off_wpe, d->x, E, 0);
     KERNEL_CHECK();
     return CMP_OK;
 }
@@ -613,9 +630,11 @@ static int enqueue_token_step2(cmp_model* m, DecodeState* d) {
 static int enqueue_token_step(cmp_model* m, DecodeState* d) { return enqueue_token_step2(m, d); }
 
 // keep > 0: sliding-window mode (cmp_decode_begin_slide), kv mode otherwise unchanged
-static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mode, float temperature, uint64_t seed, int keep) {
+static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mode, float temperature, int top_k, float top_p,
+                             uint64_t seed, int keep) {
     CMP_REQUIRE(m && prompt && P > 0, "decode_begin: prompt must hold at least one id");
     CMP_REQUIRE(mode == CMP_DECODE_LITERAL || mode == CMP_DECODE_KV, "decode_begin: bad mode %d", mode);
+    CHECK_RC(sampling_check("decode_begin", m->V, temperature, top_k, top_p));
     CMP_REQUIRE(P <= m->W, "decode_begin: prompt length %d exceeds window_size %d", P, m->W);
     for (int i = 0; i < P; i++)
         CMP_REQUIRE(prompt[i] >= 0 && prompt[i] < m->V, "decode_begin: prompt id %d out of range [0,%d)", prompt[i], m->V);
@@ -648,6 +667,8 @@ static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mod
     d->begun = false;
     d->mode = mode;
     d->temperature = temperature;
+    d->top_k = top_k;
+    d->top_p = top_p;
     d->seed = seed;
     d->cap = 1 << 16;
     const int E = m->E, Ea = m->Ea, L = m->L, W = m->W;
@@ -719,9 +740,12 @@ static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mod
     h.W = W;
     h.temperature = temperature;
     h.seed = (unsigned)seed;
+    h.top_k = top_k;
+    h.top_p = top_p;
     HIP_CHECK(hipMemcpyAsync(d->st, &h, sizeof(h), hipMemcpyHostToDevice, s));
     // first id from the last prompt row (cli.py:673 `[-1, 0]`)
-    dec_sample2_kernel<<<1, 256, 0, s>>>(m->logits, (P - 1) * m->ldz, m->V, d->st, d->ids, m->P + m->off_wte, m->P + m->off_wpe, d->x, E, 1);
+    dec_sample2_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(m->logits, (P - 1) * m->ldz, m->V, d->st, d->ids, m->P + m->off_wte,
+                                                             m->P + m->off_wpe, d->x, E, 1);
     KERNEL_CHECK();
     HIP_CHECK(hipStreamSynchronize(s));
     d->produced = 1;
@@ -747,7 +771,19 @@ static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mod
 }
 
 extern "C" int cmp_decode_begin(cmp_model* m, const int32_t* prompt, int P, int mode, float temperature, uint64_t seed) {
-    return decode_begin_impl(m, prompt, P, mode, temperature, seed, 0);
+    return decode_begin_impl(m, prompt, P, mode, temperature, 0, 1.0f, seed, 0);
+}
+
+// every begin of the batch-1 chain with the truncated-sampling filters: keep = 0 is cmp_decode_begin, keep > 0 (kv mode only)
+// cmp_decode_begin_slide
+extern "C" int cmp_decode_begin_ex(cmp_model* m, const int32_t* prompt, int P, int mode, int keep, float temperature, int top_k,
+                                   float top_p, uint64_t seed) {
+    CMP_REQUIRE(m, "decode_begin_ex: null model");
+    if (keep != 0) {
+        CMP_REQUIRE(mode == CMP_DECODE_KV, "decode_begin_ex: keep=%d goes with CMP_DECODE_KV", keep);
+        CMP_REQUIRE(keep >= 1 && keep <= m->W - 1, "decode_begin_ex: keep=%d outside [1, window_size - 1 = %d]", keep, m->W - 1);
+    }
+    return decode_begin_impl(m, prompt, P, mode, temperature, top_k, top_p, seed, keep);
 }
 
 // kv mode that goes on past the window: when the cache is full the last `keep` tokens are re-encoded at positions 0 .. keep - 1
@@ -755,7 +791,7 @@ extern "C" int cmp_decode_begin(cmp_model* m, const int32_t* prompt, int P, int 
 extern "C" int cmp_decode_begin_slide(cmp_model* m, const int32_t* prompt, int P, int keep, float temperature, uint64_t seed) {
     CMP_REQUIRE(m, "decode_begin_slide: null model");
     CMP_REQUIRE(keep >= 1 && keep <= m->W - 1, "decode_begin_slide: keep=%d outside [1, window_size - 1 = %d]", keep, m->W - 1);
-    return decode_begin_impl(m, prompt, P, CMP_DECODE_KV, temperature, seed, keep);
+    return decode_begin_impl(m, prompt, P, CMP_DECODE_KV, temperature, 0, 1.0f, seed, keep);
 }
 
 // One slide INSTEAD of a per-token step (the captured chain is not touched): gather the tail, re-encode it, refill the caches,
@@ -774,7 +810,7 @@ static int enqueue_slide(cmp_model* m, DecodeState* d) {
             cache_fill2_kernel<float><<<grid, 256, 0, s>>>((const float*)m->act[i].qkv, d->lw[i].kc, d->lw[i].vc, keep, Ea, m->H, m->D, W);
         KERNEL_CHECK();
     }
-    dec_slide_sample_kernel<<<1, 256, 0, s>>>(m->logits + (int64_t)(keep - 1) * m->ldz, m->V, d->st, d->ids, m->P + m->off_wte,
+    dec_slide_sample_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(m->logits + (int64_t)(keep - 1) * m->ldz, m->V, d->st, d->ids, m->P + m->off_wte,
                                               m->P + m->off_wpe, d->x, m->E, keep, d->logits);
     KERNEL_CHECK();
     d->row_slides++;

@@ -9,7 +9,7 @@
 // Per-row reproducibility: no arithmetic of a row depends on B or on the other rows.  The projections run on the exact-f32
 // MFMA (an output element is a fixed sum of k-ordered fma chains, the split fixed by K alone); padding rows of a 16-row tile are zero
 // and never stored; the attention key split is a function of the row's own position; the LayerNorm statistics are per row.
-// A row's ids are therefore a function of (weights, prompt, seed + b, mode, temperature) only.
+// A row's ids are therefore a function of (weights, prompt, seed + b, mode, and the row's own temperature, top_k, top_p) only.
 //
 // Sliding-window mode (cmp_decode_batch_begin_slide): a row whose cache is full sits out the replay (DecRow::hold) and draws
 // that step's id from a re-encode of its last `keep` tokens; rows that slide at the same step share forward calls.
@@ -32,6 +32,8 @@ struct DecRow {          // device-resident per-row loop state (the captured cha
     float temperature;   // <= 0: greedy
     int hold;            // sliding-window mode: 1 while the row sits out a replay (its cache is full, pos == W): attention neither
                          // appends nor reads, the sampler leaves the row alone; the row's slide, run after the replay, clears it
+    int top_k;           // truncated sampling (decode_common.h), per row: 0 or >= V: off
+    float top_p;         // 1: off
 };
 
 struct DecRowList {      // rows of one slide, by value in the kernel arguments: no host buffer has to outlive an enqueued step
@@ -355,6 +357,7 @@ __global__ __launch_bounds__(256) void decb_sample_kernel(const float* __restric
                                                           int row0, int32_t* __restrict__ ids, int cap,
                                                           const float* __restrict__ wte, const float* __restrict__ wpe,
                                                           float* __restrict__ x, int E, int W, int first) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
     __shared__ int bi[4];
     const int tid = threadIdx.x, b = row0 + blockIdx.x;
@@ -368,7 +371,7 @@ __global__ __launch_bounds__(256) void decb_sample_kernel(const float* __restric
     const int pos = first ? pos0 : (adv ? pos0 + 1 : 0);
     const int posc = min(pos, W - 1);      // host refuses to step past the table; never index outside it
     float* xr = x + (int64_t)b * E;
-    const int id = sample_block(z, V, temperature, seed, ctr, bv, bi);
+    const int id = sample_block_any(z, V, temperature, rs->top_k, rs->top_p, seed, ctr, bv, bi, trunc_lds);
     if (tid == 0) {
         if (nprod < cap) ids[(int64_t)b * cap + nprod] = id;
         rs->produced = nprod + 1;
@@ -421,6 +424,7 @@ __global__ __launch_bounds__(256) void decb_slide_sample_kernel(const float* __r
                                                                 DecRowList rl, int r0, int32_t* __restrict__ ids, int cap,
                                                                 const float* __restrict__ wte, const float* __restrict__ wpe,
                                                                 float* __restrict__ x, int E, int keep, float* __restrict__ zout) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
     __shared__ int bi[4];
     const int tid = threadIdx.x, b = rl.row[r0 + blockIdx.x];
@@ -428,7 +432,7 @@ __global__ __launch_bounds__(256) void decb_slide_sample_kernel(const float* __r
     DecRow* rs = st + b;
     const unsigned ctr = rs->rng;
     const int nprod = rs->produced;
-    const int id = sample_block(z, V, rs->temperature, rs->seed, ctr, bv, bi);
+    const int id = sample_block_any(z, V, rs->temperature, rs->top_k, rs->top_p, rs->seed, ctr, bv, bi, trunc_lds);
     __syncthreads();                       // every thread has read the state before thread 0 moves it on
     if (tid == 0) {
         if (nprod < cap) ids[(int64_t)b * cap + nprod] = id;
@@ -458,6 +462,39 @@ extern "C" int cmp_k_sample_rows(void* stream, const float* logits, int ldz, int
     CMP_REQUIRE(logits && ids_out && V > 0 && ldz >= V && B >= 0, "k_sample_rows: bad arguments");
     if (B == 0) return CMP_OK;
     sample_rows_kernel<<<B, 256, 0, (hipStream_t)stream>>>(logits, ldz, V, temperature, seed, counter, ids_out);
+    KERNEL_CHECK();
+    return CMP_OK;
+}
+
+// the same with every row's own (temperature, top_k, top_p), by value in the kernel arguments like DecRowList
+struct SampleRowParams {
+    float temperature[DECB_MAX_ROWS];
+    int top_k[DECB_MAX_ROWS];
+    float top_p[DECB_MAX_ROWS];
+};
+__global__ __launch_bounds__(256) void sample_rows_ex_kernel(const float* __restrict__ z, int ldz, int V, SampleRowParams sp,
+                                                             uint64_t seed, unsigned counter, int32_t* __restrict__ ids) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    const int b = blockIdx.x;
+    const int id = sample_block_any(z + (int64_t)b * ldz, V, sp.temperature[b], sp.top_k[b], sp.top_p[b],
+                                    (unsigned)(seed + (uint64_t)b), counter, bv, bi, trunc_lds);
+    if (threadIdx.x == 0) ids[b] = id;
+}
+extern "C" int cmp_k_sample_rows_ex(void* stream, const float* logits, int ldz, int B, int V, const float* temperature,
+                                    const int32_t* top_k, const float* top_p, uint64_t seed, uint32_t counter, int32_t* ids_out) {
+    CMP_REQUIRE(logits && ids_out && V > 0 && ldz >= V && B >= 0, "k_sample_rows_ex: bad arguments");
+    CMP_REQUIRE(B <= DECB_MAX_ROWS, "k_sample_rows_ex: B=%d rows; at most %d", B, DECB_MAX_ROWS);
+    SampleRowParams sp = {};
+    for (int b = 0; b < B; b++) {
+        sp.temperature[b] = temperature ? temperature[b] : 1.0f;
+        sp.top_k[b] = top_k ? top_k[b] : 0;
+        sp.top_p[b] = top_p ? top_p[b] : 1.0f;
+        CHECK_RC(sampling_check("k_sample_rows_ex", V, sp.temperature[b], sp.top_k[b], sp.top_p[b]));
+    }
+    if (B == 0) return CMP_OK;
+    sample_rows_ex_kernel<<<B, 256, trunc_lds_bytes(V), (hipStream_t)stream>>>(logits, ldz, V, sp, seed, counter, ids_out);
     KERNEL_CHECK();
     return CMP_OK;
 }
@@ -512,7 +549,7 @@ static int enqueue_batch_step(cmp_model* m, DecodeBatchState* d, int B) {
     }
     CHECK_RC(launch_proj(s, 0, 1, d->x, m->P + m->off_lnf_g, m->P + m->off_lnf_b, eps, m->P + m->off_wte, nullptr, nullptr,
                          d->logits, m->ldz, nullptr, E, m->V, m->D, B));
-    decb_sample_kernel<<<B, 256, 0, s>>>(d->logits, m->ldz, m->V, d->st, 0, d->ids, d->cap, m->P + m->off_wte, m->P + m->off_wpe,
+    decb_sample_kernel<<<B, 256, trunc_lds_bytes(m->V), s>>>(d->logits, m->ldz, m->V, d->st, 0, d->ids, d->cap, m->P + m->off_wte, m->P + m->off_wpe,
                                          d->x, E, m->W, 0);
     KERNEL_CHECK();
     return CMP_OK;
@@ -543,10 +580,15 @@ static int decb_alloc_rows(cmp_model* m, DecodeBatchState* d, int B) {
 }
 
 // keep > 0: sliding-window mode (cmp_decode_batch_begin_slide), kv mode otherwise unchanged
+// temperature / top_k / top_p: host arrays of B entries, or null for `temperature0` / off in every row
 static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int mode,
-                                   float temperature, uint64_t seed, int keep) {
+                                   float temperature0, const float* temperature, const int32_t* top_k, const float* top_p,
+                                   uint64_t seed, int keep) {
     CMP_REQUIRE(m && prompts && lens, "decode_batch_begin: null argument");
     CMP_REQUIRE(B >= 1 && B <= DECB_MAX_ROWS, "decode_batch_begin: B=%d rows; 1 <= B <= %d", B, DECB_MAX_ROWS);
+    for (int b = 0; b < B; b++)
+        CHECK_RC(sampling_check("decode_batch_begin", m->V, temperature ? temperature[b] : temperature0, top_k ? top_k[b] : 0,
+                                top_p ? top_p[b] : 1.0f));
     CMP_REQUIRE(mode == CMP_DECODE_LITERAL || mode == CMP_DECODE_KV, "decode_batch_begin: bad mode %d", mode);
     CMP_REQUIRE(ld >= 1, "decode_batch_begin: leading dimension %d", ld);
     for (int b = 0; b < B; b++) {
@@ -621,8 +663,10 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
         h[b].advance = (mode == CMP_DECODE_KV) ? 1 : 0;
         h[b].rng = 0;
         h[b].seed = (unsigned)(seed + (uint64_t)b);
-        h[b].temperature = temperature;
+        h[b].temperature = temperature ? temperature[b] : temperature0;
         h[b].hold = 0;
+        h[b].top_k = top_k ? top_k[b] : 0;
+        h[b].top_p = top_p ? top_p[b] : 1.0f;
         d->pos[b] = h[b].pos;
     }
     d->keep = keep;
@@ -650,7 +694,7 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
             }
         }
         // first id from the row's last prompt position (cli.py:673 `[-1, 0]`), seed + b, draw counter 0
-        decb_sample_kernel<<<1, 256, 0, s>>>(m->logits + (int64_t)(P - 1) * m->ldz, m->ldz, m->V, d->st, b, d->ids, d->cap,
+        decb_sample_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(m->logits + (int64_t)(P - 1) * m->ldz, m->ldz, m->V, d->st, b, d->ids, d->cap,
                                              m->P + m->off_wte, m->P + m->off_wpe, d->x, E, W, 1);
         KERNEL_CHECK();
         HIP_CHECK(hipStreamSynchronize(s));
@@ -678,14 +722,27 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
 
 extern "C" int cmp_decode_batch_begin(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int mode,
                                       float temperature, uint64_t seed) {
-    return decode_batch_begin_impl(m, prompts, lens, B, ld, mode, temperature, seed, 0);
+    return decode_batch_begin_impl(m, prompts, lens, B, ld, mode, temperature, nullptr, nullptr, nullptr, seed, 0);
+}
+
+// every begin of the batched chain with per-row sampling parameters: keep = 0 is cmp_decode_batch_begin, keep > 0 (kv mode only)
+// cmp_decode_batch_begin_slide; a null array is the default for every row (temperature 1, top_k 0, top_p 1)
+extern "C" int cmp_decode_batch_begin_ex(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int mode,
+                                         int keep, const float* temperature, const int32_t* top_k, const float* top_p,
+                                         uint64_t seed) {
+    CMP_REQUIRE(m, "decode_batch_begin_ex: null model");
+    if (keep != 0) {
+        CMP_REQUIRE(mode == CMP_DECODE_KV, "decode_batch_begin_ex: keep=%d goes with CMP_DECODE_KV", keep);
+        CMP_REQUIRE(keep >= 1 && keep <= m->W - 1, "decode_batch_begin_ex: keep=%d outside [1, window_size - 1 = %d]", keep, m->W - 1);
+    }
+    return decode_batch_begin_impl(m, prompts, lens, B, ld, mode, 1.0f, temperature, top_k, top_p, seed, keep);
 }
 
 extern "C" int cmp_decode_batch_begin_slide(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int keep,
                                             float temperature, uint64_t seed) {
     CMP_REQUIRE(m, "decode_batch_begin_slide: null model");
     CMP_REQUIRE(keep >= 1 && keep <= m->W - 1, "decode_batch_begin_slide: keep=%d outside [1, window_size - 1 = %d]", keep, m->W - 1);
-    return decode_batch_begin_impl(m, prompts, lens, B, ld, CMP_DECODE_KV, temperature, seed, keep);
+    return decode_batch_begin_impl(m, prompts, lens, B, ld, CMP_DECODE_KV, temperature, nullptr, nullptr, nullptr, seed, keep);
 }
 
 // The slide of the nb rows of rl (all at pos == W, held during the replay just enqueued): their tails go through the forward pass
@@ -711,7 +768,7 @@ static int enqueue_batch_slide(cmp_model* m, DecodeBatchState* d, const DecRowLi
                 decb_slide_fill_kernel<float><<<grid, 256, 0, s>>>((const float*)m->act[i].qkv, d->lw[i].kc, d->lw[i].vc, keep, Ea, m->D, W, rl, r0);
             KERNEL_CHECK();
         }
-        decb_slide_sample_kernel<<<nc, 256, 0, s>>>(m->logits, m->ldz, m->V, d->st, rl, r0, d->ids, d->cap, m->P + m->off_wte,
+        decb_slide_sample_kernel<<<nc, 256, trunc_lds_bytes(m->V), s>>>(m->logits, m->ldz, m->V, d->st, rl, r0, d->ids, d->cap, m->P + m->off_wte,
                                                     m->P + m->off_wpe, d->x, m->E, keep, d->logits);
         KERNEL_CHECK();
         d->fwd_calls++;

@@ -33,6 +33,49 @@ def slide_context_length(n, window, keep):
     return keep + (n - window - 1) % (window - keep + 1)
 
 
+def check_sampling(top_k, top_p):
+    """The argument rule of truncated sampling: top_k an integer >= 0 (0: off), top_p in (0, 1] (1: off).  Returns (int, float)."""
+    if isinstance(top_k, (bool, np.bool_)) or int(top_k) != top_k:
+        raise ValueError('top_k = %r: an integer >= 0 (0: off)' % (top_k,))
+    if int(top_k) < 0:
+        raise ValueError('top_k = %d must be >= 0 (0: off)' % int(top_k))
+    tp = float(top_p)
+    if not 0.0 < tp <= 1.0:                                     # a NaN fails both comparisons
+        raise ValueError('top_p = %r outside (0, 1] (1: off)' % (top_p,))
+    return int(top_k), tp
+
+
+def sampling_keep_set(z, temperature, top_k=0, top_p=1.0):
+    """The columns truncated sampling (top-k, then nucleus / top-p) may draw from: a sorted int array.  This is the specification
+    the device sampler is held to (include/composer_hip.h, "truncated sampling"), restated in numpy float64 -- no GPU.
+
+    z: one row of logits, taken as float32.  Columns are ranked by (z descending, index ascending).  top_k = 0 or >= V: off,
+    otherwise the first top_k columns of the order are the candidates.  top_p = 1: off, otherwise with
+    q = exp((z - z_max) / temperature) over the candidates, in float64 from the float32 values of z, temperature and top_p, the
+    kept set is the shortest prefix with sum(q[:n]) >= top_p * sum(q), n >= 1.  temperature <= 0 is the greedy argmax: the
+    filters change nothing and the set is the argmax column alone."""
+    z = np.asarray(z, dtype=np.float32).reshape(-1)
+    V = z.size
+    if V == 0:
+        raise ValueError('sampling_keep_set: an empty row')
+    if np.isnan(z).any():
+        raise ValueError('sampling_keep_set: the row holds a NaN')
+    top_k, top_p = check_sampling(top_k, top_p)
+    order = np.lexsort((np.arange(V), -z.astype(np.float64)))   # last key first: z descending, then index ascending
+    if not float(temperature) > 0.0:
+        return order[:1].astype(np.int64)
+    if 0 < top_k < V:
+        order = order[:top_k]
+    tp = np.float32(top_p)
+    if tp < np.float32(1.0):
+        z64 = z[order].astype(np.float64)
+        q = np.exp((z64 - z64[0]) / np.float64(np.float32(temperature)))
+        cum = np.cumsum(q)
+        n = int(np.searchsorted(cum, np.float64(tp) * cum[-1], side='left')) + 1     # the first n with cum[n - 1] >= top_p * total
+        order = order[:max(1, min(n, order.size))]
+    return np.sort(order).astype(np.int64)
+
+
 class ModelSaveFrequencyMode(enum.Enum):
     """reference composer/models/__init__.py:92-107"""
     EPOCH = 'epoch'
@@ -463,16 +506,25 @@ class Transformer:
         slide_context_length(self.window_size + 1, self.window_size, keep)       # the range check
         return keep
 
-    def generate(self, prompt_ids, length, temperature=1.0, mode='kv', seed=None, slide_keep=None):
+    def generate(self, prompt_ids, length, temperature=1.0, mode='kv', seed=None, slide_keep=None, top_k=0, top_p=1.0):
         """Returns `length` generated ids.  mode 'literal' restates cli.py:663-676 as written (no `past`),
         mode 'kv' is model(x, past=presents).  temperature <= 0 -> greedy argmax.  mode 'kv-slide' is 'kv' that goes on past
         window_size: when the cache is full the last `slide_keep` tokens (default window_size // 2) are re-encoded from position 0
-        and decoding continues on them (`slide_context_length` is the context every id is drawn from)."""
+        and decoding continues on them (`slide_context_length` is the context every id is drawn from).
+        top_k / top_p: truncated sampling on the device (0 / 1.0: off) -- every id is drawn from the columns
+        `sampling_keep_set(logits, temperature, top_k, top_p)` names, renormalised."""
         p = np.ascontiguousarray(np.asarray(prompt_ids, dtype=np.int32).reshape(-1))
+        top_k, top_p = check_sampling(top_k, top_p)
+        filters = top_k != 0 or top_p != 1.0
         if mode == 'kv-slide':
             keep = self._slide_keep(slide_keep)
-            _lib.check(self._lib.cmp_decode_begin_slide(self._h, p.ctypes.data_as(C.c_void_p), len(p), keep, float(temperature),
-                                                        int(self.seed if seed is None else seed)), 'cmp_decode_begin_slide')
+            if filters:
+                _lib.check(self._lib.cmp_decode_begin_ex(self._h, p.ctypes.data_as(C.c_void_p), len(p), _lib.DECODE_KV, keep,
+                                                         float(temperature), top_k, top_p,
+                                                         int(self.seed if seed is None else seed)), 'cmp_decode_begin_ex')
+            else:
+                _lib.check(self._lib.cmp_decode_begin_slide(self._h, p.ctypes.data_as(C.c_void_p), len(p), keep, float(temperature),
+                                                            int(self.seed if seed is None else seed)), 'cmp_decode_begin_slide')
             out = np.empty(length, np.int32)
             _lib.check(self._lib.cmp_decode_steps(self._h, int(length), out.ctypes.data_as(C.c_void_p)), 'cmp_decode_steps')
             return out
@@ -483,17 +535,22 @@ class Transformer:
         if m == _lib.DECODE_KV and len(p) + length - 1 > self.window_size:
             raise IndexError('prompt_len + length - 1 = %d exceeds window_size %d (wpe rows, transformer.py:675-679,786)'
                              % (len(p) + length - 1, self.window_size))
-        _lib.check(self._lib.cmp_decode_begin(self._h, p.ctypes.data_as(C.c_void_p), len(p), m, float(temperature),
-                                              int(self.seed if seed is None else seed)), 'cmp_decode_begin')
+        if filters:
+            _lib.check(self._lib.cmp_decode_begin_ex(self._h, p.ctypes.data_as(C.c_void_p), len(p), m, 0, float(temperature), top_k,
+                                                     top_p, int(self.seed if seed is None else seed)), 'cmp_decode_begin_ex')
+        else:
+            _lib.check(self._lib.cmp_decode_begin(self._h, p.ctypes.data_as(C.c_void_p), len(p), m, float(temperature),
+                                                  int(self.seed if seed is None else seed)), 'cmp_decode_begin')
         out = np.empty(length, np.int32)
         _lib.check(self._lib.cmp_decode_steps(self._h, int(length), out.ctypes.data_as(C.c_void_p)), 'cmp_decode_steps')
         return out
 
-    def generate_batch(self, prompts, length, temperature=1.0, mode='kv', seed=None, slide_keep=None):
+    def generate_batch(self, prompts, length, temperature=1.0, mode='kv', seed=None, slide_keep=None, top_k=0, top_p=1.0):
         """B independent sequences decoded together: returns int32 [B, length].  `prompts` is a list of id sequences (ragged
         rows allowed); row b samples with seed + b, so it equals `generate(prompts[b], length, seed=seed + b)` in its first id
         and depends on nothing but its own prompt and seed.  Modes, temperature and slide_keep as in `generate`; in 'kv-slide'
-        every row slides on its own length."""
+        every row slides on its own length.  temperature, top_k and top_p are each a scalar (every row) or a sequence of B values
+        (row b's own): a row's ids depend on its own three only."""
         rows = [np.asarray(p, dtype=np.int64).reshape(-1) for p in prompts]
         slide = mode == 'kv-slide'
         if slide:
@@ -517,7 +574,28 @@ class Transformer:
         for b, r in enumerate(rows):
             buf[b, :len(r)] = r
         lens = np.array([len(r) for r in rows], np.int32)
-        if slide:
+
+        def per_row(v, name, dtype):
+            if np.ndim(v) == 0:
+                return np.full(B, v, dtype)
+            a = np.asarray(v).reshape(-1)
+            if a.size != B:
+                raise ValueError('generate_batch: %s holds %d values for %d rows' % (name, a.size, B))
+            return np.ascontiguousarray(a.astype(dtype))
+        if np.ndim(temperature) or np.ndim(top_k) or np.ndim(top_p) or top_k != 0 or top_p != 1.0:
+            tk = np.atleast_1d(np.asarray(top_k)).reshape(-1)
+            tp = np.atleast_1d(np.asarray(top_p)).reshape(-1)
+            for k in tk:
+                check_sampling(k, 1.0)
+            for q in tp:
+                check_sampling(0, q)
+            ta, ka, pa = per_row(temperature, 'temperature', np.float32), per_row(top_k, 'top_k', np.int32), per_row(top_p, 'top_p', np.float32)
+            _lib.check(self._lib.cmp_decode_batch_begin_ex(self._h, buf.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B,
+                                                           ld, m, keep if slide else 0, ta.ctypes.data_as(C.c_void_p),
+                                                           ka.ctypes.data_as(C.c_void_p), pa.ctypes.data_as(C.c_void_p),
+                                                           int(self.seed if seed is None else seed)),
+                       'cmp_decode_batch_begin_ex')
+        elif slide:
             _lib.check(self._lib.cmp_decode_batch_begin_slide(self._h, buf.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
                                                               B, ld, keep, float(temperature),
                                                               int(self.seed if seed is None else seed)),

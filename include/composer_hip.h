@@ -235,6 +235,33 @@ int cmp_decode_slide_stats(cmp_model* m, int batched, int64_t* row_slides, int64
 int cmp_k_sample(void* stream, const float* logits, int V, float temperature, uint64_t seed, uint32_t counter0, int n,
                  int32_t* ids_out);
 
+/* ---- truncated sampling: top-k and nucleus (top-p), drawn on the device inside the per-token chain ------------------------
+ * The contract, for one row of fp32 logits z[0..V), fp32 temperature, int top_k, fp32 top_p
+ * (composer_amd.transformer.sampling_keep_set restates it on the host in numpy):
+ *   1. Order: columns are ranked by (z descending, index ascending) -- exact on the fp32 values (-0 == +0), ties at a boundary
+ *      go to the lower index, the rule of the greedy argmax.
+ *   2. top_k = 0 or top_k >= V: off.  Otherwise the candidates are the first top_k columns of the order.
+ *   3. top_p = 1: off.  Otherwise, with q_c = exp((z_c - z_max) / temperature) over the candidates of step 2, the kept set is the
+ *      shortest prefix of the order whose mass reaches top_p: the smallest n >= 1 with sum(q[:n]) >= top_p * sum(q).  The
+ *      masses are FLOAT64 on the device (logits, temperature and top_p widened to double; a fixed summation order), so against
+ *      a float64 host restatement the cumulative masses differ by summation order only (~1e-13 relative).
+ *   4. The id is the plain sampler's Gumbel-max restricted to the kept set: the same per-column hash of (seed, draw counter,
+ *      column) and the same fp32 arithmetic, so it equals, bit for bit, cmp_k_sample on a copy of the row with every dropped
+ *      column set to -inf (same seed and counter), and is one draw from softmax(z / temperature) renormalised over the kept set.
+ *   5. temperature <= 0 stays the greedy argmax: the filters are accepted and change nothing.
+ *   6. CMP_ERR_INVALID before any device work: top_k < 0, top_p outside (0, 1] or NaN.  The truncating sampler ranks the row in
+ *      LDS and takes V <= 4096; a wider vocabulary is refused, naming the limit, only when a filter is on.
+ *   7. Both filters off is the plain sampler itself: every id of every entry point without `_ex` is what it was, bit for bit,
+ *      and those entry points mean "filters off".
+ * The filters live in the device-side decode state beside the temperature: changing them re-captures nothing.
+ * cmp_k_sample with the filters: */
+int cmp_k_sample_ex(void* stream, const float* logits, int V, float temperature, int top_k, float top_p, uint64_t seed,
+                    uint32_t counter0, int n, int32_t* ids_out);
+/* cmp_decode_begin (keep = 0) and cmp_decode_begin_slide (keep >= 1, mode CMP_DECODE_KV) with the filters; cmp_decode_steps and
+ * cmp_decode_logits_get as before. */
+int cmp_decode_begin_ex(cmp_model* m, const int32_t* prompt, int P, int mode, int keep, float temperature, int top_k, float top_p,
+                        uint64_t seed);
+
 /* ---- batched decode: B independent sequences per step (1 <= B <= 256), state apart from cmp_decode_begin's ----------------
  * prompts: host int32 [B][ld], row b holds lens[b] ids (1 <= lens[b] <= window_size).  Row b samples with seed (uint32)(seed + b);
  * its i-th generated id uses draw counter i, as cmp_decode_begin does, so its first id equals cmp_decode_begin's on that prompt
@@ -253,6 +280,16 @@ int cmp_decode_batch_logits_get(cmp_model* m, float* host_out);
 /* The batched sampler on its own (dev pointers): row b of logits [B][ldz] -> ids_out[b], seed + b, draw counter `counter`. */
 int cmp_k_sample_rows(void* stream, const float* logits, int ldz, int B, int V, float temperature, uint64_t seed,
                       uint32_t counter, int32_t* ids_out);
+/* Truncated sampling (the contract above) in the batched chain, PER ROW: temperature / top_k / top_p are HOST arrays of B entries;
+ * a null array is the default for every row (temperature 1, top_k 0, top_p 1).  keep = 0: cmp_decode_batch_begin; keep >= 1
+ * (mode CMP_DECODE_KV): cmp_decode_batch_begin_slide.  Row b's ids depend on (weights, its prompt, seed + b, mode, keep, and its
+ * own temperature, top_k, top_p) only -- never on B, the graph switch or another row's parameters. */
+int cmp_decode_batch_begin_ex(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int mode, int keep,
+                              const float* temperature, const int32_t* top_k, const float* top_p, uint64_t seed);
+/* cmp_k_sample_rows with the rows' own parameters (host arrays as above, B <= 256); row b equals cmp_k_sample_ex on that row
+ * with seed + b. */
+int cmp_k_sample_rows_ex(void* stream, const float* logits, int ldz, int B, int V, const float* temperature, const int32_t* top_k,
+                         const float* top_p, uint64_t seed, uint32_t counter, int32_t* ids_out);
 
 /* ---- live kernel timing (bench.py roofline): HIP events around every launch of ONE kernel class on the
  * stream it is launched on.  cls: 0 gemm forward (A[M,K].B[K,N]), 1 gemm dgrad (B stored [N,K]), 2 gemm wgrad
