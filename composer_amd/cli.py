@@ -22,7 +22,7 @@ import numpy as np
 from . import config as cfgmod
 from . import dataset as ds
 from . import tfrecord
-from .transformer import ModelSaveFrequencyMode, Transformer
+from .transformer import ModelSaveFrequencyMode, Transformer, check_train_options
 
 
 @unique
@@ -120,6 +120,22 @@ def get_dataset(model_type, dataset_path, config, mode='', max_files=None, shuff
                            expect_settings=(d.time_step_increment, d.max_time_steps, d.velocity_bins))
 
 
+def _train_options(clip_norm=0.0, accumulate_steps=1, warmup_steps=0, source='transformer.train'):
+    try:
+        return check_train_options(clip_norm, accumulate_steps, warmup_steps)
+    except (ValueError, TypeError) as e:
+        raise click.UsageError('{}: {}'.format(source, e))
+
+
+def train_options_from(config, clip_norm=None, accumulate_steps=None, warmup_steps=None):
+    """(clip_norm, accumulate_steps, warmup_steps): the optional keys of `transformer.train` (absent in the reference's files: off),
+    overridden by the flags that were given; a bad value is a click.UsageError."""
+    t = config.transformer.train
+    pick = lambda flag, key, default: t.get(key, default) if flag is None else flag
+    return _train_options(pick(clip_norm, 'clip_norm', 0.0), pick(accumulate_steps, 'accumulate_steps', 1),
+                          pick(warmup_steps, 'warmup_steps', 0))
+
+
 def get_config_from_restoredir(restoredir):
     """cli.py:500-514"""
     path = Path(restoredir) / 'config.yml'
@@ -189,10 +205,22 @@ def summary(model_type, config_filepath):
 @click.option('--max-steps', default=None, type=int, help='Stop after this many steps (not in the reference; for smoke runs).')
 @click.option('--checkpoint-format', type=click.Choice(['npz', 'tensorbundle']), default='npz',
               help='npz (default) or the reference\'s TensorBundle files (ckpt-N.index / .data-00000-of-00001). Either is restored.')
+@click.option('--clip-norm', default=None, type=float,
+              help='Global-norm gradient clipping: 0 off, > 0 clip to this norm, inf measure only (logged as grad_norm). '
+                   'Overrides transformer.train.clip_norm.')
+@click.option('--accumulate-steps', default=None, type=int,
+              help='Micro-batches summed into one optimiser step (steps, --max-steps and --save-freq count optimiser steps). '
+                   'Overrides transformer.train.accumulate_steps.')
+@click.option('--warmup-steps', default=None, type=int,
+              help='Linear learning-rate warm-up over this many optimiser steps (0 off). Overrides transformer.train.warmup_steps.')
 def train(model_type, dataset_path, logdir, restoredir, config_filepath, epochs, use_generator, max_files,
-          save_frequency_mode, save_frequency, max_checkpoints, show_progress_bar, max_steps, checkpoint_format):
+          save_frequency_mode, save_frequency, max_checkpoints, show_progress_bar, max_steps, checkpoint_format,
+          clip_norm, accumulate_steps, warmup_steps):
     """Trains the specified model (cli.py:516-589)."""
     _require_transformer(model_type)
+    for flag, value in (('--clip-norm', clip_norm), ('--accumulate-steps', accumulate_steps), ('--warmup-steps', warmup_steps)):
+        if value is not None:                                    # refused from the arguments, before any device use
+            _train_options(**{flag[2:].replace('-', '_'): value}, source=flag)
     rank = int(os.environ.get('RANK', '0'))
     if restoredir is not None:
         config = get_config_from_restoredir(restoredir)
@@ -215,6 +243,7 @@ def train(model_type, dataset_path, logdir, restoredir, config_filepath, epochs,
                 '#########################################################'])
             with open(config.filepath) as src, open(model_logdir / 'config.yml', 'w+') as dst:
                 dst.write(banner + '\n' + src.read())
+    clip_norm, accumulate_steps, warmup_steps = train_options_from(config, clip_norm, accumulate_steps, warmup_steps)
     model, _ = create_model(model_type, config)
     rank, world = _init_distributed(model)
     _, seed = _runtime(config)
@@ -223,7 +252,8 @@ def train(model_type, dataset_path, logdir, restoredir, config_filepath, epochs,
     model.train(dataset, input_shape, model_logdir, restoredir=restoredir, epochs=epochs,
                 learning_rate=config.transformer.train.learning_rate, save_frequency_mode=save_frequency_mode,
                 save_frequency=save_frequency, max_checkpoints=max_checkpoints,
-                show_progress_bar=show_progress_bar and rank == 0, max_steps=max_steps, checkpoint_format=checkpoint_format)
+                show_progress_bar=show_progress_bar and rank == 0, max_steps=max_steps, checkpoint_format=checkpoint_format,
+                clip_norm=clip_norm, accumulate_steps=accumulate_steps, warmup_steps=warmup_steps)
     if rank == 0 and model_logdir is not None:
         click.echo(str(model_logdir))
 

@@ -852,31 +852,99 @@ __global__ __launch_bounds__(1024) void metrics_reduce_kernel(const float* __res
 //   m += (g-m)(1-b1); v += (g^2-v)(1-b2); theta -= alpha*m/(sqrt(v)+eps), alpha = lr*sqrt(1-b2^t)/(1-b1^t)
 // one flat pass over all parameters: reads theta,g,m,v (16 B/param) writes theta,m,v (12) [+2 bf16 shadow]
 // =================================================================================================
+// (the loop is shared by two kernels, textually, so that adam_kernel keeps its instructions: adam_kernel multiplies the gradient by the
+//  launch argument, adam_dev_kernel by the one float the gradient-clipping finish kernel left in device memory -- the same multiply at
+//  the same place, so a clip that does not bind changes no bit of the update)
+#define ADAM_LOOP()                                                                     \
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;                         \
+    for (; i < n4; i += (int64_t)gridDim.x * blockDim.x) {                              \
+        f32x4 pv = reinterpret_cast<f32x4*>(p)[i];                                      \
+        f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];                                \
+        f32x4 mv = reinterpret_cast<f32x4*>(m)[i];                                      \
+        f32x4 vv = reinterpret_cast<f32x4*>(v)[i];                                      \
+        _Pragma("unroll")                                                               \
+        for (int j = 0; j < 4; j++) {                                                   \
+            float gg = gv[j] * gscale;                                                  \
+            mv[j] = beta1 * mv[j] + (1.0f - beta1) * gg;                                \
+            vv[j] = beta2 * vv[j] + (1.0f - beta2) * gg * gg;                           \
+            pv[j] = pv[j] - alpha * mv[j] / (sqrtf(vv[j]) + eps);                       \
+        }                                                                               \
+        reinterpret_cast<f32x4*>(p)[i] = pv;                                            \
+        reinterpret_cast<f32x4*>(m)[i] = mv;                                            \
+        reinterpret_cast<f32x4*>(v)[i] = vv;                                            \
+        if (shadow) {                                                                   \
+            bf16x4 s;                                                                   \
+            _Pragma("unroll")                                                           \
+            for (int j = 0; j < 4; j++) s[j] = (bf16_t)pv[j];                           \
+            reinterpret_cast<bf16x4*>(shadow)[i] = s;                                   \
+        }                                                                               \
+    }
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, bf16_t* __restrict__ shadow, int64_t n4, int64_t n,
                             float alpha, float beta1, float beta2, float eps, float gscale) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
-        f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
-        f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
-        f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+    ADAM_LOOP()
+}
+__global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                float* __restrict__ v, bf16_t* __restrict__ shadow, int64_t n4, int64_t n,
+                                float alpha, float beta1, float beta2, float eps, const float* __restrict__ factor_dev) {
+    const float gscale = *factor_dev;
+    ADAM_LOOP()
+}
+#undef ADAM_LOOP
+
+// =================================================================================================
+// Global-norm gradient clipping (tf.clip_by_global_norm): norm = gscale * sqrt(sum G^2), the squares and their sum in float64.
+// grad_sumsq_kernel: workgroup c sums elements [c * CLIP_CHUNK, (c + 1) * CLIP_CHUNK) of its range (16-byte loads, every element
+// widened to double, one f64 FMA chain per vector component and lane), folds the lanes by shuffles and the four waves through LDS
+// in a fixed order, and stores ONE double to slot c with a plain store: which elements meet in which order depends on element
+// offsets alone -- no atomics, no arrival order, the same bits in G give the same double.
+// grad_clip_finish_kernel (one workgroup, the launch boundary is the only synchronisation): lane t adds slots t, t + 256, ... in
+// ascending order, the 256 lane sums are folded by a fixed tree; writes {norm, scale, factor = gscale * scale}.
+// =================================================================================================
+#define CLIP_CHUNK 8192
+struct GradClipOut { double norm; float scale; float factor; };
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n4, double* __restrict__ slots) {
+    __shared__ double sw[4];
+    const int64_t base = (int64_t)blockIdx.x * (CLIP_CHUNK / 4);
+    const int64_t lim = min(n4, base + CLIP_CHUNK / 4);
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            float gg = gv[j] * gscale;
-            mv[j] = beta1 * mv[j] + (1.0f - beta1) * gg;
-            vv[j] = beta2 * vv[j] + (1.0f - beta2) * gg * gg;
-            pv[j] = pv[j] - alpha * mv[j] / (sqrtf(vv[j]) + eps);
+    for (int r = 0; r < CLIP_CHUNK / 4 / 256; r++) {
+        const int64_t i = base + r * 256 + threadIdx.x;
+        if (i < lim) {
+            const f32x4 x = reinterpret_cast<const f32x4*>(g)[i];
+            const double d0 = (double)x[0], d1 = (double)x[1], d2 = (double)x[2], d3 = (double)x[3];
+            a0 = fma(d0, d0, a0);
+            a1 = fma(d1, d1, a1);
+            a2 = fma(d2, d2, a2);
+            a3 = fma(d3, d3, a3);
         }
-        reinterpret_cast<f32x4*>(p)[i] = pv;
-        reinterpret_cast<f32x4*>(m)[i] = mv;
-        reinterpret_cast<f32x4*>(v)[i] = vv;
-        if (shadow) {
-            bf16x4 s;
+    }
+    double a = (a0 + a1) + (a2 + a3);
 #pragma unroll
-            for (int j = 0; j < 4; j++) s[j] = (bf16_t)pv[j];
-            reinterpret_cast<bf16x4*>(shadow)[i] = s;
-        }
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) slots[blockIdx.x] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+}
+__global__ __launch_bounds__(256) void grad_clip_finish_kernel(const double* __restrict__ slots, int nslots, float gscale, float clip_norm,
+                                                               GradClipOut* __restrict__ out) {
+    __shared__ double sl[256];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < nslots; i += 256) a += slots[i];
+    sl[threadIdx.x] = a;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sl[threadIdx.x] += sl[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double norm = (double)gscale * sqrt(sl[0]);
+        // a non-finite norm gets no special case: the comparison is false and the factor is non-finite, as in TensorFlow
+        const float scale = norm <= (double)clip_norm ? 1.0f : (float)((double)clip_norm / norm);
+        out->norm = norm;
+        out->scale = scale;
+        out->factor = gscale * scale;
     }
 }
 
@@ -1445,6 +1513,46 @@ extern "C" int cmp_k_adam(void* stream, float* p, const float* g, float* m, floa
     PROF_STOP(7, s, (double)n * (28.0 + (shadow_bf16 ? 2.0 : 0.0)), (double)n * (28.0 + (shadow_bf16 ? 2.0 : 0.0)));
     KERNEL_CHECK();
     return CMP_OK;
+}
+
+extern "C" int cmp_k_adam_dev(void* stream, float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n,
+                              float lr, float beta1, float beta2, float eps, int64_t step, const float* factor_dev) {
+    CMP_REQUIRE(n % 4 == 0, "adam_dev: n=%lld must be a multiple of 4", (long long)n);
+    CMP_REQUIRE(factor_dev, "adam_dev: null factor");
+    if (n == 0) return CMP_OK;
+    hipStream_t s = (hipStream_t)stream;
+    double alpha = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
+    int64_t n4 = n / 4;
+    int grid = (int)std::min<int64_t>(cdiv64(n4, 256), 8192);
+    PROF_START(7, s);
+    adam_dev_kernel<<<grid, 256, 0, s>>>(p, g, m, v, (bf16_t*)shadow_bf16, n4, n, (float)alpha, beta1, beta2, eps, factor_dev);
+    PROF_STOP(7, s, (double)n * (28.0 + (shadow_bf16 ? 2.0 : 0.0)), (double)n * (28.0 + (shadow_bf16 ? 2.0 : 0.0)));
+    KERNEL_CHECK();
+    return CMP_OK;
+}
+
+// slots a range of n floats takes (one per CLIP_CHUNK elements); the sums of squares of [g, g + n) into slots[0, that)
+int64_t grad_sumsq_slots(int64_t n) { return cdiv64(n, CLIP_CHUNK); }
+int grad_sumsq_run(void* stream, const float* g, int64_t n, double* slots) {
+    CMP_REQUIRE(n % 4 == 0 && ((uintptr_t)g & 15) == 0, "grad_sumsq: n=%lld must be a multiple of 4 and the range 16-byte aligned", (long long)n);
+    CMP_REQUIRE(grad_sumsq_slots(n) < (1ll << 31), "grad_sumsq: n=%lld is too large", (long long)n);
+    if (n == 0) return CMP_OK;
+    grad_sumsq_kernel<<<(int)grad_sumsq_slots(n), 256, 0, (hipStream_t)stream>>>(g, n / 4, slots);
+    KERNEL_CHECK();
+    return CMP_OK;
+}
+int grad_clip_finish_run(void* stream, const double* slots, int nslots, float gscale, float clip_norm, void* out) {
+    grad_clip_finish_kernel<<<1, 256, 0, (hipStream_t)stream>>>(slots, nslots, gscale, clip_norm, (GradClipOut*)out);
+    KERNEL_CHECK();
+    return CMP_OK;
+}
+extern "C" int64_t cmp_k_grad_clip_ws(int64_t n) { return std::max<int64_t>(1, grad_sumsq_slots(n)) * 8; }
+extern "C" int cmp_k_grad_clip(void* stream, const float* g, int64_t n, float gscale, float clip_norm, void* ws, void* out) {
+    CMP_REQUIRE(g && ws && out && n > 0, "grad_clip: null argument or empty range");
+    CMP_REQUIRE(clip_norm > 0.f, "grad_clip: clip_norm %g must be positive (+inf: measure only)", (double)clip_norm);
+    CMP_REQUIRE(((uintptr_t)ws & 7) == 0 && ((uintptr_t)out & 7) == 0, "grad_clip: ws and out must be 8-byte aligned");
+    { const int rc = grad_sumsq_run(stream, g, n, (double*)ws); if (rc != CMP_OK) return rc; }
+    return grad_clip_finish_run(stream, (const double*)ws, (int)grad_sumsq_slots(n), gscale, clip_norm, out);
 }
 
 int launch_cast_bf16(hipStream_t s, const float* in, void* out, int64_t n) {

@@ -9,6 +9,8 @@
 struct DecodeState;
 struct DecodeBatchState;
 
+struct GradClipStats { double norm; float scale; float factor; };     // elementwise.hip: grad_clip_finish_kernel
+
 struct Metrics {
     double loss_sum;
     long long correct;
@@ -44,6 +46,7 @@ struct cmp_ctx {
     bool dp_on() const { return comm != nullptr || xfn != nullptr; }
     int rank = 0, nranks = 1;
     uint32_t seed_mix = 0;              // mix32(rank), xor-ed into every dropout seed: replicas draw independent masks
+    int mask_rank = 0;                  // the rank seed_mix was made from (micro-step j of k accumulated ones draws mask rank r * k + j)
     int gemm_max_wgs = 0;               // cap on the persistent GEMM grids while a communicator exists (0 = all CUs)
     hipStream_t copy_stream = nullptr;  // host -> device id uploads of the pipelined train loop
     SchedWs gemm_sched;                 // item counters of the persistent GEMMs launched on `stream` (gemm.hip: sched_next)
@@ -186,6 +189,18 @@ struct cmp_model {
     int dp_msgs_step = 0;              // all-reduce calls of the last step
     int dp_buckets_updated = 0;        // buckets of the step being enqueued whose Adam update is already on the communication stream
     bool poisoned = false;             // a data-parallel step failed after some of them: parameters partially stepped (train steps refuse)
+    // train options (cmp_train_options): global-norm clipping and gradient accumulation
+    float clip_norm = 0.f;             // 0 off, > 0 on, +inf measure only
+    int accum_steps = 1;               // k: micro-steps per optimiser step
+    int accum_pending = 0;             // micro-steps of the current group already enqueued (their gradients are summed in G)
+    int accumB = 0, accumT = 0;        // ... and their shape
+    double* clip_slots = nullptr;      // device: one float64 partial sum of squares per CLIP_CHUNK elements (grad_sumsq_kernel)
+    int64_t clip_slots_cap = 0;
+    int64_t clip_slots_used = 0;       // data-parallel step being enqueued: slots handed to the buckets so far
+    GradClipStats* clip_out = nullptr;     // device: what grad_clip_finish_kernel wrote for the last clipped step
+    GradClipStats* clip_host = nullptr;    // pinned [1 + STAGES]: the last step's, then one per staging slot
+    bool last_has_norm = false;        // the last enqueued step computed a norm
+    bool stage_has_norm[3] = {false, false, false};
     std::vector<char> reload_seen;     // while poisoned: which parameters cmp_param_set has replaced since (all of them clears the flag)
     int ln_fused_mode = -1;            // COMPOSER_LN_FUSED as read when the model was created (-1 unset, 0 off, 2 training passes too)
     DecodeState* dec = nullptr;
@@ -239,6 +254,9 @@ int lnf_fold_prep_run(void* stream, const float* wte, const float* gamma, const 
 int colsum_run(void* stream, const void* X, int ldx, float* out, int rows, int cols, int dtype, float* det_ws, size_t det_ws_bytes);
 int launch_metrics_reduce(hipStream_t s, const float* row_loss, const int32_t* row_correct, int rows, void* metrics);
 int launch_cast_bf16(hipStream_t s, const float* in, void* out, int64_t n);
+int64_t grad_sumsq_slots(int64_t n);
+int grad_sumsq_run(void* stream, const float* g, int64_t n, double* slots);
+int grad_clip_finish_run(void* stream, const double* slots, int nslots, float gscale, float clip_norm, void* out);
 // model.hip
 int ensure_workspace(cmp_model* m, int B, int T);
 int model_forward(cmp_model* m, const int32_t* x_dev, int B, int T, bool training, int64_t step, int past_len = 0);

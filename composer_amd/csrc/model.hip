@@ -188,6 +188,7 @@ extern "C" int cmp_dp_init(cmp_ctx* c, int rank, int nranks, const void* id128) 
     c->rank = rank;
     c->nranks = nranks;
     c->seed_mix = mix32((uint32_t)rank);      // seed ^ mix32(rank): rank 0 keeps the model seed, the others draw their own masks
+    c->mask_rank = rank;
     return CMP_OK;
 }
 extern "C" int cmp_dp_init_exchange(cmp_ctx* c, int rank, int nranks, int (*fn)(void*, void*, int64_t, void*), void* user) {
@@ -198,6 +199,7 @@ extern "C" int cmp_dp_init_exchange(cmp_ctx* c, int rank, int nranks, int (*fn)(
     c->rank = rank;
     c->nranks = nranks;
     c->seed_mix = mix32((uint32_t)rank);
+    c->mask_rank = rank;
     return CMP_OK;
 }
 // sum of p[0, n) over the ranks, in place, ordered on the communication stream: RCCL, or the caller's exchange function
@@ -216,6 +218,7 @@ static int dp_allreduce(cmp_ctx* c, float* p, size_t n) {
 extern "C" int cmp_dp_set_mask_rank(cmp_ctx* c, int rank) {
     CMP_REQUIRE(c && rank >= 0, "dp_set_mask_rank: bad arguments");
     c->seed_mix = mix32((uint32_t)rank);
+    c->mask_rank = rank;
     return CMP_OK;
 }
 extern "C" int cmp_dp_set_gemm_cus(cmp_ctx* c, int cus) {
@@ -408,6 +411,7 @@ extern "C" int cmp_model_destroy(cmp_model* m) {
     for (auto& wg : m->wgrad_groups) wgrad_group_free(&wg);
     wgrad_ws_free(&m->wgrad_ws);
     if (m->metrics_host) hipHostFree(m->metrics_host);
+    if (m->clip_host) hipHostFree(m->clip_host);
     if (m->stage_metrics) hipHostFree(m->stage_metrics);
     for (int i = 0; i < cmp_model::STAGES; i++) {
         if (m->stage_host[i]) hipHostFree(m->stage_host[i]);
@@ -940,6 +944,9 @@ static int adam_range(cmp_model* m, hipStream_t s, int64_t begin, int64_t end, f
 // Runs whenever a communicator exists, also with ONE rank (RCCL then copies in place): the 1-GPU tests and a 1-rank
 // launched bench execute exactly the event / side-stream / ncclAllReduce sequence of the 8-GPU job.
 // update == false: gradients only (cmp_loss_and_grads).
+// With clipping on (m->clip_norm > 0) no bucket can be updated before the norm of the WHOLE gradient exists: the bucket's sum of
+// squares goes out behind its all-reduce instead (its own run of slots, in the order the backward pass completes the buckets), and
+// adam() finishes the norm and updates the whole flat buffer behind the last bucket, still on the communication stream.
 static int bucket_ready(cmp_model* m, int ev, int64_t begin, int64_t end, float lr, bool update) {
     cmp_ctx* c = m->ctx;
     if (!c->dp_on()) return CMP_OK;
@@ -948,21 +955,28 @@ static int bucket_ready(cmp_model* m, int ev, int64_t begin, int64_t end, float 
     CHECK_RC(dp_allreduce(c, m->G + begin, (size_t)(end - begin)));
     m->dp_bytes_step += (end - begin) * 4;
     m->dp_msgs_step += 1;
-    if (update) {
-        CHECK_RC(adam_range(m, c->comm_stream, begin, end, lr, m->iterations + 1, 1.0f / (float)c->nranks));
+    if (update && m->clip_norm > 0.f) {
+        const int64_t ns = grad_sumsq_slots(end - begin);
+        CMP_REQUIRE(m->clip_slots && m->clip_slots_used + ns <= m->clip_slots_cap, "train step: gradient-norm workspace too small");
+        CHECK_RC(grad_sumsq_run(c->comm_stream, m->G + begin, end - begin, m->clip_slots + m->clip_slots_used));
+        m->clip_slots_used += ns;
+    } else if (update) {
+        CHECK_RC(adam_range(m, c->comm_stream, begin, end, lr, m->iterations + 1, 1.0f / (float)(c->nranks * m->accum_steps)));
         m->dp_buckets_updated += 1;
     }
     return CMP_OK;
 }
 
 // reverse mode of forward() (tf.GradientTape, transformer.py:916-920); formulas in SURVEY appendix A
-static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t step, bool allreduce, float lr = 0.f, bool update = false) {
+// zero == false: the gradients are ADDED to what G holds (micro-steps 2 .. k of an accumulated optimiser step)
+static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t step, bool allreduce, float lr = 0.f, bool update = false,
+                    bool zero = true) {
     Range range_("composer.backward");
     hipStream_t s = m->ctx->stream;
     const int E = m->E, Ea = m->Ea, M = B * T, dt = m->dtype, V = m->V;
     const float pr = m->cfg.resid_dropout, pa = m->cfg.attn_dropout;
     const bool ln = m->cfg.use_layer_norm != 0;
-    HIP_CHECK(hipMemsetAsync(m->G, 0, (size_t)m->total * 4, s));
+    if (zero) HIP_CHECK(hipMemsetAsync(m->G, 0, (size_t)m->total * 4, s));
     // tied logits: dwte += dZ^T.hf ; dhf = dZ.wte
     {
         // few output tiles (390 x 512 = 4 of 256x256): on the 128x128 kernel the launch is 768 workgroups of a 48th of the tokens each
@@ -1158,9 +1172,36 @@ static int dp_fold(cmp_model* m, int slot, bool all) {
     return CMP_OK;
 }
 
+// the compute stream waits for the metrics all-reduce of a micro-step that does not update (no timed events: cmp_dp_stats counts
+// optimiser steps)
+static int dp_metrics_end(cmp_model* m) {
+    cmp_ctx* c = m->ctx;
+    if (!c->dp_on()) return CMP_OK;
+    HIP_CHECK(hipEventRecord(m->comm_done, c->comm_stream));
+    HIP_CHECK(hipStreamWaitEvent(c->stream, m->comm_done, 0));
+    dp_metrics_unpack_kernel<<<1, 64, 0, c->stream>>>(m->metrics, m->dp_metrics);
+    KERNEL_CHECK();
+    return CMP_OK;
+}
+
+// Adam on the whole flat buffer with the factor grad_clip_finish_kernel leaves in device memory (clipping on)
+static int adam_clipped(cmp_model* m, hipStream_t s, int nslots, float lr, int64_t step, float gscale) {
+    CHECK_RC(grad_clip_finish_run(s, m->clip_slots, nslots, gscale, m->clip_norm, m->clip_out));
+    return cmp_k_adam_dev(s, m->P, m->G, m->Am, m->Av, m->S ? (void*)m->S : nullptr, m->total, lr, 0.9f, 0.999f, 1e-7f, step,
+                          &m->clip_out->factor);
+}
+
 static int adam(cmp_model* m, float lr) {
     Range range_("composer.adam");
     cmp_ctx* c = m->ctx;
+    const bool clip = m->clip_norm > 0.f;
+    const float gscale = 1.0f / (float)(c->nranks * m->accum_steps);
+    if (clip && c->dp_on()) {
+        // every bucket's all-reduce and sum of squares is on the communication stream: the norm, then ONE update of the whole buffer
+        // behind them (not hidden behind the backward pass: it sits in the end-of-step wait below)
+        CHECK_RC(adam_clipped(m, c->comm_stream, (int)m->clip_slots_used, lr, m->iterations + 1, gscale));
+        m->dp_buckets_updated = m->L + 2;
+    }
     m->iterations += 1;
     m->param_version += 1;
     if (c->dp_on()) {
@@ -1183,7 +1224,11 @@ static int adam(cmp_model* m, float lr) {
         KERNEL_CHECK();
         return CMP_OK;
     }
-    return adam_range(m, c->stream, 0, m->total, lr, m->iterations, 1.0f);
+    if (clip) {
+        CHECK_RC(grad_sumsq_run(c->stream, m->G, m->total, m->clip_slots));
+        return adam_clipped(m, c->stream, (int)grad_sumsq_slots(m->total), lr, m->iterations, gscale);
+    }
+    return adam_range(m, c->stream, 0, m->total, lr, m->iterations, gscale);
 }
 
 extern "C" int cmp_dp_stats(cmp_model* m, int reset, int64_t* steps, double* exposed_ms, int64_t* bytes_per_step, int* msgs_per_step) {
@@ -1279,6 +1324,62 @@ __global__ void sanitize_ids_kernel(const int32_t* __restrict__ x, const int32_t
     if (nbad) atomicAdd(bad, nbad);
 }
 
+// Inside a group of accumulated micro-steps every call has the shape of the first (checked before anything is enqueued; the
+// pending group is kept)
+static int accum_shape_check(cmp_model* m, int B, int T) {
+    CMP_REQUIRE(m->accum_pending == 0 || (B == m->accumB && T == m->accumT),
+                "train step: micro-step %d of %d has shape [%d,%d], the group's first had [%d,%d]", m->accum_pending + 1, m->accum_steps, B,
+                T, m->accumB, m->accumT);
+    return CMP_OK;
+}
+
+// {norm, scale, factor} of a clipped step to pinned memory (slot 0: the last step's; 1 + s: staging slot s); behind the step
+static int fetch_clip(cmp_model* m, int slot) {
+    if (!m->last_has_norm) return CMP_OK;
+    HIP_CHECK(hipMemcpyAsync(&m->clip_host[slot], m->clip_out, sizeof(GradClipStats), hipMemcpyDeviceToHost, m->ctx->stream));
+    return CMP_OK;
+}
+
+extern "C" int cmp_train_options(cmp_model* m, float clip_norm, int accum_steps) {
+    CMP_REQUIRE(m, "train_options: null model");
+    CMP_REQUIRE(clip_norm >= 0.f, "train_options: clip_norm %g is not 0 (off), positive or +inf (measure only)", (double)clip_norm);
+    CMP_REQUIRE(accum_steps >= 1, "train_options: accum_steps %d must be at least 1", accum_steps);
+    // every writer of the gradient buffer adds to it (split-K and grouped weight gradients in the atomic, slab and last-arriver
+    // forms, bias column sums, LayerNorm parameter partials, both embedding backward forms) -- except wgrad_ln_fix_kernel, which
+    // rewrites two accumulated weight gradients of every block in place
+    CMP_REQUIRE(accum_steps == 1 || m->ln_fused_mode != 3, "train_options: COMPOSER_LN_FUSED=3 transforms the weight gradients in place and "
+                "cannot accumulate (accum_steps %d)", accum_steps);
+    HIP_CHECK(hipSetDevice(m->ctx->device));
+    if (clip_norm > 0.f && !m->clip_slots) {
+        // one run of slots per gradient bucket (a bucket's last slot may be partial), or one run over the whole buffer
+        const int64_t cap = grad_sumsq_slots(m->total) + m->L + 2;
+        CHECK_RC(dev_alloc(m, &m->clip_out, sizeof(GradClipStats)));
+        HIP_CHECK(hipHostMalloc((void**)&m->clip_host, sizeof(GradClipStats) * (1 + cmp_model::STAGES), hipHostMallocDefault));
+        memset(m->clip_host, 0, sizeof(GradClipStats) * (1 + cmp_model::STAGES));
+        CHECK_RC(dev_alloc(m, &m->clip_slots, (size_t)cap * 8));
+        m->clip_slots_cap = cap;
+    }
+    m->clip_norm = clip_norm;
+    m->accum_steps = accum_steps;
+    m->accum_pending = 0;              // a partial group is discarded: the next micro-step zeroes G
+    return CMP_OK;
+}
+extern "C" int cmp_train_options_get(cmp_model* m, float* clip_norm, int* accum_steps, int* pending_micro_steps) {
+    CMP_REQUIRE(m, "train_options_get: null model");
+    if (clip_norm) *clip_norm = m->clip_norm;
+    if (accum_steps) *accum_steps = m->accum_steps;
+    if (pending_micro_steps) *pending_micro_steps = m->accum_pending;
+    return CMP_OK;
+}
+extern "C" int cmp_train_grad_stats(cmp_model* m, float* norm, float* scale) {
+    CMP_REQUIRE(m, "train_grad_stats: null model");
+    HIP_CHECK(hipSetDevice(m->ctx->device));
+    HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+    if (norm) *norm = m->last_has_norm ? (float)m->clip_host[0].norm : NAN;
+    if (scale) *scale = m->last_has_norm ? m->clip_host[0].scale : 1.0f;
+    return CMP_OK;
+}
+
 // the step itself on ids already in HBM and already known to be in range
 static int train_step_enqueue(cmp_model* m, const int32_t* x_dev, const int32_t* y_dev, int B, int T, float lr) {
     // everything that can be checked is checked before anything is enqueued: in a data-parallel job the peers are already in the
@@ -1286,13 +1387,30 @@ static int train_step_enqueue(cmp_model* m, const int32_t* x_dev, const int32_t*
     CMP_REQUIRE(lr >= 0.f && lr == lr, "train step: learning rate %g is not a non-negative number", (double)lr);
     CMP_REQUIRE(!m->poisoned, "train step: an earlier data-parallel step failed after some gradient buckets had been all-reduced and "
                 "applied (parameters are partially stepped and may differ between replicas): reload a checkpoint on every rank");
+    CHECK_RC(accum_shape_check(m, B, T));
     const int64_t step = m->iterations;
-    CHECK_RC(model_forward(m, x_dev, B, T, true, step));
-    CHECK_RC(loss(m, y_dev, B * T, true));
-    CHECK_RC(dp_metrics_begin(m));
+    // Accumulation: call j (0-based) of a group of k adds its gradients to G; only the last one all-reduces and updates.  It draws the
+    // dropout masks of mask rank r * k + j (k = 1: r, today's masks; k micro-batches on one GPU: the masks of a k-rank job).
+    const int k = m->accum_steps, j = m->accum_pending;
+    const bool final_ = j == k - 1;
+    const uint32_t seed_mix = m->ctx->seed_mix;
+    if (k > 1) m->ctx->seed_mix = mix32((uint32_t)(m->ctx->mask_rank * k + j));
+    m->last_has_norm = false;
     m->dp_buckets_updated = 0;
-    int rc = backward(m, x_dev, B, T, step, true, lr, true);
-    if (rc == CMP_OK) rc = adam(m, lr);
+    m->clip_slots_used = 0;
+    int rc = model_forward(m, x_dev, B, T, true, step);
+    if (rc == CMP_OK) rc = loss(m, y_dev, B * T, true);
+    if (rc == CMP_OK) rc = dp_metrics_begin(m);
+    if (rc == CMP_OK) rc = backward(m, x_dev, B, T, step, final_, lr, final_, j == 0);
+    m->ctx->seed_mix = seed_mix;
+    if (rc == CMP_OK) rc = final_ ? adam(m, lr) : dp_metrics_end(m);
+    if (rc == CMP_OK) {
+        m->accum_pending = final_ ? 0 : j + 1;
+        m->accumB = B; m->accumT = T;
+        m->last_has_norm = final_ && m->clip_norm > 0.f;
+    } else {
+        m->accum_pending = 0;          // G holds part of a micro-batch: the group cannot be completed
+    }
     if (rc != CMP_OK && m->ctx->dp_on()) {
         // Buckets already handed to the communication stream keep running (all-reduce + Adam): the compute stream must not touch
         // G / P before they are done (the next step's memset of G would race them), and a model whose buckets were partly
@@ -1313,6 +1431,7 @@ static int train_step_enqueue(cmp_model* m, const int32_t* x_dev, const int32_t*
 
 extern "C" int cmp_train_step_dev(cmp_model* m, const void* x_dev, const void* y_dev, int B, int T, float lr) {
     CMP_REQUIRE(m && x_dev && y_dev, "train_step_dev: null argument");
+    CHECK_RC(accum_shape_check(m, B, T));
     HIP_CHECK(hipSetDevice(m->ctx->device));
     CHECK_RC(ensure_workspace(m, B, T));
     hipStream_t s = m->ctx->stream;
@@ -1322,6 +1441,7 @@ extern "C" int cmp_train_step_dev(cmp_model* m, const void* x_dev, const void* y
     KERNEL_CHECK();
     CHECK_RC(train_step_enqueue(m, m->x_dev, m->y_dev, B, T, lr));
     CHECK_RC(fetch_metrics(m));
+    CHECK_RC(fetch_clip(m, 0));
     return CMP_OK;
 }
 
@@ -1346,7 +1466,10 @@ extern "C" int cmp_train_step_graph_probe(cmp_model* m, const void* x_dev, const
     HIP_CHECK(hipStreamSynchronize(s));
     const int64_t it = m->iterations, pv = m->param_version, gen = m->fwd_gen, stv = m->st_version;
     const int sts = m->st_state, lB = m->lastB, lT = m->lastT, lP = m->last_past;
-    const bool fl = m->fused_last, hv = m->hf_valid;
+    const bool fl = m->fused_last, hv = m->hf_valid, hn = m->last_has_norm;
+    const int ap = m->accum_pending, aB = m->accumB, aT = m->accumT;
+    m->accum_pending = m->accum_steps - 1;         // the FINAL micro-step under the current options (accum_steps 1: the whole step)
+    m->accumB = B; m->accumT = T;
     // (precondition: the grouped weight-gradient item tables of this shape exist, i.e. one train step of the shape has EXECUTED --
     //  building them synchronises the stream, which a capture cannot do; wgrad_group_run says so when it happens)
     HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -1355,6 +1478,7 @@ extern "C" int cmp_train_step_graph_probe(cmp_model* m, const void* x_dev, const
     const hipError_t e = hipStreamEndCapture(s, &g);
     m->iterations = it; m->param_version = pv; m->fwd_gen = gen; m->st_version = stv; m->st_state = sts;
     m->lastB = lB; m->lastT = lT; m->last_past = lP; m->fused_last = fl; m->hf_valid = hv;
+    m->accum_pending = ap; m->accumB = aB; m->accumT = aT; m->last_has_norm = hn;
     if (rc != CMP_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
     HIP_CHECK(e);
     size_t n = 0;
@@ -1449,6 +1573,7 @@ static int ensure_stages(cmp_model* m, int64_t tokens) {
 
 extern "C" int cmp_train_step_async(cmp_model* m, const int32_t* x, const int32_t* y, int B, int T, float lr, int64_t* ticket) {
     CMP_REQUIRE(m && x && y && ticket, "train_step_async: null argument");
+    CHECK_RC(accum_shape_check(m, B, T));
     HIP_CHECK(hipSetDevice(m->ctx->device));
     CHECK_RC(ensure_workspace(m, B, T));
     const int64_t n = (int64_t)B * T;
@@ -1468,6 +1593,9 @@ extern "C" int cmp_train_step_async(cmp_model* m, const int32_t* x, const int32_
     CHECK_RC(train_step_enqueue(m, m->stage_dev[slot], m->stage_dev[slot] + n, B, T, lr));
     HIP_CHECK(hipMemcpyAsync(&m->stage_metrics[slot], m->metrics, sizeof(Metrics), hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipMemcpyAsync(m->metrics_host, m->metrics, sizeof(Metrics), hipMemcpyDeviceToHost, c->stream));
+    CHECK_RC(fetch_clip(m, 0));
+    CHECK_RC(fetch_clip(m, 1 + slot));
+    m->stage_has_norm[slot] = m->last_has_norm;
     HIP_CHECK(hipEventRecord(m->stage_done[slot], c->stream));
     m->stage_ticket[slot] = tk;
     m->next_ticket = tk + 1;
@@ -1475,6 +1603,14 @@ extern "C" int cmp_train_step_async(cmp_model* m, const int32_t* x, const int32_
     return CMP_OK;
 }
 
+extern "C" int cmp_train_metrics_wait_ex(cmp_model* m, int64_t ticket, float* loss_out, float* acc_out, float* norm, float* scale) {
+    CHECK_RC(cmp_train_metrics_wait(m, ticket, loss_out, acc_out));
+    const int slot = (int)(ticket % cmp_model::STAGES);
+    const bool has = m->stage_has_norm[slot];
+    if (norm) *norm = has ? (float)m->clip_host[1 + slot].norm : NAN;
+    if (scale) *scale = has ? m->clip_host[1 + slot].scale : 1.0f;
+    return CMP_OK;
+}
 extern "C" int cmp_train_metrics_wait(cmp_model* m, int64_t ticket, float* loss_out, float* acc_out) {
     CMP_REQUIRE(m, "train_metrics_wait: null model");
     const int slot = (int)(ticket % cmp_model::STAGES);
@@ -1490,10 +1626,12 @@ extern "C" int cmp_train_metrics_wait(cmp_model* m, int64_t ticket, float* loss_
 extern "C" int cmp_train_step(cmp_model* m, const int32_t* x, const int32_t* y, int B, int T, float lr, float* loss_out,
                               float* acc_out) {
     CMP_REQUIRE(m && x && y, "train_step: null argument");
+    CHECK_RC(accum_shape_check(m, B, T));
     HIP_CHECK(hipSetDevice(m->ctx->device));
     CHECK_RC(upload_xy(m, x, y, B, T));
     CHECK_RC(train_step_enqueue(m, m->x_dev, m->y_dev, B, T, lr));
     CHECK_RC(fetch_metrics(m));
+    CHECK_RC(fetch_clip(m, 0));
     if (loss_out || acc_out) CHECK_RC(cmp_train_metrics(m, loss_out, acc_out));
     return CMP_OK;
 }
@@ -1504,6 +1642,7 @@ extern "C" int cmp_loss_and_grads(cmp_model* m, const int32_t* x, const int32_t*
     HIP_CHECK(hipSetDevice(m->ctx->device));
     CHECK_RC(upload_xy(m, x, y, B, T));
     const int64_t step = m->iterations;
+    m->accum_pending = 0;          // (never part of a group: it zeroes G, so a pending group ends here)
     CHECK_RC(model_forward(m, m->x_dev, B, T, true, step));
     CHECK_RC(loss(m, m->y_dev, B * T, true));
     CHECK_RC(backward(m, m->x_dev, B, T, step, false));

@@ -111,6 +111,36 @@ class Presents:
         return (self[i] for i in range(len(self)))
 
 
+def clip_scale(norm, clip_norm):
+    """The factor global-norm clipping multiplies the gradient by (tf.clip_by_global_norm): 1 if norm <= clip_norm, else
+    clip_norm / norm.  clip_norm 0 means off (1), +inf measures only (1); a NaN norm gives NaN -- no special case."""
+    norm, clip_norm = float(norm), float(clip_norm)
+    if clip_norm == 0.0:
+        return 1.0
+    if norm != norm:
+        return float('nan')
+    return 1.0 if norm <= clip_norm else clip_norm / norm
+
+
+def warmup_lr(learning_rate, step, warmup_steps):
+    """lr(step) = learning_rate * min(1, step / warmup_steps), step = the optimiser step counted from 1; warmup_steps 0: off."""
+    if not warmup_steps:
+        return float(learning_rate)
+    return float(learning_rate) * min(1.0, float(step) / float(warmup_steps))
+
+
+def check_train_options(clip_norm, accumulate_steps, warmup_steps=0):
+    """Range checks shared by Transformer.set_train_options, Transformer.train and the CLI (ValueError names the option)."""
+    clip_norm = float(clip_norm)
+    if not clip_norm >= 0.0:
+        raise ValueError('clip_norm {}: must be 0 (off), positive, or inf (measure only).'.format(clip_norm))
+    if int(accumulate_steps) != accumulate_steps or int(accumulate_steps) < 1:
+        raise ValueError('accumulate_steps {}: must be an integer >= 1.'.format(accumulate_steps))
+    if int(warmup_steps) != warmup_steps or int(warmup_steps) < 0:
+        raise ValueError('warmup_steps {}: must be an integer >= 0 (0 = off).'.format(warmup_steps))
+    return clip_norm, int(accumulate_steps), int(warmup_steps)
+
+
 class Transformer:
     def __init__(self, vocab_size, embedding_size, window_size, decoder_layers_count,
                  attention_head_count, use_relative_attention=False, initializer_mean=0,
@@ -463,6 +493,32 @@ class Transformer:
         _lib.check(self._lib.cmp_train_metrics_wait(self._h, int(ticket), C.byref(loss), C.byref(acc)), 'cmp_train_metrics_wait')
         return loss.value, acc.value
 
+    def set_train_options(self, clip_norm=0.0, accumulate_steps=1):
+        """cmp_train_options: global-norm clipping (0 off, > 0 on, inf measure only) and gradient accumulation (train_step* become
+        micro-steps; every `accumulate_steps`-th call updates).  Discards a pending partial group."""
+        clip_norm, accumulate_steps, _ = check_train_options(clip_norm, accumulate_steps)
+        _lib.check(self._lib.cmp_train_options(self._h, clip_norm, accumulate_steps), 'cmp_train_options')
+
+    def train_options(self):
+        """{'clip_norm', 'accumulate_steps', 'pending_micro_steps'} (cmp_train_options_get)."""
+        c, k, p = C.c_float(), C.c_int(), C.c_int()
+        _lib.check(self._lib.cmp_train_options_get(self._h, C.byref(c), C.byref(k), C.byref(p)), 'cmp_train_options_get')
+        return {'clip_norm': c.value, 'accumulate_steps': k.value, 'pending_micro_steps': p.value}
+
+    def grad_stats(self):
+        """(norm | None, scale) of the last enqueued step: the global gradient norm and the clip scale applied; None / 1.0 when no
+        norm was computed (clipping off, or a micro-step that did not update).  Synchronises like last_metrics."""
+        n, sc = C.c_float(), C.c_float()
+        _lib.check(self._lib.cmp_train_grad_stats(self._h, C.byref(n), C.byref(sc)), 'cmp_train_grad_stats')
+        return (None if n.value != n.value else n.value), sc.value
+
+    def step_metrics_ex(self, ticket):
+        """(loss, accuracy, norm | None, scale) of the step `ticket` was issued for (cmp_train_metrics_wait_ex)."""
+        loss, acc, n, sc = C.c_float(), C.c_float(), C.c_float(), C.c_float()
+        _lib.check(self._lib.cmp_train_metrics_wait_ex(self._h, int(ticket), C.byref(loss), C.byref(acc), C.byref(n), C.byref(sc)),
+                   'cmp_train_metrics_wait_ex')
+        return loss.value, acc.value, (None if n.value != n.value else n.value), sc.value
+
     def last_metrics(self):
         loss, acc = C.c_float(), C.c_float()
         _lib.check(self._lib.cmp_train_metrics(self._h, C.byref(loss), C.byref(acc)), 'cmp_train_metrics')
@@ -669,7 +725,15 @@ class Transformer:
     # ------------------------------------------------------------------ train loop (transformer.py:846-960)
     def train(self, dataset, input_shape, logdir, restoredir=None, epochs=None, learning_rate=1e-3,
               save_frequency_mode=ModelSaveFrequencyMode.EPOCH, save_frequency=1, max_checkpoints=1,
-              show_progress_bar=True, max_steps=None, checkpoint_format='npz'):
+              show_progress_bar=True, max_steps=None, checkpoint_format='npz', clip_norm=0.0, accumulate_steps=1, warmup_steps=0):
+        """clip_norm / accumulate_steps: set_train_options; warmup_steps: warmup_lr.  With accumulate_steps = k > 1 every dataset batch is
+        a micro-batch: `step`, max_steps and save_frequency count OPTIMISER steps, the logged loss / accuracy of a step are the means
+        over its k micro-batches, a group may span an epoch boundary, checkpoints are written at group boundaries only and a partial
+        group left at the end is discarded."""
+        clip_norm, k, warmup_steps = check_train_options(clip_norm, accumulate_steps, warmup_steps)
+        if clip_norm != 0.0 or k != 1 or hasattr(self._lib, 'cmp_train_options'):   # (an older library as the other arm of an A/B lacks it)
+            self.set_train_options(clip_norm, k)
+        clip_on = clip_norm > 0.0
         logdir = Path(logdir) if logdir is not None else None
         if restoredir is not None:
             logdir = Path(restoredir)                                            # :884-885
@@ -686,6 +750,7 @@ class Transformer:
                 logging.error('Failed to restore model from \'{}\'.'.format(restoredir))
                 exit(1)
         summary = ckpt.ScalarLog(logdir / 'train') if rank == 0 else None        # :903
+        first_step = step
         save_frequency_mode = ModelSaveFrequencyMode(save_frequency_mode)
         history = []
 
@@ -695,45 +760,66 @@ class Transformer:
             return manager.save(self.state_dict(), {'step': step, 'epoch': epoch})
 
         done = False
+        group = []                                                               # (loss, accuracy) of the retired micro-steps of the open group
+        micro = 0                                                                # micro-steps submitted into the open group
         while (epochs is None or epoch < epochs) and not done:                   # :907 (epoch starts at 1)
             logging.info('Epoch {}'.format(epoch if epochs is None else '{}/{}'.format(epoch, epochs)))
             ep_loss, ep_correct, ep_n, t0 = 0.0, 0.0, 0, time.time()
             # The device runs up to two steps ahead of this loop: step s is submitted (ids uploaded on the copy stream behind
             # step s-1) and the metrics of step s-1 are read and logged while s computes.  Logged values, their step numbers
             # and the checkpoint contents are those of the reference's synchronous loop (a save first drains the pipeline).
-            pending = []                                                         # [(ticket, step number)]
+            pending = []                                                         # [(ticket, step number, lr, last micro-step of its group)]
+            ep_batches = 0
 
             def retire(upto):
                 nonlocal ep_loss, ep_correct
                 while len(pending) > upto:
-                    tk, st = pending.pop(0)
-                    loss, acc = self.step_metrics(tk)
+                    tk, st, lr, last = pending.pop(0)
+                    if k == 1 and not clip_on:
+                        loss, acc = self.step_metrics(tk)
+                    else:                                                        # means over the micro-batches; the last one holds the norm
+                        loss, acc, norm, _ = self.step_metrics_ex(tk)
+                        group.append((loss, acc))
+                        if not last:
+                            continue
+                        loss, acc = sum(v[0] for v in group) / len(group), sum(v[1] for v in group) / len(group)
+                        del group[:]
                     ep_loss += loss; ep_correct += acc
                     history.append((st, loss, acc))
                     if summary:
                         summary.scalar('loss', loss, st)                         # :933-936
                         summary.scalar('accuracy', acc, st)
+                        if clip_on:
+                            summary.scalar('grad_norm', float('nan') if norm is None else norm, st)
+                        if warmup_steps:
+                            summary.scalar('learning_rate', lr, st)
                     if show_progress_bar and rank == 0 and (st % 10 == 1):
                         print('\r- loss: {:.4f} - accuracy: {:.4f}'.format(loss, acc), end='', flush=True)   # :939
 
             for x, y in dataset:                                                 # :914
-                pending.append((self.train_step_async(x, y, learning_rate), step))
-                ep_n += 1
+                lr = warmup_lr(learning_rate, step, warmup_steps)
+                micro += 1
+                ep_batches += 1
+                pending.append((self.train_step_async(x, y, lr), step, lr, micro == k))
                 retire(1)
+                if micro < k:                                                    # a micro-step that does not update: no optimiser step yet
+                    continue
+                micro = 0
+                ep_n += 1
                 if save_frequency_mode == ModelSaveFrequencyMode.GLOBAL_STEP and step % save_frequency == 0:
                     retire(0)
                     path = save()                                                # :941-943
                     if path and show_progress_bar:
                         print('\nSaved checkpoint for step {} at {}.'.format(step, path))
                 step += 1                                                        # :945
-                if max_steps is not None and len(history) + len(pending) >= max_steps:
+                if max_steps is not None and step - first_step >= max_steps:
                     done = True
                     break
             retire(0)
-            if ep_n == 0:
+            if ep_batches == 0:
                 logging.error('The dataset yielded no batches.')
                 break
-            if summary:
+            if summary and ep_n:
                 summary.scalar('epoch_loss', ep_loss / ep_n, epoch)              # :949-951
                 summary.scalar('epoch_accuracy', ep_correct / ep_n, epoch)
             if save_frequency_mode == ModelSaveFrequencyMode.EPOCH and epoch % save_frequency == 0:
@@ -741,6 +827,9 @@ class Transformer:
                 if path and show_progress_bar:
                     print('\nSaved checkpoint for epoch {} at {}.'.format(epoch, path))
             epoch += 1                                                           # :960
+        if micro:
+            logging.info('Discarding a partial group of {} micro-batch(es) (accumulate_steps {}).'.format(micro, k))
+            self.set_train_options(clip_norm, k)
         if summary:
             summary.close()
         return history

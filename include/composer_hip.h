@@ -148,7 +148,8 @@ int cmp_train_step(cmp_model* m, const int32_t* x, const int32_t* y, int B, int 
 int cmp_train_step_dev(cmp_model* m, const void* x_dev, const void* y_dev, int B, int T, float lr);
 int cmp_train_metrics(cmp_model* m, float* loss, float* acc);        /* syncs; last step's values */
 /* Diagnostic (bench.py `default_cfg.launches`): the kernel launches (and memset / copy nodes) ONE train step of this shape enqueues,
- * counted on a stream capture of the step that is then dropped -- nothing executes, no state changes.  Single-process models only. */
+ * counted on a stream capture of the step that is then dropped -- nothing executes, no state changes.  Single-process models only.
+ * Under cmp_train_options it is the FINAL micro-step of a group that is counted / replayed (accum_steps 1: the whole step). */
 int cmp_train_step_launches(cmp_model* m, const void* x_dev, const void* y_dev, int B, int T, int* kernels, int* others);
 /* The same capture, instantiated and replayed `replay_reps` times back to back: milliseconds per replay (measurement only -- every
  * replay repeats the captured step's dropout masks and Adam iteration, the model is not a training run afterwards).  What a hipGraph of
@@ -160,6 +161,36 @@ int cmp_train_step_graph_probe(cmp_model* m, const void* x_dev, const void* y_de
  * finished and returns its loss/accuracy.  At most 3 steps are in flight (a 4th submit waits for the oldest). */
 int cmp_train_step_async(cmp_model* m, const int32_t* x, const int32_t* y, int B, int T, float lr, int64_t* ticket);
 int cmp_train_metrics_wait(cmp_model* m, int64_t ticket, float* loss, float* acc);
+/* ---- train options: global-norm gradient clipping and gradient accumulation -------------------
+ * N ranks, k = accum_steps; G = the flat fp32 gradient buffer after the last micro-batch of an optimiser step and after the
+ * all-reduce: the SUM over micro-batches and ranks (the tied wte gradient once, as stored; padding words zero).  gscale = 1/(k*N);
+ * the gradient Adam applies is gscale * G.
+ * Accumulation (k > 1): cmp_train_step / _dev / _async become micro-steps.  Calls 1 .. k-1 of a group run forward, loss and backward
+ * and add into G: no gradient all-reduce, no Adam; iterations, parameters, m and v do not change.  Call k adds its gradient,
+ * all-reduces the buckets, updates with gscale and increments iterations once.  Every call returns its own micro-batch's loss and
+ * accuracy (the 3-float metrics all-reduce stays per call).  G is zeroed only by the first micro-step of a group.  All micro-steps of
+ * a group have the shape (B, T) of the first: another shape is CMP_ERR_INVALID before anything is enqueued, the pending group is
+ * kept.  Dropout: micro-step j (0-based) draws the masks cmp_dp_set_mask_rank(r * k + j) would select, r the mask rank in force; the
+ * optimiser iteration is the same for the whole group (k = 1: today's masks; k micro-batches on one GPU: the masks of a k-rank job).
+ * cmp_loss_and_grads never takes part in a group (it zeroes G: a pending group ends there).  After a group's final step
+ * cmp_param_get(kind = 3) returns G, the SUM.  Every mode accumulates except COMPOSER_LN_FUSED=3 (refused here, by name).
+ * Clipping: clip_norm 0 off, > 0 on, +inf measure only.  norm = gscale * sqrt(sum G^2), squares and sum in FLOAT64 on the device in a
+ * fixed order (no float atomic, no arrival order: the same bits in G and the same bucket layout give the same double; between no
+ * communicator and a 1-rank communicator the norm may differ by float64 summation order only).  scale = 1 if norm <= clip_norm, else
+ * clip_norm / norm (tf.clip_by_global_norm).  Adam multiplies every gradient element by ONE fp32 number, factor = gscale * scale,
+ * read from device memory, exactly where it multiplies by 1/N today: a clip that does not bind changes no bit of the update.  A
+ * non-finite norm gets no special case (factor and parameters become non-finite, as in TensorFlow; the reported norm shows it).
+ * With a communicator and clipping on, no bucket is updated before the last all-reduce has been enqueued: each bucket's sum of
+ * squares follows its all-reduce on the communication stream, then the norm and ONE Adam launch over the whole buffer.
+ * clip_norm: 0 off, > 0 on, +inf measure only; accum_steps >= 1.
+ * CMP_ERR_INVALID: negative or NaN clip, accum_steps < 1, a mode that cannot accumulate.  Discards a pending partial group. */
+int cmp_train_options(cmp_model* m, float clip_norm, int accum_steps);
+int cmp_train_options_get(cmp_model* m, float* clip_norm, int* accum_steps, int* pending_micro_steps);
+/* Last enqueued step: norm (NaN when no norm was computed: clipping off, or a non-final micro-step), scale (1 then).
+ * Syncs like cmp_train_metrics. */
+int cmp_train_grad_stats(cmp_model* m, float* norm, float* scale);
+/* The same for the step a ticket was issued for. */
+int cmp_train_metrics_wait_ex(cmp_model* m, int64_t ticket, float* loss, float* acc, float* norm, float* scale);
 /* forward+backward only (no all-reduce, no Adam): gradients readable with cmp_param_get(kind=3) */
 int cmp_loss_and_grads(cmp_model* m, const int32_t* x, const int32_t* y, int B, int T,
                        float* loss, float* acc);
@@ -434,6 +465,16 @@ int cmp_k_softmax_xent(void* stream, const float* logits, int ldz, const int32_t
 /* Keras Adam (transformer.py:887,921): eps outside the bias correction; step = optimizer.iterations+1 */
 int cmp_k_adam(void* stream, float* p, const float* g, float* m, float* v, void* shadow_bf16,
                int64_t n, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale);
+/* cmp_k_adam with the factor read from device memory (the float cmp_k_grad_clip leaves in out.factor): the same multiply at the
+ * same place, bitwise equal to cmp_k_adam with grad_scale = *factor_dev. */
+int cmp_k_adam_dev(void* stream, float* p, const float* g, float* m, float* v, void* shadow_bf16,
+                   int64_t n, float lr, float beta1, float beta2, float eps, int64_t step, const float* factor_dev);
+/* Global-norm clipping at kernel level: sum of squares + finish on n floats (n % 4 == 0, g 16-byte aligned); ws >=
+ * cmp_k_grad_clip_ws(n) bytes; out = {double norm; float scale; float factor}: norm = gscale * sqrt(sum g^2) with the squares and
+ * their sum in float64 in a fixed order (no atomics: the same bits give the same double), scale = 1 if norm <= clip_norm else
+ * clip_norm / norm, factor = gscale * scale.  clip_norm > 0 (+inf: measure only). */
+int64_t cmp_k_grad_clip_ws(int64_t n);
+int cmp_k_grad_clip(void* stream, const float* g, int64_t n, float gscale, float clip_norm, void* ws, void* out);
 
 #ifdef __cplusplus
 }
