@@ -364,7 +364,8 @@ int cmp_k_layernorm_bwd_fused(void* stream, const void* dy, const void* x, const
  * epilogue: +bias[N] (fp32, may be NULL); act: 0 none, 1 gelu (pre-activation stored to aux if aux!=NULL),
  * 2 multiply by gelu'(aux[m,n]); dropout (p>0) then +resid[m,n] (may be NULL).  out_fp32: C is fp32 regardless of
  * dtype.  splitk>1: fp32 atomic accumulation into C (C must be pre-zeroed or hold the value to add to).
- * dropout index = row*ldc + col (ldc == N for the model's outputs). */
+ * The dropout mask of element (m, n) is a function of (seed, rng_stream, m, n) only -- the oracle's dropout_keep_rows over [M, N] --
+ * independent of ldc. */
 int cmp_k_gemm(void* stream, int dtype, int ta, int tb, int M, int N, int K,
                const void* A, int lda, const void* Bm, int ldb, void* C, int ldc,
                const float* bias, int act, void* aux, int ldaux, const void* resid, int ldr,

@@ -179,16 +179,24 @@ def test_grouped_weight_gradients_last_arriver_form_is_bitwise_reproducible(lib,
 
 
 def test_gemm_bf16_ragged_k_zero_padded(lib):
-    """dH = dZ.wte: K = V = 390 with dZ rows zero-padded to 448 (CMP_GEMM_KPAD_ZERO) takes the fast path."""
+    """dH = dZ.wte: K = V = 390 with dZ rows zero-padded to 448 (CMP_GEMM_KPAD_ZERO) takes the fast path.  The operands live in a
+    guard-banded arena (tests/kernel_arena.py): the memory right after B IS a band of NaN bytes, so a load past B's last row
+    that reached the product would show in every output element; range-checked loads keep it out."""
+    from kernel_arena import Arena
     M, N, K, ld = 300, 128, 390, 448
     g = torch.Generator().manual_seed(1)
     a = torch.zeros(M, ld); a[:, :K] = torch.randn(M, K, generator=g)
-    A, B = dev(a, BF16), dev(torch.randn(K, N, generator=g), BF16)
-    junk = dev(torch.full((64, N), 1e4), BF16)      # memory right after B must not leak in: range-checked loads
-    ref = A.double()[:, :K] @ B.double()
+    b = torch.randn(K, N, generator=g)
     for flags in (1, 2):
-        out = gemm(lib, BF16, 0, 0, A, B, M, N, K, flags=flags)
-        assert rel_err(out, ref) < TOL[BF16]
+        ar = Arena("cuda", 2 << 20)
+        A = ar.operand(a, torch.bfloat16, M, ld, ld, name="A")            # columns 390..448 are the contract's zeros
+        B = ar.operand(b, torch.bfloat16, K, N, N, name="B")              # flush against its guard
+        Cm = ar.output(torch.bfloat16, M, N, N, name="C")
+        ar.arm()
+        ck(lib, lib.cmp_k_gemm(stream(), BF16, 0, 0, M, N, K, P(A.t), ld, P(B.t), N, P(Cm.t), N, None, 0, None, 0, None, 0, 0, 1, 0.0, 0, 0, flags))
+        ar.check()
+        ref = A.host().double()[:, :K] @ B.host().double()
+        assert rel_err(Cm.host(), ref) < TOL[BF16]
 
 
 @pytest.mark.parametrize("dtype", [FP32, BF16])
