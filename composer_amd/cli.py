@@ -318,16 +318,30 @@ def evaluate(model_type, dataset_path, restoredir, use_generator, max_files):
 @click.option('--top-p', default=1.0, type=float,
               help='Nucleus sampling: sample from the smallest set of most likely events whose probability (after --temperature '
                    'and --top-k) reaches P, in (0, 1]; 1 = off. Defaults to 1.')
+@click.option('--constrain/--no-constrain', default=False,
+              help='Event-grammar decoding: never sample an event the MIDI conversion would ignore in the current state (a NOTE_OFF of '
+                   'a silent pitch, a NOTE_ON of a sounding one, a pedal event that changes nothing). Defaults to off, the '
+                   'reference\'s sampler.')
+@click.option('--pitch-range', default=None, metavar='LO:HI',
+              help='Never sample a NOTE_ON of a pitch outside LO..HI (MIDI pitches, 0 <= LO <= HI <= 127).')
 @click.option('--num-samples', default=1, type=click.IntRange(1, 256),
               help='Number of sequences to generate from the prompt, decoded together; sample i uses seed + i and goes to '
                    'OUTPUT-i.mid (or OUTPUT-i.data). Defaults to 1.')
 def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt_data, prompt_length, generate_length,
-             temperature, decode_mode, slide_keep, top_k, top_p, num_samples):
+             temperature, decode_mode, slide_keep, top_k, top_p, constrain, pitch_range, num_samples):
     """Generate a MIDI file (cli.py:617-680): MIDI prompt -> event ids -> model -> event ids -> MIDI.  An output path
     ending in `.data` gets the event ids in the dataset's binary format instead of a MIDI file.  With --num-samples N > 1
     the N sequences are decoded as one batch and written to OUTPUT-0 ... OUTPUT-{N-1} (same suffix); --top-k / --top-p apply
-    to every sample."""
+    to every sample, and so do --constrain / --pitch-range."""
     from composer_amd import notes as nt
+    from composer_amd import grammar as gm
+    if pitch_range is not None:                                  # refused from the arguments, before any device use
+        try:
+            lo, hi = (int(t) for t in pitch_range.split(':'))
+            if not 0 <= lo <= hi <= 127:
+                raise ValueError
+        except ValueError:
+            raise click.UsageError('--pitch-range {}: LO:HI with 0 <= LO <= HI <= 127.'.format(pitch_range))
     if top_k < 0:                                                # refused from the arguments, before any device use
         raise click.UsageError('--top-k {}: must be >= 0 (0 = off).'.format(top_k))
     if not 0.0 < top_p <= 1.0:
@@ -378,6 +392,14 @@ def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt
     slide = {'slide_keep': slide_keep} if decode_mode == 'kv-slide' else {}
     if top_k or top_p < 1.0:
         slide.update(top_k=top_k, top_p=top_p)
+    if constrain or pitch_range is not None:
+        # the layout always (the pitch range is stated in it); the dynamic rules only with --constrain
+        g = gm.EventGrammar.from_dataset_params(d.time_step_increment, d.max_time_steps, d.velocity_bins,
+                                                rules=gm.ALL if constrain else 0)
+        slide.update(grammar=g)
+        if pitch_range is not None:
+            slide.update(banned_ids=g.pitch_range_bans(lo, hi))
+        click.echo('grammar: constrain {} pitch-range {}'.format('on' if constrain else 'off', pitch_range or 'off'), err=True)
     if num_samples == 1:
         ids = model.generate(x, generate_length, temperature=temperature, mode=decode_mode, **slide)
         _write_generated(list(x) + ids.tolist(), out, d)         # prompt + generated (cli.py:676)

@@ -32,6 +32,7 @@ struct DecState {        // device-resident loop state
     unsigned seed;       // graph does not depend on them and survives from one cmp_decode_begin to the next
     int top_k;           // truncated sampling (decode_common.h): 0 or >= V: off
     float top_p;         // 1: off
+    DecGrammar gr;       // event grammar (decode_common.h): layout, rules and the fold of prompt ++ ids so far
 };
 
 struct DecLayerW {
@@ -60,6 +61,7 @@ struct DecodeState {
     // sliding-window mode (cmp_decode_begin_slide): the prompt stays on the device beside the generated ids, so that the tail a
     // slide re-encodes is gathered without a host round trip
     int32_t* prompt = nullptr;          // [W]
+    unsigned* banw = nullptr;           // static bans of the event grammar, ceil(V / 32) words at a fixed address (zero: none)
     int P = 0, keep = 0;                // keep == 0: plain kv / literal decode
     int64_t row_slides = 0, fwd_calls = 0;
 };
@@ -456,12 +458,13 @@ __global__ __launch_bounds__(256) void dec_sample2_kernel(const float* __restric
                                                           DecState* __restrict__ st,
                                                           int32_t* __restrict__ ids, const float* __restrict__ wte,
                                                           const float* __restrict__ wpe, float* __restrict__ x, int E,
-                                                          int first) {
+                                                          int first, const unsigned* __restrict__ banw) {
     extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
     __shared__ int bi[4];
     const int tid = threadIdx.x;
     const float* z = logits + ldz_row_off;
+    const GramRegs g0 = grammar_read(&st->gr);          // the grammar state the draw sees: in registers before thread 0 moves it on
     const unsigned ctr = st->rng;
     const float temperature = st->temperature;
     const int top_k = st->top_k;
@@ -474,13 +477,14 @@ __global__ __launch_bounds__(256) void dec_sample2_kernel(const float* __restric
     float pe[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) { const int e = tid + 256 * i; pe[i] = e < E ? wpe[(int64_t)posc * E + e] : 0.f; }
-    const int id = sample_block_any(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, trunc_lds);
+    const int id = sample_block_grammar(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, trunc_lds, g0, banw);
     if (tid == 0) {
         if (nprod < capI) ids[nprod] = id;
         st->produced = nprod + 1;
         st->rng = ctr + 1;
         st->token = id;
         st->pos = pos;
+        grammar_advance(&st->gr, g0, id);
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) { const int e = tid + 256 * i; if (e < E) x[e] = wte[(int64_t)id * E + e] + pe[i]; }
@@ -514,6 +518,95 @@ extern "C" int cmp_k_sample(void* stream, const float* logits, int V, float temp
     return cmp_k_sample_ex(stream, logits, V, temperature, 0, 1.0f, seed, counter0, n, ids_out);
 }
 
+// cmp_k_sample_ex with a device bit vector of banned columns: the banning samplers of the event grammar on their own
+__global__ __launch_bounds__(256) void sample_many_banned_kernel(const float* __restrict__ z, int V, float temperature, int top_k,
+                                                                 float top_p, const unsigned* __restrict__ banw, unsigned seed,
+                                                                 unsigned counter0, int32_t* __restrict__ ids) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    const int id = sample_block_banned(z, V, temperature, top_k, top_p, seed, counter0 + blockIdx.x, bv, bi, trunc_lds,
+                                       ban_static(banw));
+    if (threadIdx.x == 0) ids[blockIdx.x] = id;
+}
+
+extern "C" int cmp_k_sample_banned(void* stream, const float* logits, int V, float temperature, int top_k, float top_p,
+                                   const uint32_t* banned_dev, uint64_t seed, uint32_t counter0, int n, int32_t* ids_out) {
+    CMP_REQUIRE(logits && ids_out && banned_dev && V > 0 && n >= 0, "k_sample_banned: bad arguments");
+    CHECK_RC(sampling_check("k_sample_banned", V, temperature, top_k, top_p));
+    if (n == 0) return CMP_OK;
+    sample_many_banned_kernel<<<n, 256, trunc_lds_bytes(V), (hipStream_t)stream>>>(logits, V, temperature, top_k, top_p, banned_dev,
+                                                                                   (unsigned)seed, counter0, ids_out);
+    KERNEL_CHECK();
+    return CMP_OK;
+}
+
+// ---- event grammar: configuration and state read-back of both chains (composer_hip.h) ----
+extern "C" int cmp_decode_grammar(cmp_model* m, int batched, const cmp_event_grammar* g, const uint32_t* banned_words) {
+    CMP_REQUIRE(m, "decode_grammar: null model");
+    const int V = m->V, nw = grammar_words(V);
+    DecGrammarCfg c;
+    if (g) {
+        CMP_REQUIRE((g->rules & ~CMP_GRAMMAR_ALL) == 0, "decode_grammar: unknown rule bits 0x%x (known: 0x%x)", g->rules, CMP_GRAMMAR_ALL);
+        CMP_REQUIRE(g->time_shift_n >= 1, "decode_grammar: time_shift_n=%d must be >= 1", g->time_shift_n);
+        CMP_REQUIRE((g->sustain_on < 0) == (g->sustain_off < 0), "decode_grammar: sustain_on=%d without sustain_off=%d (or the reverse): "
+                    "both ids, or -1 for both", g->sustain_on, g->sustain_off);
+        CMP_REQUIRE(g->sustain_on >= -1 && g->sustain_off >= -1, "decode_grammar: sustain ids %d / %d: an id, or -1 for both",
+                    g->sustain_on, g->sustain_off);
+        struct R { const char* name; int64_t lo, n; };
+        const R rg[5] = {{"note_on", g->note_on0, 128}, {"note_off", g->note_off0, 128}, {"time_shift", g->time_shift0, g->time_shift_n},
+                         {"sustain_on", g->sustain_on, 1}, {"sustain_off", g->sustain_off, 1}};
+        const int nr = g->sustain_on < 0 ? 3 : 5;
+        for (int i = 0; i < nr; i++)
+            CMP_REQUIRE(rg[i].lo >= 0 && rg[i].lo + rg[i].n <= V, "decode_grammar: %s ids [%lld, %lld) outside the vocabulary [0, %d)",
+                        rg[i].name, (long long)rg[i].lo, (long long)(rg[i].lo + rg[i].n), V);
+        for (int i = 0; i < nr; i++)
+            for (int j = i + 1; j < nr; j++)
+                CMP_REQUIRE(rg[i].lo + rg[i].n <= rg[j].lo || rg[j].lo + rg[j].n <= rg[i].lo,
+                            "decode_grammar: the %s ids [%lld, %lld) overlap the %s ids [%lld, %lld)", rg[i].name, (long long)rg[i].lo,
+                            (long long)(rg[i].lo + rg[i].n), rg[j].name, (long long)rg[j].lo, (long long)(rg[j].lo + rg[j].n));
+        c.has_layout = true;
+        c.g = *g;
+    }
+    if (banned_words) {
+        c.words.assign(banned_words, banned_words + nw);
+        if (V & 31) c.words[nw - 1] &= (1u << (V & 31)) - 1u;       // bits at or above V name no column
+        auto clear_in = [&](int lo, int n) {
+            for (int id = lo; id < lo + n; id++)
+                if (!((c.words[id >> 5] >> (id & 31)) & 1u)) return true;
+            return false;
+        };
+        if (g) CMP_REQUIRE(clear_in(g->time_shift0, g->time_shift_n), "decode_grammar: the static vector bans every TIME_SHIFT id "
+                           "[%d, %d): at least one must stay drawable", g->time_shift0, g->time_shift0 + g->time_shift_n);
+        else CMP_REQUIRE(clear_in(0, V), "decode_grammar: the static vector bans all %d ids: at least one must stay drawable", V);
+    }
+    m->gram[batched ? 1 : 0] = c;          // read by the chain's next begin
+    return CMP_OK;
+}
+
+int decode_grammar_state(cmp_model* m, int row, uint32_t sounding[4], int32_t* pedal, int64_t* time_steps) {
+    DecodeState* d = m->dec;
+    if (!d || !d->begun) {
+        cmp_set_error("decode_grammar_state: call cmp_decode_begin first");
+        return CMP_ERR_STATE;
+    }
+    CMP_REQUIRE(row == 0, "decode_grammar_state: row %d of the batch-1 chain (row 0 only)", row);
+    HIP_CHECK(hipSetDevice(m->ctx->device));
+    HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+    DecState h;
+    HIP_CHECK(hipMemcpy(&h, d->st, sizeof(h), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; i++) sounding[i] = h.gr.sounding[i];
+    *pedal = h.gr.pedal;
+    *time_steps = h.gr.time_steps;
+    return CMP_OK;
+}
+
+extern "C" int cmp_decode_grammar_state(cmp_model* m, int batched, int row, uint32_t sounding[4], int32_t* pedal, int64_t* time_steps) {
+    CMP_REQUIRE(m && sounding && pedal && time_steps, "decode_grammar_state: null argument");
+    return batched ? decode_batch_grammar_state(m, row, sounding, pedal, time_steps)
+                   : decode_grammar_state(m, row, sounding, pedal, time_steps);
+}
+
 // Sliding window (cmp_decode_begin_slide).  The re-encode input of a slide: the last `keep` tokens of prompt ++ ids, t0 = the
 // index of the first of them in that sequence.
 __global__ void dec_slide_gather_kernel(const int32_t* __restrict__ prompt, int P, const int32_t* __restrict__ ids, int t0, int keep,
@@ -530,14 +623,15 @@ __global__ void dec_slide_gather_kernel(const int32_t* __restrict__ prompt, int 
 __global__ __launch_bounds__(256) void dec_slide_sample_kernel(const float* __restrict__ z, int V, DecState* __restrict__ st,
                                                                int32_t* __restrict__ ids, const float* __restrict__ wte,
                                                                const float* __restrict__ wpe, float* __restrict__ x, int E, int keep,
-                                                               float* __restrict__ zout) {
+                                                               float* __restrict__ zout, const unsigned* __restrict__ banw) {
     extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
     __shared__ int bi[4];
     const int tid = threadIdx.x;
     const unsigned ctr = st->rng;
     const int nprod = st->produced, capI = st->cap;
-    const int id = sample_block_any(z, V, st->temperature, st->top_k, st->top_p, st->seed, ctr, bv, bi, trunc_lds);
+    const GramRegs g0 = grammar_read(&st->gr);
+    const int id = sample_block_grammar(z, V, st->temperature, st->top_k, st->top_p, st->seed, ctr, bv, bi, trunc_lds, g0, banw);
     __syncthreads();                    // every thread has read the state before thread 0 moves it on
     if (tid == 0) {
         if (nprod < capI) ids[nprod] = id;
@@ -545,6 +639,7 @@ __global__ __launch_bounds__(256) void dec_slide_sample_kernel(const float* __re
         st->rng = ctr + 1;
         st->token = id;
         st->pos = keep;
+        grammar_advance(&st->gr, g0, id);
     }
     for (int e = tid; e < E; e += 256) x[e] = wte[(int64_t)id * E + e] + wpe[(int64_t)keep * E + e];
     for (int c = tid; c < V; c += 256) zout[c] = z[c];
@@ -621,7 +716,7 @@ static int enqueue_token_step2(cmp_model* m, DecodeState* d) {
     CHECK_RC(launch_gemv2(s, 0, 1, d->x, m->P + m->off_lnf_g, m->P + m->off_lnf_b, eps, m->P + m->off_wte, nullptr, nullptr,
                           d->logits, nullptr, E, m->V, m->D));
     dec_sample2_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(d->logits, 0, m->V, d->st, d->ids, m->P + m->off_wte,
-                                                             m->P + m->off_wpe, d->x, E, 0);
+                                                             m->P + m->off_wpe, d->x, E, 0, d->banw);
     KERNEL_CHECK();
     return CMP_OK;
 }
@@ -682,6 +777,7 @@ static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mod
         CHECK_RC(dalloc(d, &d->r, (size_t)E * 4));
         CHECK_RC(dalloc(d, &d->g, (size_t)4 * E * 4));
         CHECK_RC(dalloc(d, &d->logits, (size_t)m->ldz * 4));
+        CHECK_RC(dalloc(d, &d->banw, (size_t)grammar_words(m->V) * 4));
         d->lw.resize(L);
         for (int i = 0; i < L; i++) {
             DecLayerW& w = d->lw[i];
@@ -730,7 +826,7 @@ static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mod
             KERNEL_CHECK();
         }
     }
-    DecState h;
+    DecState h = {};
     h.pos = (mode == CMP_DECODE_KV) ? P : 0;     // position of the first generated token when it is fed back
     h.token = 0;
     h.produced = 0;
@@ -742,10 +838,12 @@ static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mod
     h.seed = (unsigned)seed;
     h.top_k = top_k;
     h.top_p = top_p;
+    h.gr = grammar_begin(m->gram[0], prompt, P);
+    HIP_CHECK(grammar_upload(m->gram[0], m->V, d->banw, s));
     HIP_CHECK(hipMemcpyAsync(d->st, &h, sizeof(h), hipMemcpyHostToDevice, s));
     // first id from the last prompt row (cli.py:673 `[-1, 0]`)
     dec_sample2_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(m->logits, (P - 1) * m->ldz, m->V, d->st, d->ids, m->P + m->off_wte,
-                                                             m->P + m->off_wpe, d->x, E, 1);
+                                                             m->P + m->off_wpe, d->x, E, 1, d->banw);
     KERNEL_CHECK();
     HIP_CHECK(hipStreamSynchronize(s));
     d->produced = 1;
@@ -811,7 +909,7 @@ static int enqueue_slide(cmp_model* m, DecodeState* d) {
         KERNEL_CHECK();
     }
     dec_slide_sample_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(m->logits + (int64_t)(keep - 1) * m->ldz, m->V, d->st, d->ids, m->P + m->off_wte,
-                                              m->P + m->off_wpe, d->x, m->E, keep, d->logits);
+                                              m->P + m->off_wpe, d->x, m->E, keep, d->logits, d->banw);
     KERNEL_CHECK();
     d->row_slides++;
     d->fwd_calls++;

@@ -34,6 +34,7 @@ struct DecRow {          // device-resident per-row loop state (the captured cha
                          // appends nor reads, the sampler leaves the row alone; the row's slide, run after the replay, clears it
     int top_k;           // truncated sampling (decode_common.h), per row: 0 or >= V: off
     float top_p;         // 1: off
+    DecGrammar gr;       // event grammar (decode_common.h): layout, rules and the fold of the row's prompt ++ ids so far
 };
 
 struct DecRowList {      // rows of one slide, by value in the kernel arguments: no host buffer has to outlive an enqueued step
@@ -54,6 +55,8 @@ struct DecodeBatchState {
     std::vector<DecBatchLayerW> lw;
     std::vector<void*> row_allocs;      // sized by capB (replaced when a larger B is asked for)
     std::vector<void*> w_allocs;        // transposed weights (independent of B)
+    unsigned* banw = nullptr;           // static bans of the event grammar, ceil(V / 32) words shared by all rows (in w_allocs: its
+                                        // address outlives every captured chain)
     std::map<int, std::pair<hipGraph_t, hipGraphExec_t>> graphs;     // captured chain per B
     bool graph_on = true;
     int64_t weights_version = -1;
@@ -356,14 +359,16 @@ __global__ void decb_cache_fill_kernel(const T* __restrict__ qkv, float* __restr
 __global__ __launch_bounds__(256) void decb_sample_kernel(const float* __restrict__ logits, int ldz, int V, DecRow* __restrict__ st,
                                                           int row0, int32_t* __restrict__ ids, int cap,
                                                           const float* __restrict__ wte, const float* __restrict__ wpe,
-                                                          float* __restrict__ x, int E, int W, int first) {
+                                                          float* __restrict__ x, int E, int W, int first,
+                                                          const unsigned* __restrict__ banw) {
     extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
     __shared__ int bi[4];
     const int tid = threadIdx.x, b = row0 + blockIdx.x;
     const float* z = logits + (int64_t)blockIdx.x * ldz;
     DecRow* rs = st + b;
-    if (rs->hold) return;                  // the row's slide draws this step's id (workgroup-uniform)
+    if (rs->hold) return;                  // the row's slide draws this step's id (workgroup-uniform); its grammar state stays
+    const GramRegs g0 = grammar_read(&rs->gr);          // the grammar state the draw sees: in registers before thread 0 moves it on
     const unsigned ctr = rs->rng;
     const float temperature = rs->temperature;
     const unsigned seed = rs->seed;
@@ -371,13 +376,14 @@ __global__ __launch_bounds__(256) void decb_sample_kernel(const float* __restric
     const int pos = first ? pos0 : (adv ? pos0 + 1 : 0);
     const int posc = min(pos, W - 1);      // host refuses to step past the table; never index outside it
     float* xr = x + (int64_t)b * E;
-    const int id = sample_block_any(z, V, temperature, rs->top_k, rs->top_p, seed, ctr, bv, bi, trunc_lds);
+    const int id = sample_block_grammar(z, V, temperature, rs->top_k, rs->top_p, seed, ctr, bv, bi, trunc_lds, g0, banw);
     if (tid == 0) {
         if (nprod < cap) ids[(int64_t)b * cap + nprod] = id;
         rs->produced = nprod + 1;
         rs->rng = ctr + 1;
         rs->token = id;
         rs->pos = pos;
+        grammar_advance(&rs->gr, g0, id);
     }
     for (int e = tid; e < E; e += 256) xr[e] = wte[(int64_t)id * E + e] + wpe[(int64_t)posc * E + e];
 }
@@ -423,7 +429,8 @@ __global__ void decb_slide_fill_kernel(const T* __restrict__ qkv, float* __restr
 __global__ __launch_bounds__(256) void decb_slide_sample_kernel(const float* __restrict__ logits, int ldz, int V, DecRow* __restrict__ st,
                                                                 DecRowList rl, int r0, int32_t* __restrict__ ids, int cap,
                                                                 const float* __restrict__ wte, const float* __restrict__ wpe,
-                                                                float* __restrict__ x, int E, int keep, float* __restrict__ zout) {
+                                                                float* __restrict__ x, int E, int keep, float* __restrict__ zout,
+                                                                const unsigned* __restrict__ banw) {
     extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
     __shared__ int bi[4];
@@ -432,7 +439,8 @@ __global__ __launch_bounds__(256) void decb_slide_sample_kernel(const float* __r
     DecRow* rs = st + b;
     const unsigned ctr = rs->rng;
     const int nprod = rs->produced;
-    const int id = sample_block_any(z, V, rs->temperature, rs->top_k, rs->top_p, rs->seed, ctr, bv, bi, trunc_lds);
+    const GramRegs g0 = grammar_read(&rs->gr);
+    const int id = sample_block_grammar(z, V, rs->temperature, rs->top_k, rs->top_p, rs->seed, ctr, bv, bi, trunc_lds, g0, banw);
     __syncthreads();                       // every thread has read the state before thread 0 moves it on
     if (tid == 0) {
         if (nprod < cap) ids[(int64_t)b * cap + nprod] = id;
@@ -441,6 +449,7 @@ __global__ __launch_bounds__(256) void decb_slide_sample_kernel(const float* __r
         rs->token = id;
         rs->pos = keep;
         rs->hold = 0;
+        grammar_advance(&rs->gr, g0, id);
     }
     float* xr = x + (int64_t)b * E;
     for (int e = tid; e < E; e += 256) xr[e] = wte[(int64_t)id * E + e] + wpe[(int64_t)keep * E + e];
@@ -550,7 +559,7 @@ static int enqueue_batch_step(cmp_model* m, DecodeBatchState* d, int B) {
     CHECK_RC(launch_proj(s, 0, 1, d->x, m->P + m->off_lnf_g, m->P + m->off_lnf_b, eps, m->P + m->off_wte, nullptr, nullptr,
                          d->logits, m->ldz, nullptr, E, m->V, m->D, B));
     decb_sample_kernel<<<B, 256, trunc_lds_bytes(m->V), s>>>(d->logits, m->ldz, m->V, d->st, 0, d->ids, d->cap, m->P + m->off_wte, m->P + m->off_wpe,
-                                         d->x, E, m->W, 0);
+                                         d->x, E, m->W, 0, d->banw);
     KERNEL_CHECK();
     return CMP_OK;
 }
@@ -628,6 +637,7 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
             w.kc = w.vc = nullptr;
         }
     }
+    if (!d->banw) CHECK_RC(balloc(d->w_allocs, &d->banw, (size_t)grammar_words(m->V) * 4));
     if (d->graph_on != graph_on) {
         HIP_CHECK(hipStreamSynchronize(s));
         decb_drop_graphs(d);
@@ -654,7 +664,7 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
         }
         d->weights_version = m->param_version;
     }
-    std::vector<DecRow> h(B);
+    std::vector<DecRow> h(B, DecRow{});
     d->pos.assign(B, 0);
     for (int b = 0; b < B; b++) {
         h[b].pos = (mode == CMP_DECODE_KV) ? lens[b] : 0;     // position of the row's first generated token when it is fed back
@@ -667,10 +677,12 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
         h[b].hold = 0;
         h[b].top_k = top_k ? top_k[b] : 0;
         h[b].top_p = top_p ? top_p[b] : 1.0f;
+        h[b].gr = grammar_begin(m->gram[1], prompts + (int64_t)b * ld, lens[b]);
         d->pos[b] = h[b].pos;
     }
     d->keep = keep;
     d->row_slides = d->fwd_calls = 0;
+    HIP_CHECK(grammar_upload(m->gram[1], m->V, d->banw, s));
     HIP_CHECK(hipMemcpyAsync(d->st, h.data(), (size_t)B * sizeof(DecRow), hipMemcpyHostToDevice, s));
     if (keep > 0) HIP_CHECK(hipMemcpyAsync(d->plen, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
     // prefill, one row at a time through the batch-1 path's forward call; the host prompt upload is stream-ordered, so the
@@ -695,7 +707,7 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
         }
         // first id from the row's last prompt position (cli.py:673 `[-1, 0]`), seed + b, draw counter 0
         decb_sample_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(m->logits + (int64_t)(P - 1) * m->ldz, m->ldz, m->V, d->st, b, d->ids, d->cap,
-                                             m->P + m->off_wte, m->P + m->off_wpe, d->x, E, W, 1);
+                                             m->P + m->off_wte, m->P + m->off_wpe, d->x, E, W, 1, d->banw);
         KERNEL_CHECK();
         HIP_CHECK(hipStreamSynchronize(s));
     }
@@ -769,7 +781,7 @@ static int enqueue_batch_slide(cmp_model* m, DecodeBatchState* d, const DecRowLi
             KERNEL_CHECK();
         }
         decb_slide_sample_kernel<<<nc, 256, trunc_lds_bytes(m->V), s>>>(m->logits, m->ldz, m->V, d->st, rl, r0, d->ids, d->cap, m->P + m->off_wte,
-                                                    m->P + m->off_wpe, d->x, m->E, keep, d->logits);
+                                                    m->P + m->off_wpe, d->x, m->E, keep, d->logits, d->banw);
         KERNEL_CHECK();
         d->fwd_calls++;
     }
@@ -784,6 +796,23 @@ int decode_batch_slide_stats(DecodeBatchState* d, int64_t* row_slides, int64_t* 
     }
     *row_slides = d->row_slides;
     *forward_calls = d->fwd_calls;
+    return CMP_OK;
+}
+
+int decode_batch_grammar_state(cmp_model* m, int row, uint32_t sounding[4], int32_t* pedal, int64_t* time_steps) {
+    DecodeBatchState* d = m->decb;
+    if (!d || !d->begun) {
+        cmp_set_error("decode_grammar_state: call cmp_decode_batch_begin first");
+        return CMP_ERR_STATE;
+    }
+    CMP_REQUIRE(row >= 0 && row < d->B, "decode_grammar_state: row %d outside the batch of %d rows", row, d->B);
+    HIP_CHECK(hipSetDevice(m->ctx->device));
+    HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+    DecRow h;
+    HIP_CHECK(hipMemcpy(&h, d->st + row, sizeof(h), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; i++) sounding[i] = h.gr.sounding[i];
+    *pedal = h.gr.pedal;
+    *time_steps = h.gr.time_steps;
     return CMP_OK;
 }
 

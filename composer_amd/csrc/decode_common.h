@@ -59,18 +59,135 @@ __device__ __forceinline__ int block_argmax(float best, int arg, float* bv, int*
     return id;
 }
 
+// ---- event grammar (composer_hip.h, "event-grammar decoding") ----------------------------------------------------------------
+// The per-row state of the grammar beside the sampling parameters in DecState / DecRow: the caller's id layout, the rule bits and
+// the fold of prompt ++ ids so far.  `layout` = 0: no layout was given (no dynamic rule, the state never moves); `active` = 0: no
+// rule and no static bit -- the kernels that draw then call today's sampler and nothing else.
+struct DecGrammar {
+    int note_on0, note_off0, time_shift0, time_shift_n, sustain_on, sustain_off;
+    unsigned rules;          // CMP_GRAMMAR_* bits (0 without a layout)
+    int layout;
+    int active;
+    int pedal;
+    unsigned sounding[4];    // bit p: pitch p sounds
+    long long time_steps;    // sum over the TIME_SHIFT events of the sequence, id time_shift0 + j counting j + 1
+};
+
+// the transition NoteSequence.from_events implements, for one id: the prompt's fold in the begin functions (host)
+static inline void grammar_step(DecGrammar& g, int id) {
+    if (!g.layout) return;
+    const unsigned on = (unsigned)(id - g.note_on0), off = (unsigned)(id - g.note_off0), ts = (unsigned)(id - g.time_shift0);
+    if (on < 128u) g.sounding[on >> 5] |= 1u << (on & 31);
+    else if (off < 128u) g.sounding[off >> 5] &= ~(1u << (off & 31));
+    else if (ts < (unsigned)g.time_shift_n) g.time_steps += (long long)ts + 1;
+    else if (id == g.sustain_on) g.pedal = 1;
+    else if (id == g.sustain_off) g.pedal = 0;
+}
+// The state as the kernels that draw hold it: every word loaded into a register of its own BEFORE the draw (field by field: no
+// copy of the struct, no array, nothing that would live in scratch memory).
+struct GramRegs {
+    int note_on0, note_off0, time_shift0, time_shift_n, sustain_on, sustain_off;
+    unsigned rules;
+    int layout, active, pedal;
+    unsigned s0, s1, s2, s3;
+    long long time_steps;
+};
+__device__ __forceinline__ GramRegs grammar_read(const DecGrammar* __restrict__ g) {
+    GramRegs r;
+    r.note_on0 = g->note_on0; r.note_off0 = g->note_off0; r.time_shift0 = g->time_shift0; r.time_shift_n = g->time_shift_n;
+    r.sustain_on = g->sustain_on; r.sustain_off = g->sustain_off;
+    r.rules = g->rules;
+    r.layout = g->layout; r.active = g->active; r.pedal = g->pedal;
+    r.s0 = g->sounding[0]; r.s1 = g->sounding[1]; r.s2 = g->sounding[2]; r.s3 = g->sounding[3];
+    r.time_steps = g->time_steps;
+    return r;
+}
+// ... and the transition for the drawn id on the device, by ONE lane after every thread has read the state: g0 is the state the
+// draw saw, gm the state in memory; only the word that changes is written (a note event updates its word of the sounding set in
+// memory: which word is known only now, and a run-time choice between registers is what the compiler turns into scratch)
+__device__ __forceinline__ void grammar_advance(DecGrammar* __restrict__ gm, const GramRegs& g0, int id) {
+    if (!g0.layout) return;
+    const unsigned on = (unsigned)(id - g0.note_on0), off = (unsigned)(id - g0.note_off0), ts = (unsigned)(id - g0.time_shift0);
+    if (on < 128u) {
+        gm->sounding[on >> 5] |= 1u << (on & 31);
+    } else if (off < 128u) {
+        gm->sounding[off >> 5] &= ~(1u << (off & 31));
+    } else if (ts < (unsigned)g0.time_shift_n) {
+        gm->time_steps = g0.time_steps + (long long)ts + 1;
+    } else if (id == g0.sustain_on) {
+        gm->pedal = 1;
+    } else if (id == g0.sustain_off) {
+        gm->pedal = 0;
+    }
+}
+
+// What the ban predicate reads: a few words, the same in every lane of the workgroup (readfirstlane keeps them in scalar
+// registers), snapshotted before the draw so that the lane that moves the state on afterwards races with no reader.
+struct BanCtx {
+    const unsigned* words;   // static bans, ceil(V / 32) words (all zero when unused)
+    int note_on0, note_off0, sustain_on, sustain_off;
+    unsigned rules;
+    int pedal;
+    unsigned s0, s1, s2, s3;
+};
+__device__ __forceinline__ int uni_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ BanCtx ban_load(const GramRegs& g, const unsigned* __restrict__ words) {
+    BanCtx b;
+    b.words = words;
+    b.note_on0 = uni_i(g.note_on0); b.note_off0 = uni_i(g.note_off0);
+    b.sustain_on = uni_i(g.sustain_on); b.sustain_off = uni_i(g.sustain_off);
+    b.rules = (unsigned)uni_i((int)g.rules);
+    b.pedal = uni_i(g.pedal);
+    b.s0 = (unsigned)uni_i((int)g.s0); b.s1 = (unsigned)uni_i((int)g.s1);
+    b.s2 = (unsigned)uni_i((int)g.s2); b.s3 = (unsigned)uni_i((int)g.s3);
+    return b;
+}
+// static bans only (cmp_k_sample_banned)
+__device__ __forceinline__ BanCtx ban_static(const unsigned* __restrict__ words) {
+    BanCtx b = {words, 0, 0, -1, -1, 0u, 0, 0u, 0u, 0u, 0u};
+    return b;
+}
+// bit p of the sounding set, in arithmetic alone (a select between the four words ends up as an indexed load from scratch)
+__device__ __forceinline__ bool ban_sounds(const BanCtx& b, unsigned p) {
+    const unsigned r = p & 31, i = p >> 5;
+    const unsigned m = ((b.s0 >> r) & (unsigned)(i == 0u)) | ((b.s1 >> r) & (unsigned)(i == 1u)) |
+                       ((b.s2 >> r) & (unsigned)(i == 2u)) | ((b.s3 >> r) & (unsigned)(i == 3u));
+    return m & 1u;
+}
+// column c (0 <= c < V) cannot be drawn in this state
+__device__ __forceinline__ bool banned(const BanCtx& b, int c) {
+    bool r = (b.words[c >> 5] >> (c & 31)) & 1u;
+    if (b.rules & CMP_GRAMMAR_NOTE_OFF_SOUNDING) {
+        const unsigned p = (unsigned)(c - b.note_off0);
+        if (p < 128u) r = r || !ban_sounds(b, p);
+    }
+    if (b.rules & CMP_GRAMMAR_NOTE_ON_SILENT) {
+        const unsigned p = (unsigned)(c - b.note_on0);
+        if (p < 128u) r = r || ban_sounds(b, p);
+    }
+    if (b.rules & CMP_GRAMMAR_PEDAL) r = r || (c == b.sustain_on && b.pedal) || (c == b.sustain_off && !b.pedal);
+    return r;
+}
+// every read of a logit by the samplers: BAN = false is the load itself
+template <bool BAN> __device__ __forceinline__ float z_at(const float* __restrict__ z, int c, const BanCtx& b) {
+    if (BAN) return banned(b, c) ? -INFINITY : z[c];
+    return z[c];
+}
+
 // The draw itself, shared by the per-token sampler and the kernel-level test entry (cmp_k_sample): every thread of a 256-thread
 // workgroup returns the chosen id.  temperature <= 0: argmax, lowest index on ties (tf.argmax).  Otherwise Gumbel-max:
 // argmax_c(z[c]/temperature + G_c), G_c = -log(-log(u_c)) with u_c a counter hash of (seed, draw counter, column) -- one
 // draw from softmax(z / temperature) (tf.random.categorical, cli.py:671-673).  bv/bi: 4-entry LDS scratch.
-__device__ __forceinline__ int sample_block(const float* __restrict__ z, int V, float temperature, unsigned seed, unsigned ctr,
-                                            float* bv, int* bi) {
+// BAN: every logit is read through the ban predicate (a banned column reads -inf: the draw of the contract, by construction).
+template <bool BAN>
+__device__ __forceinline__ int sample_block_t(const float* __restrict__ z, int V, float temperature, unsigned seed, unsigned ctr,
+                                              float* bv, int* bi, const BanCtx& ban) {
     const int tid = threadIdx.x;
     float best = -INFINITY;
     int arg = 0x7fffffff;
     const float inv_t = temperature > 0.f ? 1.0f / temperature : 0.f;
     for (int c = tid; c < V; c += 256) {
-        float v = z[c];
+        float v = z_at<BAN>(z, c, ban);
         if (temperature > 0.f) {
             unsigned hsh = drop_hash(seed, 0xC0FFEEu + ctr, (uint64_t)c);
             float u = ((float)(hsh >> 9) + 0.5f) * (1.0f / 8388608.0f);       // 23 bits + 0.5: exact, strictly inside (0,1)
@@ -80,6 +197,10 @@ __device__ __forceinline__ int sample_block(const float* __restrict__ z, int V, 
     }
     const int id = block_argmax(best, arg, bv, bi);
     return min(max(id, 0), V - 1);       // all-NaN logits leave the sentinel index: never address outside wte
+}
+__device__ __forceinline__ int sample_block(const float* __restrict__ z, int V, float temperature, unsigned seed, unsigned ctr,
+                                            float* bv, int* bi) {
+    return sample_block_t<false>(z, V, temperature, seed, ctr, bv, bi, BanCtx{});
 }
 
 // ---- truncated sampling: top-k and nucleus (top-p) -------------------------------------------------------------------------
@@ -121,8 +242,10 @@ __device__ __forceinline__ unsigned trunc_key(float z) {
 //      the chunk sums are added in chunk order by every thread (offset of its chunk, total), so cum[r] = offset + the chunk's
 //      serial partial sum is non-decreasing in r and the kept count is 1 + #{r : cum[r] < top_p * total};
 //   5. Gumbel-max over ranks 0 .. n - 1 with sample_block's arithmetic per column.
-__device__ __forceinline__ int sample_block_trunc(const float* __restrict__ z, int V, float temperature, int top_k, float top_p,
-                                                  unsigned seed, unsigned ctr, float* bv, int* bi, unsigned char* lds) {
+template <bool BAN>
+__device__ __forceinline__ int sample_block_trunc_t(const float* __restrict__ z, int V, float temperature, int top_k, float top_p,
+                                                    unsigned seed, unsigned ctr, float* bv, int* bi, unsigned char* lds,
+                                                    const BanCtx& ban) {
     __shared__ double ts[256];
     __shared__ int below;
     const int tid = threadIdx.x;
@@ -133,7 +256,7 @@ __device__ __forceinline__ int sample_block_trunc(const float* __restrict__ z, i
     int* hits = reinterpret_cast<int*>(q);                              // [Vp], steps 1-3: columns per count
     unsigned short* gcnt = reinterpret_cast<unsigned short*>(hits + Vp);// [Vp], steps 2-3: a column's count
     for (int c = tid; c < Vp; c += 256) {
-        ks[c] = c < V ? trunc_key(z[c]) : 0u;        // padding: key 0 at an index above every column is never counted
+        ks[c] = c < V ? trunc_key(z_at<BAN>(z, c, ban)) : 0u;        // padding: key 0 at an index above every column is never counted
         hits[c] = 0;
     }
     if (tid == 0) below = 0;
@@ -161,8 +284,8 @@ __device__ __forceinline__ int sample_block_trunc(const float* __restrict__ z, i
     const int kc = (top_k > 0 && top_k < V) ? top_k : V;
     int n = kc;
     if (top_p < 1.0f) {
-        const double zmax = (double)z[min((int)ord[0], V - 1)], dt = (double)temperature;
-        for (int r = tid; r < kc; r += 256) q[r] = exp(((double)z[min((int)ord[r], V - 1)] - zmax) / dt);
+        const double zmax = (double)z_at<BAN>(z, min((int)ord[0], V - 1), ban), dt = (double)temperature;
+        for (int r = tid; r < kc; r += 256) q[r] = exp(((double)z_at<BAN>(z, min((int)ord[r], V - 1), ban) - zmax) / dt);
         __syncthreads();
         const int per = max(4, (kc + 255) >> 8), nt = (kc + per - 1) / per;
         const int r0 = tid * per, r1 = min(kc, r0 + per);
@@ -195,7 +318,7 @@ __device__ __forceinline__ int sample_block_trunc(const float* __restrict__ z, i
     const float inv_t = 1.0f / temperature;
     for (int r = tid; r < n; r += 256) {
         const int c = min((int)ord[r], V - 1);       // (the ranks are a permutation; the clamp keeps any read inside the row)
-        float v = z[c];
+        float v = z_at<BAN>(z, c, ban);
         unsigned hsh = drop_hash(seed, 0xC0FFEEu + ctr, (uint64_t)c);
         float u = ((float)(hsh >> 9) + 0.5f) * (1.0f / 8388608.0f);
         v = v * inv_t - __logf(-__logf(u));
@@ -205,10 +328,56 @@ __device__ __forceinline__ int sample_block_trunc(const float* __restrict__ z, i
     return min(max(id, 0), V - 1);
 }
 
+__device__ __forceinline__ int sample_block_trunc(const float* __restrict__ z, int V, float temperature, int top_k, float top_p,
+                                                  unsigned seed, unsigned ctr, float* bv, int* bi, unsigned char* lds) {
+    return sample_block_trunc_t<false>(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, lds, BanCtx{});
+}
+
 // what every kernel that draws an id calls: the existing sampler unless a filter is on (uniform per workgroup)
 __device__ __forceinline__ int sample_block_any(const float* __restrict__ z, int V, float temperature, int top_k, float top_p,
                                                 unsigned seed, unsigned ctr, float* bv, int* bi, unsigned char* lds) {
     if (trunc_filters_on(V, temperature, top_k, top_p) && V <= TRUNC_MAX_V)
         return sample_block_trunc(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, lds);
     return sample_block(z, V, temperature, seed, ctr, bv, bi);
+}
+
+// ... with the event grammar: the banning samplers only when a rule or a static bit is active (`active`, uniform per workgroup),
+// so a chain without a grammar runs sample_block_any itself
+__device__ __forceinline__ int sample_block_banned(const float* __restrict__ z, int V, float temperature, int top_k, float top_p,
+                                                   unsigned seed, unsigned ctr, float* bv, int* bi, unsigned char* lds,
+                                                   const BanCtx& ban) {
+    if (trunc_filters_on(V, temperature, top_k, top_p) && V <= TRUNC_MAX_V)
+        return sample_block_trunc_t<true>(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, lds, ban);
+    return sample_block_t<true>(z, V, temperature, seed, ctr, bv, bi, ban);
+}
+__device__ __forceinline__ int sample_block_grammar(const float* __restrict__ z, int V, float temperature, int top_k, float top_p,
+                                                    unsigned seed, unsigned ctr, float* bv, int* bi, unsigned char* lds,
+                                                    const GramRegs& g, const unsigned* __restrict__ words) {
+    if (uni_i(g.active)) return sample_block_banned(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, lds, ban_load(g, words));
+    return sample_block_any(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, lds);
+}
+
+// ---- host side of the grammar: what cmp_decode_grammar keeps per chain, and what the begin functions make of it ---------------
+static inline int grammar_words(int V) { return (V + 31) / 32; }
+// the state of a row whose sequence so far is its prompt
+static inline DecGrammar grammar_begin(const DecGrammarCfg& c, const int32_t* prompt, int P) {
+    DecGrammar g = {};
+    g.note_on0 = g.note_off0 = g.time_shift0 = g.sustain_on = g.sustain_off = -1;
+    if (c.has_layout) {
+        g.note_on0 = c.g.note_on0; g.note_off0 = c.g.note_off0; g.time_shift0 = c.g.time_shift0; g.time_shift_n = c.g.time_shift_n;
+        g.sustain_on = c.g.sustain_on; g.sustain_off = c.g.sustain_off;
+        g.rules = (unsigned)c.g.rules;
+        g.layout = 1;
+    }
+    bool any = false;
+    for (uint32_t w : c.words) any = any || w != 0u;
+    g.active = (g.rules != 0u || any) ? 1 : 0;
+    for (int i = 0; i < P; i++) grammar_step(g, prompt[i]);
+    return g;
+}
+// the chain's static bans into its device buffer (all zero when there are none), stream-ordered in front of the first draw
+static inline hipError_t grammar_upload(const DecGrammarCfg& c, int V, unsigned* banw, hipStream_t s) {
+    const size_t bytes = (size_t)grammar_words(V) * 4;
+    if (c.words.empty()) return hipMemsetAsync(banw, 0, bytes, s);
+    return hipMemcpyAsync(banw, c.words.data(), bytes, hipMemcpyHostToDevice, s);
 }

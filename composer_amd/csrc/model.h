@@ -9,6 +9,13 @@
 struct DecodeState;
 struct DecodeBatchState;
 
+// what cmp_decode_grammar keeps for one decode chain until it is replaced (decode_common.h: the begin functions read it)
+struct DecGrammarCfg {
+    bool has_layout = false;
+    cmp_event_grammar g = {};
+    std::vector<uint32_t> words;       // static bans, ceil(V / 32) words; empty: none
+};
+
 struct GradClipStats { double norm; float scale; float factor; };     // elementwise.hip: grad_clip_finish_kernel
 
 struct Metrics {
@@ -205,6 +212,7 @@ struct cmp_model {
     int ln_fused_mode = -1;            // COMPOSER_LN_FUSED as read when the model was created (-1 unset, 0 off, 2 training passes too)
     DecodeState* dec = nullptr;
     DecodeBatchState* decb = nullptr;  // batched decode (decode_batch.hip): its own buffers, KV caches and captured chains
+    DecGrammarCfg gram[2];             // event grammar of the batch-1 chain [0] and of the batched chain [1] (cmp_decode_grammar)
     int gemm_role = -1;                // profiler class of the GEMMs being enqueued (0 while the forward pass is)
 
     // dropout seed of this replica: the model seed with the data-parallel rank folded in (rank 0: the seed itself)
@@ -265,3 +273,4 @@ void decode_state_free(DecodeState* d);
 // decode_batch.hip
 void decode_batch_state_free(DecodeBatchState* d);
 int decode_batch_slide_stats(DecodeBatchState* d, int64_t* row_slides, int64_t* forward_calls);
+int decode_batch_grammar_state(cmp_model* m, int row, uint32_t sounding[4], int32_t* pedal, int64_t* time_steps);

@@ -562,15 +562,53 @@ class Transformer:
         slide_context_length(self.window_size + 1, self.window_size, keep)       # the range check
         return keep
 
-    def generate(self, prompt_ids, length, temperature=1.0, mode='kv', seed=None, slide_keep=None, top_k=0, top_p=1.0):
+    def _set_decode_grammar(self, batched, grammar, banned_ids):
+        """cmp_decode_grammar for the chain the next begin call belongs to; with neither argument the chain is switched off again
+        only if an earlier call of this object switched it on (a library without the entry point is then never asked for it)."""
+        from composer_amd import grammar as gm
+        on = getattr(self, '_grammar_on', None)
+        if on is None:
+            on = self._grammar_on = [False, False]
+        if grammar is None and banned_ids is None:
+            if on[batched]:
+                _lib.check(self._lib.cmp_decode_grammar(self._h, batched, None, None), 'cmp_decode_grammar')
+                on[batched] = False
+            return
+        if grammar is not None and grammar.vocab_size != self.vocab_size:
+            raise ValueError('grammar: a layout for %d ids, the model has %d' % (grammar.vocab_size, self.vocab_size))
+        words = None
+        if banned_ids is not None:
+            words = gm.check_static_bans(self.vocab_size, gm.ban_words(self.vocab_size, banned_ids), grammar)
+        cg = grammar.to_c() if grammar is not None else None
+        _lib.check(self._lib.cmp_decode_grammar(self._h, batched, C.byref(cg) if cg is not None else None,
+                                                words.ctypes.data_as(C.c_void_p) if words is not None else None),
+                   'cmp_decode_grammar')
+        on[batched] = True
+
+    def decode_grammar_state(self, batched=False, row=0):
+        """`composer_amd.grammar.GrammarState` of a row after its latest id (cmp_decode_grammar_state): the sounding pitches, the
+        pedal and the summed time shifts of prompt ++ ids so far.  Empty while the chain has no layout."""
+        from composer_amd import grammar as gm
+        w, ped, ts = (C.c_uint32 * 4)(), C.c_int32(0), C.c_int64(0)
+        _lib.check(self._lib.cmp_decode_grammar_state(self._h, 1 if batched else 0, int(row), C.byref(w), C.byref(ped), C.byref(ts)),
+                   'cmp_decode_grammar_state')
+        bits = np.unpackbits(np.array(list(w), '<u4').view(np.uint8), bitorder='little').astype(bool)
+        return gm.GrammarState(bits, bool(ped.value), ts.value)
+
+    def generate(self, prompt_ids, length, temperature=1.0, mode='kv', seed=None, slide_keep=None, top_k=0, top_p=1.0,
+                 grammar=None, banned_ids=None):
         """Returns `length` generated ids.  mode 'literal' restates cli.py:663-676 as written (no `past`),
         mode 'kv' is model(x, past=presents).  temperature <= 0 -> greedy argmax.  mode 'kv-slide' is 'kv' that goes on past
         window_size: when the cache is full the last `slide_keep` tokens (default window_size // 2) are re-encoded from position 0
         and decoding continues on them (`slide_context_length` is the context every id is drawn from).
         top_k / top_p: truncated sampling on the device (0 / 1.0: off) -- every id is drawn from the columns
-        `sampling_keep_set(logits, temperature, top_k, top_p)` names, renormalised."""
+        `sampling_keep_set(logits, temperature, top_k, top_p)` names, renormalised.
+        grammar (a `composer_amd.grammar.EventGrammar`) / banned_ids (ids, a bool mask or ban words): event-grammar decoding -- ids
+        the grammar bans in the state of prompt ++ ids so far, and the banned ids, are never drawn (they read -inf, before top_k /
+        top_p rank the row and for the greedy argmax too).  Default: off, the sampler as it was."""
         p = np.ascontiguousarray(np.asarray(prompt_ids, dtype=np.int32).reshape(-1))
         top_k, top_p = check_sampling(top_k, top_p)
+        self._set_decode_grammar(0, grammar, banned_ids)
         filters = top_k != 0 or top_p != 1.0
         if mode == 'kv-slide':
             keep = self._slide_keep(slide_keep)
@@ -601,12 +639,15 @@ class Transformer:
         _lib.check(self._lib.cmp_decode_steps(self._h, int(length), out.ctypes.data_as(C.c_void_p)), 'cmp_decode_steps')
         return out
 
-    def generate_batch(self, prompts, length, temperature=1.0, mode='kv', seed=None, slide_keep=None, top_k=0, top_p=1.0):
+    def generate_batch(self, prompts, length, temperature=1.0, mode='kv', seed=None, slide_keep=None, top_k=0, top_p=1.0,
+                       grammar=None, banned_ids=None):
         """B independent sequences decoded together: returns int32 [B, length].  `prompts` is a list of id sequences (ragged
         rows allowed); row b samples with seed + b, so it equals `generate(prompts[b], length, seed=seed + b)` in its first id
         and depends on nothing but its own prompt and seed.  Modes, temperature and slide_keep as in `generate`; in 'kv-slide'
         every row slides on its own length.  temperature, top_k and top_p are each a scalar (every row) or a sequence of B values
-        (row b's own): a row's ids depend on its own three only."""
+        (row b's own): a row's ids depend on its own three only.  grammar / banned_ids as in `generate`: one grammar and one ban
+        vector for all rows, the state each row's own."""
+        self._set_decode_grammar(1, grammar, banned_ids)
         rows = [np.asarray(p, dtype=np.int64).reshape(-1) for p in prompts]
         slide = mode == 'kv-slide'
         if slide:

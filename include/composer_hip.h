@@ -293,6 +293,64 @@ int cmp_k_sample_ex(void* stream, const float* logits, int V, float temperature,
 int cmp_decode_begin_ex(cmp_model* m, const int32_t* prompt, int P, int mode, int keep, float temperature, int top_k, float top_p,
                         uint64_t seed);
 
+/* ---- event-grammar decoding: on-device note / pedal state masks the sampler -------------------------------------------------
+ * The vocabulary is a grammar: NoteSequence.from_events (the reference's EventSequence.to_note_sequence) silently drops a NOTE_OFF
+ * of a silent pitch, a NOTE_ON of a sounding one, a SUSTAIN_ON while the pedal is down and a SUSTAIN_OFF while it is up.  With a
+ * grammar configured, both decode chains draw only events that mean something in the row's current state.  The contract
+ * (composer_amd.grammar.EventGrammar restates it on the host):
+ *   Layout: given by the caller, never hard-coded.  note_on0 / note_off0: the first of 128 consecutive ids each, id - base = the
+ *     pitch; time_shift0 / time_shift_n: the TIME_SHIFT ids; sustain_on / sustain_off: single ids, or -1 for BOTH when the
+ *     vocabulary has none.  (composer_amd.dataset.event_ranges; the default dataset config: 0 / 128 / 288, 100 / 388 / 389, V = 390.)
+ *   State: of a sequence s = prompt ++ ids so far, a 128-bit sounding set and a pedal bit: the left fold over s of from_events'
+ *     transition -- NOTE_ON p sets bit p if clear, else is ignored; NOTE_OFF p clears bit p if set, else is ignored; SUSTAIN_ON /
+ *     SUSTAIN_OFF set / clear the pedal likewise; every other id leaves the state alone.  The prompt is folded the same way (its
+ *     ignored events are allowed and change nothing).  The state is a function of the whole sequence: a kv-slide re-encode does
+ *     not reset it, and the literal mode carries it too.
+ *   Rules: a bit mask selects what is banned in the current state -- CMP_GRAMMAR_NOTE_OFF_SOUNDING: NOTE_OFF p while p is silent;
+ *     CMP_GRAMMAR_NOTE_ON_SILENT: NOTE_ON p while p sounds; CMP_GRAMMAR_PEDAL: SUSTAIN_ON while the pedal is down, SUSTAIN_OFF while
+ *     it is up.
+ *   Static bans: an optional bit vector of ceil(V / 32) words (bit c % 32 of word c / 32 set: column c is never drawn), shared by
+ *     all rows of the chain and ORed with the dynamic bans.
+ *   The draw: with the ban set N of that step, the id equals, bit for bit, cmp_k_sample_ex on a copy of the logits row with the
+ *     columns of N at -inf (same temperature, top_k, top_p, seed and draw counter).  So the bans apply before the ranking: top_k
+ *     counts allowed columns first, a banned column carries mass 0 in top_p, and the greedy draw (temperature <= 0) is the argmax
+ *     over the allowed columns, lowest index on ties -- unlike the filters, the grammar is NOT a no-op for greedy.
+ *   Always a drawable column: no dynamic rule ever bans a TIME_SHIFT; with a layout, a static vector must leave at least one
+ *     TIME_SHIFT id clear; without one, at least one id.
+ *   Off: rules 0 and no static bit set is today's sampler itself (the kernels that draw branch, uniformly, to the banning
+ *     samplers only when a rule or a static bit is active): every id of every entry point is what it was, bit for bit.
+ *   Refusals (CMP_ERR_INVALID before any device work, the reason in cmp_last_error): a range outside [0, V); overlapping ranges;
+ *     one sustain id without the other; time_shift_n < 1; unknown rule bits; a static vector that bans every id it must not.
+ *   No vocabulary limit of its own: the predicate is evaluated per column from a few uniform words at any V (the 4096-column limit
+ *     of the truncating sampler keeps applying only when a filter is on). */
+#define CMP_GRAMMAR_NOTE_OFF_SOUNDING 1
+#define CMP_GRAMMAR_NOTE_ON_SILENT 2
+#define CMP_GRAMMAR_PEDAL 4
+#define CMP_GRAMMAR_ALL 7
+typedef struct cmp_event_grammar {
+    int32_t note_on0;
+    int32_t note_off0;
+    int32_t time_shift0;
+    int32_t time_shift_n;
+    int32_t sustain_on;
+    int32_t sustain_off;
+    int32_t rules;             /* CMP_GRAMMAR_* bits */
+} cmp_event_grammar;
+/* Configures the batch-1 chain (batched = 0) or the batched chain (batched != 0).  Validated against the model's V here; takes
+ * effect at that chain's next begin call (any of them: the begin argument lists do not grow) and stays until replaced.  g: the
+ * layout and the rules, or null (no layout: no dynamic rule, the state stays empty); banned_words: HOST array of ceil(V / 32)
+ * words (bits at or above V are ignored), or null.  Both null: off.  The configuration lives in the device-side decode state and
+ * in a device buffer of fixed address: changing it re-captures nothing. */
+int cmp_decode_grammar(cmp_model* m, int batched, const cmp_event_grammar* g, const uint32_t* banned_words);
+/* The state of row `row` of the chain (batch-1: row 0) after its latest id; synchronises.  sounding: bit p % 32 of word p / 32 =
+ * pitch p sounds; time_steps: the sum over all TIME_SHIFT events of s, id time_shift0 + j counting j + 1 (what a duration-based
+ * stop would read).  All zero while the chain has no layout.  CMP_ERR_STATE before begin, CMP_ERR_INVALID for a bad row. */
+int cmp_decode_grammar_state(cmp_model* m, int batched, int row, uint32_t sounding[4], int32_t* pedal, int64_t* time_steps);
+/* The sampler alone with a DEVICE bit vector of ceil(V / 32) words (the kernel-level test of the draw): cmp_k_sample_ex reading
+ * every banned column as -inf. */
+int cmp_k_sample_banned(void* stream, const float* logits, int V, float temperature, int top_k, float top_p,
+                        const uint32_t* banned_dev, uint64_t seed, uint32_t counter0, int n, int32_t* ids_out);
+
 /* ---- batched decode: B independent sequences per step (1 <= B <= 256), state apart from cmp_decode_begin's ----------------
  * prompts: host int32 [B][ld], row b holds lens[b] ids (1 <= lens[b] <= window_size).  Row b samples with seed (uint32)(seed + b);
  * its i-th generated id uses draw counter i, as cmp_decode_begin does, so its first id equals cmp_decode_begin's on that prompt
