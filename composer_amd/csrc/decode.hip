@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256) void dec_gemv_kernel(const float* __restrict__
 
 
 // =================================================================================================
-// The per-token kernels (second generation; the first one is kept in experiments builds for A/B timing).  Same arithmetic; every kernel's dependent chain is as short as the
+// The per-token kernels (second generation; the first one is in history, see below).  Same arithmetic; every kernel's dependent chain is as short as the
 // data flow allows, because a batch-1 token is 5L+2 dependent launches of ~1.8 us boundary each (tools/ubench/graph_chain.hip)
 // and what is left to win is inside the kernels:
 //   * GEMV: a workgroup is 1-4 INDEPENDENT waves, one output column per wave: no LDS, no barrier.  Each lane loads the
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void dec_gemv_kernel(const float* __restrict__
 //   * attention: the K cache is stored [H][D/4][W][4] so that TWO lanes own a key (one DPP add per score instead of a
 //     16-lane shuffle tree); each wave runs its own online softmax over its keys and the four waves meet at ONE barrier;
 //     the current token's k/v come from the c_attn output instead of a write -> barrier -> read through the cache.
-// (The first-generation kernels live in experiments/decode_lab.hip.)
+// (The first-generation kernels are in history: git show a635116:composer_amd/csrc/experiments/decode_lab.hip)
 // =================================================================================================
 
 // y[n] = act( IN(x) . Wt[n,:] + bias[n] ) + resid[n]; a wave owns CW adjacent output columns, blockDim.x / 64 waves per workgroup.
@@ -696,7 +696,8 @@ static int launch_attn2(hipStream_t s, cmp_model* m, DecodeState* d, const DecLa
     return CMP_OK;
 }
 
-static int enqueue_token_step2(cmp_model* m, DecodeState* d) {
+// one token: consumes d->x (embedding of st->token at st->pos), produces the next id and the next d->x
+static int enqueue_token_step(cmp_model* m, DecodeState* d) {
     hipStream_t s = m->ctx->stream;
     const int E = m->E, Ea = m->Ea, L = m->L;
     const bool ln = m->cfg.use_layer_norm != 0;
@@ -720,9 +721,6 @@ static int enqueue_token_step2(cmp_model* m, DecodeState* d) {
     KERNEL_CHECK();
     return CMP_OK;
 }
-
-// one token: consumes d->x (embedding of st->token at st->pos), produces the next id and the next d->x
-static int enqueue_token_step(cmp_model* m, DecodeState* d) { return enqueue_token_step2(m, d); }
 
 // keep > 0: sliding-window mode (cmp_decode_begin_slide), kv mode otherwise unchanged
 static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mode, float temperature, int top_k, float top_p,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One-off fuzzing of the attention kernels (forward, dQ, dK/dV, fused bias sums) through the kernel-level parity check of
-tests/test_gpu_kernels.py on random shapes:  python tests/extra/fuzz_attention.py [N] [seed]   (COMPOSER_ATTN64 selects the opt-in forwards)"""
+tests/test_gpu_kernels.py on random shapes:  python tests/extra/fuzz_attention.py [N] [seed]"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

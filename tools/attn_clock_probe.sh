@@ -1,5 +1,7 @@
+# effective shader clock and SQ counters of the forward attention kernel: tools/attn_clock_probe.sh [<lib> ...]
+# (lib = file under composer_amd/lib without .so; the product library when none is given)
 export TMPDIR=/tmp
-for l in libcomposer_hip ad5 ad3 ad2; do
+for l in "${@:-libcomposer_hip}"; do
   out=gpurun_out/clk/$l; mkdir -p $out
   KB_B=128 COMPOSER_HIP_LIB=composer_amd/lib/$l.so timeout 200 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $out -o k -- python3 tools/kbench.py attn > $out.log 2>&1
   python3 - <<PY

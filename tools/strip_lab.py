@@ -2,8 +2,9 @@
 """Resolves the measurement-only preprocessor branches of a HIP source the way a product build sees them and writes the result
 back: `#if` / `#ifdef` / `#ifndef` / `#elif` whose condition only involves the names below are evaluated (names in UNDEF are
 not defined, names in DEFINED have the given value), the dead branches and the directives themselves are dropped, everything
-else is kept byte for byte.  Used once in round 6 to move the lab out of the shipped translation units: the unstripped files
-live on as composer_amd/csrc/experiments/*_lab.hip (compiled only by tools/ab_build.py with -DCOMPOSER_EXPERIMENTS).
+else is kept byte for byte.  Used once in round 6 to move the lab out of the shipped translation units; the unstripped files
+are in history, consistent only with the rest of that commit's tree: git show a635116:composer_amd/csrc/experiments/<name>_lab.hip
+tests/test_build_guards.py runs it over the shipped sources: stripping them again must change nothing.
     python tools/strip_lab.py composer_amd/csrc/attention.hip [...]
 """
 import re
