@@ -82,6 +82,8 @@ SIGNATURES = {
     "cmp_train_metrics_wait_ex": (_i, [_P, _i64, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f)]),
     "cmp_loss_and_grads": (_i, [_P, _P, _P, _i, _i, C.POINTER(_f), C.POINTER(_f)]),
     "cmp_eval_step": (_i, [_P, _P, _P, _i, _i, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(_i64)]),
+    "cmp_score": (_i, [_P, _P, _P, _i, _i, _P, _P, _P]),
+    "cmp_k_score_rows": (_i, [_P, _P, _i, _P, _P, _P, _P, _i, _i]),
     "cmp_present_get": (_i, [_P, _i, _i, _i, _P]),
     "cmp_forward_generation": (_i, [_P, C.POINTER(_i64)]),
     "cmp_present_get_at": (_i, [_P, _i, _i, _i, _i64, _P]),
@@ -149,7 +151,7 @@ SIGNATURES = {
 # timing (tools/ab_step.py) may lack them; the package's own library must export every symbol
 _ADDED_LATER = {"cmp_gemm_ln_scale_next", "cmp_attn_bwd_ln_next", "cmp_k_layernorm_bwd_prescaled", "cmp_k_wgrad_ln_fix", "cmp_k_ln_stats_merge", "cmp_dp_rccl_version", "cmp_dp_allreduce_pattern", "cmp_dp_init_exchange", "cmp_train_step_graph_probe", "cmp_train_step_launches", "cmp_k_embed_fwd_stats", "cmp_k_ln_fold_prep", "cmp_gemm_ln_next", "cmp_k_layernorm_bwd_parts", "cmp_model_path_info", "cmp_forward_ex", "cmp_hidden_get_at", "cmp_dp_stats", "cmp_prof_end2", "cmp_prof_pause", "cmp_prof_resume", "cmp_k_wgrad_group", "cmp_k_embed_bwd_v", "cmp_decode_batch_begin", "cmp_decode_batch_steps", "cmp_k_sample_rows", "cmp_decode_logits_get", "cmp_decode_batch_logits_get", "cmp_k_sample_ex", "cmp_k_sample_rows_ex", "cmp_decode_begin_ex", "cmp_decode_batch_begin_ex", "cmp_train_options",
                 "cmp_train_options_get", "cmp_train_grad_stats", "cmp_train_metrics_wait_ex", "cmp_k_adam_dev", "cmp_k_grad_clip_ws", "cmp_k_grad_clip",
-                "cmp_decode_grammar", "cmp_decode_grammar_state", "cmp_k_sample_banned"}
+                "cmp_decode_grammar", "cmp_decode_grammar_state", "cmp_k_sample_banned", "cmp_score", "cmp_k_score_rows"}
 
 _lib = None
 

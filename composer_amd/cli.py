@@ -1,4 +1,4 @@
-"""`composer train | evaluate | generate | make-config | summary` for the Transformer hot path.
+"""`composer train | evaluate | generate | score | make-config | summary` for the Transformer hot path.
 
 Mirrors the commands, arguments and defaults of the reference's composer/cli.py (train :516-589, evaluate :591-615,
 generate :617-680, make-config :69-78, summary :424-440) with the TensorFlow model replaced by the HIP one.  Out of
@@ -7,8 +7,10 @@ scope: the MusicRNN model type, MIDI preprocessing/synthesis.
 Documented divergences: `--temperature 0` means greedy argmax (the reference divides by the temperature, cli.py:671);
 besides the reference's MIDI prompt (`--prompt`, read by composer_amd.midi instead of pretty_midi) a prompt can be given
 as event ids (`--prompt-ids` / `--prompt-data`), and an output path ending in `.data` gets event ids instead of a MIDI
-file; `--decode-mode` selects the literal loop of cli.py:663-676 or a real KV cache."""
+file; `--decode-mode` selects the literal loop of cli.py:663-676 or a real KV cache.  `score` (not in the reference) prints the
+per-event likelihood of MIDI / `.data` files under a restored model; `generate --keep-best` ranks the samples by it."""
 import datetime
+import json
 import logging
 import os
 import shutil
@@ -327,8 +329,12 @@ def evaluate(model_type, dataset_path, restoredir, use_generator, max_files):
 @click.option('--num-samples', default=1, type=click.IntRange(1, 256),
               help='Number of sequences to generate from the prompt, decoded together; sample i uses seed + i and goes to '
                    'OUTPUT-i.mid (or OUTPUT-i.data). Defaults to 1.')
+@click.option('--keep-best', default=None, type=int,
+              help='Score the --num-samples N sequences under the model (mean log-probability of the generated events, '
+                   'temperature 1, no filter) and write only the K best as OUTPUT-0 ... OUTPUT-{K-1}, best first; 1 <= K <= N. '
+                   'Defaults to off: every sample is written.')
 def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt_data, prompt_length, generate_length,
-             temperature, decode_mode, slide_keep, top_k, top_p, constrain, pitch_range, num_samples):
+             temperature, decode_mode, slide_keep, top_k, top_p, constrain, pitch_range, num_samples, keep_best):
     """Generate a MIDI file (cli.py:617-680): MIDI prompt -> event ids -> model -> event ids -> MIDI.  An output path
     ending in `.data` gets the event ids in the dataset's binary format instead of a MIDI file.  With --num-samples N > 1
     the N sequences are decoded as one batch and written to OUTPUT-0 ... OUTPUT-{N-1} (same suffix); --top-k / --top-p apply
@@ -346,7 +352,20 @@ def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt
         raise click.UsageError('--top-k {}: must be >= 0 (0 = off).'.format(top_k))
     if not 0.0 < top_p <= 1.0:
         raise click.UsageError('--top-p {}: must be in (0, 1] (1 = off).'.format(top_p))
+    if keep_best is not None and not 1 <= keep_best <= num_samples:
+        raise click.UsageError('--keep-best {}: must be in [1, --num-samples = {}].'.format(keep_best, num_samples))
     config = get_config_from_restoredir(restoredir)
+    x_early = None
+    if keep_best is not None:                                    # refused from the arguments and the prompt, before any device use
+        x_early = _prompt_ids(prompt, prompt_ids, prompt_data, prompt_length, config.dataset)
+        if len(x_early) == 0:                                    # (the scored positions are those behind the prompt: it needs one id)
+            raise click.UsageError('--keep-best: the prompt is empty.')
+        w = config.transformer.model.window_size
+        if len(x_early) + generate_length > w and (decode_mode == 'reference-literal' or
+                                                   (decode_mode is None and len(x_early) + generate_length - 1 > w)):
+            # that loop draws every id from the whole prefix fed at once, which is not the scoring contract's context
+            raise click.UsageError('--keep-best: --decode-mode reference-literal with prompt ({}) + length ({}) > window_size ({}) '
+                                   'cannot be scored; use --decode-mode kv-slide.'.format(len(x_early), generate_length, w))
     if slide_keep is not None:                                   # refused from the restored config, before any device use
         if decode_mode != 'kv-slide':
             raise click.UsageError('--slide-keep goes with --decode-mode kv-slide.')
@@ -358,15 +377,7 @@ def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt
     model.compile(config.transformer.train.learning_rate)
     model.build(input_shape=(1, None))
     d = config.dataset
-    if prompt is not None:                                       # cli.py:645-660
-        x = nt.prompt_ids_from_midi(prompt, prompt_length, d.time_step_increment, d.max_time_steps, d.velocity_bins)
-    elif prompt_ids is not None:
-        x = [int(t) for t in prompt_ids.split(',') if t.strip() != '']
-    elif prompt_data is not None:
-        x = ds.read_data_file(prompt_data)[0].astype(np.int32).tolist()
-    else:
-        raise NotImplementedError()                              # cli.py:642-643
-    x = x[:prompt_length]                                        # cli.py:649
+    x = x_early if x_early is not None else _prompt_ids(prompt, prompt_ids, prompt_data, prompt_length, d)
     model.reset_states()
     window = config.transformer.model.window_size
     fits = len(x) + generate_length - 1 <= window
@@ -400,15 +411,106 @@ def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt
         if pitch_range is not None:
             slide.update(banned_ids=g.pitch_range_bans(lo, hi))
         click.echo('grammar: constrain {} pitch-range {}'.format('on' if constrain else 'off', pitch_range or 'off'), err=True)
-    if num_samples == 1:
+    if num_samples == 1 and keep_best is None:
         ids = model.generate(x, generate_length, temperature=temperature, mode=decode_mode, **slide)
         _write_generated(list(x) + ids.tolist(), out, d)         # prompt + generated (cli.py:676)
         click.echo(','.join(str(int(i)) for i in ids))
         return
     batch = model.generate_batch([x] * num_samples, generate_length, temperature=temperature, mode=decode_mode, **slide)
+    if keep_best is not None:
+        # prompt ++ ids of every sample under the scoring contract (the run's --slide-keep when it slid); only the generated
+        # positions count.  Sample i was drawn with seed + i.
+        scores = model.score([list(x) + ids.tolist() for ids in batch], slide_keep=slide_keep if decode_mode == 'kv-slide' else None)
+        means = [float(np.mean(s.logp[len(x) - 1:].astype(np.float64))) for s in scores]
+        for i, v in enumerate(means):
+            click.echo('keep-best: sample {} seed {} mean log-probability {:.6f}'.format(i, model.seed + i, v), err=True)
+        order = sorted(range(num_samples), key=lambda i: (-means[i], i))[:keep_best]
+        click.echo('keep-best: kept {}'.format(','.join(str(i) for i in order)), err=True)
+        batch = [batch[i] for i in order]
     for i, ids in enumerate(batch):
         _write_generated(list(x) + ids.tolist(), out.with_name('{}-{}{}'.format(out.stem, i, out.suffix)), d)
         click.echo(','.join(str(int(t)) for t in ids))
+
+
+def _prompt_ids(prompt, prompt_ids, prompt_data, prompt_length, d):
+    """The prompt of `generate` as event ids (host only)."""
+    from composer_amd import notes as nt
+    if prompt is not None:                                       # cli.py:645-660
+        x = nt.prompt_ids_from_midi(prompt, prompt_length, d.time_step_increment, d.max_time_steps, d.velocity_bins)
+    elif prompt_ids is not None:
+        x = [int(t) for t in prompt_ids.split(',') if t.strip() != '']
+    elif prompt_data is not None:
+        x = ds.read_data_file(prompt_data)[0].astype(np.int32).tolist()
+    else:
+        raise NotImplementedError()                              # cli.py:642-643
+    return x[:prompt_length]                                     # cli.py:649
+
+
+EVENT_TYPE_NAMES = {ds.NOTE_ON: 'NOTE_ON', ds.NOTE_OFF: 'NOTE_OFF', ds.VELOCITY: 'VELOCITY', ds.TIME_SHIFT: 'TIME_SHIFT',
+                    ds.SUSTAIN_ON: 'SUSTAIN_ON', ds.SUSTAIN_OFF: 'SUSTAIN_OFF'}
+
+
+def read_score_file(path, d):
+    """Event ids of one file to score: `.mid` / `.midi` through the codec path of `generate --prompt` (the whole file), `.data`
+    through read_data_file with its settings checked against the config, as load_dataset does."""
+    p = Path(path)
+    if p.suffix.lower() in ('.mid', '.midi'):
+        from composer_amd import notes as nt
+        try:
+            return nt.prompt_ids_from_midi(p, None, d.time_step_increment, d.max_time_steps, d.velocity_bins)
+        except IndexError:                                       # (trim_start of a file without a note)
+            raise click.ClickException('{} holds no notes.'.format(p))
+    if p.suffix == '.data':
+        ids, settings = ds.read_data_file(p)
+        want = (d.time_step_increment, d.max_time_steps, d.velocity_bins)
+        if tuple(settings) != want:
+            raise click.ClickException('{} was preprocessed with {} but the config says {}'.format(p, tuple(settings), want))
+        return ids.astype(np.int32).tolist()
+    raise click.UsageError('{}: a .mid / .midi or a .data file is expected.'.format(p))
+
+
+@cli.command()
+@click.argument('model-type', type=EnumType(ModelType, False))
+@click.argument('restoredir')
+@click.argument('files', nargs=-1, required=True)
+@click.option('--slide-keep', default=None, type=int,
+              help='Events re-encoded from position 0 when a file is longer than window_size (the context rule of generate '
+                   '--decode-mode kv-slide), 1 .. window_size - 1. Defaults to window_size // 2.')
+@click.option('--by-event-type', is_flag=True, default=False, help='Also print the count and mean NLL of every event class.')
+@click.option('--json', 'json_out', default=None, help='Write the figures and the per-event arrays to this JSON file.')
+def score(model_type, restoredir, files, slide_keep, by_event_type, json_out):
+    """How likely are these pieces under the model?  One line per file: events scored, NLL per event (nats), bits per event,
+    perplexity and top-1 accuracy -- every event after the first, each against the context kv-slide generation would draw it
+    from (temperature 1, no filter, no grammar)."""
+    _require_transformer(model_type)
+    config = get_config_from_restoredir(restoredir)
+    window = config.transformer.model.window_size
+    if slide_keep is not None and not 1 <= slide_keep <= window - 1:     # refused from the restored config, before any device use
+        raise click.UsageError('--slide-keep {}: must be in [1, window_size - 1 = {}].'.format(slide_keep, window - 1))
+    d = config.dataset
+    seqs = [read_score_file(f, d) for f in files]
+    for f, s in zip(files, seqs):
+        if len(s) == 0:
+            raise click.ClickException('{} holds no events.'.format(f))
+    model, _ = create_model(model_type, config, dtype='fp32')
+    model.load_from_checkpoint(restoredir)
+    results = model.score(seqs, slide_keep=slide_keep)
+    rg = ds.event_ranges(ds.event_value_ranges(d.time_step_increment, d.max_time_steps, d.velocity_bins))
+    report = []
+    for f, r in zip(files, results):
+        click.echo('{}: events {} nll {:.9g} bits {:.9g} perplexity {:.9g} top1 {:.9g}'.format(
+            f, r.events, r.nll_per_event, r.bits_per_event, r.perplexity, r.top1_accuracy))
+        entry = dict(file=str(f), **r.to_dict())
+        if by_event_type:
+            entry['by_event_type'] = {}
+            for t, (count, nll) in r.by_event_type(rg).items():
+                click.echo('  {}: count {} nll {:.9g}'.format(EVENT_TYPE_NAMES[t], count, nll))
+                entry['by_event_type'][EVENT_TYPE_NAMES[t]] = {'count': count, 'nll_per_event': nll}
+        report.append(entry)
+    if json_out is not None:
+        keep = window // 2 if slide_keep is None else slide_keep
+        with open(json_out, 'w') as fh:
+            json.dump({'window_size': window, 'slide_keep': keep, 'files': report}, fh)
 
 
 def _write_generated(all_ids, out, d):

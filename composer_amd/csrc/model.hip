@@ -1702,6 +1702,30 @@ static int io_scratch(cmp_model* m, int slot, size_t bytes, void** out) {
     *out = m->io_buf[slot];
     return CMP_OK;
 }
+// ---- scoring (include/composer_hip.h, "scoring"): inference forward pass + cmp_k_score_rows on its logits.  Nothing that lasts is
+// written: the per-row results go to row_loss / row_correct (scratch of the loss, rewritten by every step) and to the inspection
+// staging; m->metrics, the metrics bookkeeping of the train steps, G, the Adam state and the accumulation group are not touched.
+extern "C" int cmp_score(cmp_model* m, const int32_t* x, const int32_t* y, int B, int T, float* logp, int32_t* rank, float* entropy) {
+    CMP_REQUIRE(m && x && y, "score: null argument");
+    HIP_CHECK(hipSetDevice(m->ctx->device));
+    CHECK_RC(ensure_workspace(m, B, T));
+    const int M = B * T;
+    CHECK_RC(check_host_ids(m, x, M, "score: input ids"));          // (targets outside [0, V) are the "not scored" mark)
+    void* ent_dev = nullptr;
+    if (entropy) CHECK_RC(io_scratch(m, 0, (size_t)M * 4, &ent_dev));
+    hipStream_t s = m->ctx->stream;
+    HIP_CHECK(hipMemcpyAsync(m->x_dev, x, (size_t)M * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(m->y_dev, y, (size_t)M * 4, hipMemcpyHostToDevice, s));
+    CHECK_RC(model_forward(m, m->x_dev, B, T, false, 0));
+    CHECK_RC(cmp_k_score_rows(s, m->logits, m->ldz, m->y_dev, logp ? m->row_loss : nullptr, rank ? m->row_correct : nullptr,
+                              (float*)ent_dev, M, m->V));
+    if (logp) HIP_CHECK(hipMemcpyAsync(logp, m->row_loss, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+    if (rank) HIP_CHECK(hipMemcpyAsync(rank, m->row_correct, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+    if (entropy) HIP_CHECK(hipMemcpyAsync(entropy, ent_dev, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return CMP_OK;
+}
+
 extern "C" int cmp_forward_generation(cmp_model* m, int64_t* gen) {
     CMP_REQUIRE(m && gen, "forward_generation: null argument");
     *gen = m->fwd_gen;

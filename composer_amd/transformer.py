@@ -5,6 +5,7 @@ Same constructor arguments (transformer.py:610-614), same call / train / evaluat
 surface (cli.py:579-589, 606-615, 635-676).  All arithmetic happens in hand-written HIP kernels on an
 MI355X; this file only moves integers in and numbers out.  There is no CPU path.
 """
+import collections
 import ctypes as C
 import enum
 import logging
@@ -31,6 +32,126 @@ def slide_context_length(n, window, keep):
     if n <= window:
         return n
     return keep + (n - window - 1) % (window - keep + 1)
+
+
+def score_windows(n, window, keep):
+    """The forward passes that score a sequence of n ids under the scoring contract (include/composer_hip.h, "scoring"): a list
+    of (start, length, first_scored_row).  A window feeds s[start : start + length] at positions 0 .. length - 1; its row r holds
+    the logits of position start + r + 1, drawn from the context s[start : start + r + 1], and the rows first_scored_row ..
+    length - 1 are the ones that count.  Every position 1 .. n - 1 is scored by exactly one (window, row), and the context that
+    row gives it has length slide_context_length(position, window, keep): for positions up to `window` the plain causal pass,
+    past it the conditioning of 'kv-slide' generation.  Window 0 is s[0 : min(n - 1, W)] and scores every row; window j >= 1
+    starts at W + 1 + (j - 1)(W - keep + 1) - keep, holds up to W inputs and scores rows keep - 1 ...  n = 1: no window."""
+    n, W, keep = int(n), int(window), int(keep)
+    if not 1 <= keep <= W - 1:
+        raise ValueError('slide keep = %d outside [1, window_size - 1 = %d]' % (keep, W - 1))
+    if n < 1:
+        raise ValueError('n = %d: the sequence holds at least one token' % n)
+    out = []
+    if n >= 2:
+        out.append((0, min(n - 1, W), 0))
+    period = W - keep + 1
+    first = W + 1                                   # the first position window j scores
+    while first <= n - 1:
+        start = first - keep
+        out.append((start, min(W, n - 1 - start), keep - 1))
+        first += period
+    return out
+
+
+class SequenceScore:
+    """What `Transformer.score` returns for one sequence s of N ids: `logp` (nats), `rank` (0 = the model's first choice) and
+    `entropy` (nats) of the positions 1 .. N-1, aligned with `targets` = s[1:]; and the figures derived from them.  An empty
+    result (N = 1) has NaN figures."""
+
+    def __init__(self, targets, logp, rank, entropy):
+        self.targets = np.asarray(targets, np.int32)
+        self.logp = np.asarray(logp, np.float32)
+        self.rank = np.asarray(rank, np.int32)
+        self.entropy = np.asarray(entropy, np.float32)
+        if not (self.targets.shape == self.logp.shape == self.rank.shape == self.entropy.shape and self.targets.ndim == 1):
+            raise ValueError('SequenceScore: the four arrays must be 1-D of one length')
+
+    def __len__(self):
+        return int(self.logp.size)
+
+    @property
+    def events(self):
+        return len(self)
+
+    @property
+    def log_likelihood(self):
+        """Sum of the log-probabilities (float64), nats."""
+        return float(self.logp.astype(np.float64).sum())
+
+    @property
+    def nll_per_event(self):
+        return -self.log_likelihood / len(self) if len(self) else float('nan')
+
+    @property
+    def bits_per_event(self):
+        return self.nll_per_event / math.log(2.0)
+
+    @property
+    def perplexity(self):
+        nll = self.nll_per_event
+        if nll != nll:
+            return float('nan')
+        return math.exp(nll) if nll < 709.0 else float('inf')
+
+    @property
+    def top1_accuracy(self):
+        return float((self.rank == 0).mean()) if len(self) else float('nan')
+
+    def by_event_type(self, event_ranges):
+        """{event type: (count, mean NLL or NaN)} over the scored events, `event_ranges` = composer_amd.dataset.event_ranges(...)
+        (event type -> range of ids)."""
+        out = collections.OrderedDict()
+        nll = -self.logp.astype(np.float64)
+        for t, interval in event_ranges.items():
+            sel = (self.targets >= interval.start) & (self.targets < interval.stop)
+            k = int(sel.sum())
+            out[t] = (k, float(nll[sel].sum() / k) if k else float('nan'))
+        return out
+
+    def to_dict(self, arrays=True):
+        d = {'events': len(self), 'nll_per_event': self.nll_per_event, 'bits_per_event': self.bits_per_event,
+             'perplexity': self.perplexity, 'top1_accuracy': self.top1_accuracy}
+        if arrays:
+            d.update(logp=[float(v) for v in self.logp], rank=[int(v) for v in self.rank], entropy=[float(v) for v in self.entropy])
+        return d
+
+
+def score_sequences(score_call, sequences, window, keep, max_tokens):
+    """The host side of `Transformer.score`, no GPU: plans `score_windows` for every sequence, packs the windows into as few
+    `score_call(x, y) -> (logp, rank, entropy)` calls as `max_tokens` (= B * T of a call) allows and scatters the rows that count
+    into one `SequenceScore` per sequence.  x, y: int32 [B, T]; the windows of a call are right-padded with id 0 to the call's T
+    and pad targets are -1, so are the targets of the rows before a window's first scored row.  A window is never split (its rows
+    need the whole context): one that is longer than `max_tokens` goes out alone in a call of its own length, and it is
+    `score_call`'s business to refuse it (cmp_score does, by name, when the model's workspace was sized smaller)."""
+    seqs = [np.ascontiguousarray(np.asarray(s, dtype=np.int64).reshape(-1)) for s in sequences]
+    jobs = []                                                       # (length, sequence, start, first scored row)
+    for k, s in enumerate(seqs):
+        if s.size == 0:
+            raise ValueError('score: sequence %d is empty' % k)
+        jobs += [(length, k, start, first) for start, length, first in score_windows(s.size, window, keep)]
+    jobs.sort(key=lambda j: (-j[0], j[1], j[2]))                    # longest first: a call's T is its first window's length
+    res = [(np.zeros(s.size - 1, np.float32), np.full(s.size - 1, -1, np.int32), np.zeros(s.size - 1, np.float32)) for s in seqs]
+    i = 0
+    while i < len(jobs):
+        T = jobs[i][0]
+        B = max(1, min(len(jobs) - i, int(max_tokens) // T))
+        x = np.zeros((B, T), np.int32)
+        y = np.full((B, T), -1, np.int32)
+        for b, (length, k, start, first) in enumerate(jobs[i:i + B]):
+            x[b, :length] = seqs[k][start:start + length]
+            y[b, first:length] = seqs[k][start + first + 1:start + length + 1]
+        outs = score_call(x, y)
+        for b, (length, k, start, first) in enumerate(jobs[i:i + B]):
+            for dst, src in zip(res[k], outs):
+                dst[start + first:start + length] = src[b, first:length]
+        i += B
+    return [SequenceScore(s[1:], *r) for s, r in zip(seqs, res)]
 
 
 def check_sampling(top_k, top_p):
@@ -189,6 +310,10 @@ class Transformer:
             self._ctx = None
             raise _lib.HipLibraryError("cmp_model_create failed (status %d): %s" % (rc, msg))
         self._h = h
+        # tokens per cmp_score call that `score` packs to: what the library's workspace holds at least (an earlier, larger call may have
+        # sized it bigger, which only means smaller calls than possible; with max_seq < window_size a full window exceeds this figure,
+        # is sent alone, and the library refuses it by name if its workspace is already sized smaller)
+        self._max_tokens = max(1, int(max_batch)) * max(1, min(int(max_seq or window_size), int(window_size)))
         self._specs = self._param_specs()
         self._learning_rate = 1e-3
         self._dp = None          # (rank, nranks) once init_data_parallel() ran
@@ -555,6 +680,35 @@ class Transformer:
         if cnt == 0:
             return float('nan'), float('nan')
         return tot / cnt, cor / cnt
+
+    # ------------------------------------------------------------------ scoring
+    def _score_call(self, x, y):
+        """cmp_score on one padded batch: (logp, rank, entropy), each [B, T]."""
+        x, y = self._ids(x), self._ids(y)
+        self._check_ids(x)
+        B, T = x.shape
+        logp, rank, ent = np.empty((B, T), np.float32), np.empty((B, T), np.int32), np.empty((B, T), np.float32)
+        _lib.check(self._lib.cmp_score(self._h, x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), B, T,
+                                       logp.ctypes.data_as(C.c_void_p), rank.ctypes.data_as(C.c_void_p),
+                                       ent.ctypes.data_as(C.c_void_p)), 'cmp_score')
+        return logp, rank, ent
+
+    def score(self, sequences, slide_keep=None):
+        """How likely are these event sequences under the model?  `sequences`: one sequence of ids, or a list of (ragged)
+        sequences; returns one `SequenceScore`, or a list of them.  Every position n >= 1 of a sequence s is scored against the
+        context s[n - c(n) : n], c = slide_context_length(n, window_size, slide_keep) (default window_size // 2): the plain causal
+        pass up to window_size, the conditioning of 'kv-slide' generation past it (`score_windows`).  logp / rank / entropy are
+        reduced from the fp32 logits on the device (cmp_score: temperature 1, no filter, no grammar); only [B, T] arrays come back.
+        A sequence of length 1 yields empty arrays."""
+        keep = self._slide_keep(slide_keep)
+        single = len(sequences) > 0 and np.ndim(sequences[0]) == 0
+        seqs = [sequences] if single else list(sequences)
+        for k, s in enumerate(seqs):
+            a = np.asarray(s)
+            if a.size and (a.min() < 0 or a.max() >= self.vocab_size):
+                raise ValueError('score: sequence %d holds an id outside [0, %d)' % (k, self.vocab_size))
+        out = score_sequences(self._score_call, seqs, self.window_size, keep, self._max_tokens)
+        return out[0] if single else out
 
     # ------------------------------------------------------------------ decode (cli.py:659-676)
     def _slide_keep(self, slide_keep):

@@ -199,6 +199,34 @@ int cmp_loss_and_grads(cmp_model* m, const int32_t* x, const int32_t* y, int B, 
 int cmp_eval_step(cmp_model* m, const int32_t* x, const int32_t* y, int B, int T,
                   double* loss_sum, int64_t* correct, int64_t* count);
 
+/* ---- scoring: per-event log-likelihood, rank and entropy of given sequences, reduced on the device ---------------------------
+ * The contract (composer_amd.transformer.score_windows / Transformer.score restate it on the host):
+ *   For a sequence s of N ids, W = window_size and 1 <= keep <= W - 1 (default W / 2), every position n in 1 .. N-1 is scored
+ *   against the context s[n - c(n) : n] at positions 0 .. c(n) - 1, c the context length of cmp_decode_begin_slide below:
+ *       c(n) = n                                          if n <= W
+ *       c(n) = keep + ((n - W - 1) mod (W - keep + 1))    otherwise.
+ *   For n <= W that is the plain causal pass; past W it is exactly the conditioning kv-slide generation draws s[n] under: scoring
+ *   and generation share one definition.  Position 0 has no context and is not scored.
+ *   Each scored position gets three numbers from its fp32 logits row z over the columns [0, V), at temperature 1, no filter, no
+ *   grammar (the model's distribution, not the one a truncated or constrained draw was taken from), y = s[n]:
+ *     logp    = z[y] - logsumexp(z), in nats;
+ *     rank    = #{c : z[c] > z[y] or (z[c] == z[y] and c < y)}: 0-based, exact on the fp32 values, the order of the truncated
+ *               sampler (below) and of the greedy argmax -- rank == 0 is cmp_k_softmax_xent's row_correct;
+ *     entropy = logsumexp(z) - sum_c p_c z[c], p = softmax(z); a column at -inf contributes 0.
+ *   A target outside [0, V) (negative values are the padding convention) marks a row as not scored: logp = 0, rank = -1, entropy
+ *   as computed.
+ * cmp_score: x, y host int32 [B,T]; row (b, t) is scored against x[b, 0..t] with target y[b, t] -- one window of the contract per
+ * batch row, right-padded by the caller (causal attention keeps padding from touching earlier rows).  Uploads the inputs, runs the
+ * inference forward pass (training = false), scores its logits with cmp_k_score_rows, synchronises once and copies back only the
+ * requested host [B,T] arrays (any of the three may be null).  Ids of x outside [0, V) fail the call before anything is enqueued.
+ * Read-only for everything that lasts: parameters, gradients, Adam state and iterations, a pending accumulation group, the
+ * metrics of the last train step and both decode chains are what they were.  The workspace is sized as for cmp_eval_step. */
+int cmp_score(cmp_model* m, const int32_t* x, const int32_t* y, int B, int T, float* logp, int32_t* rank, float* entropy);
+/* The kernel alone (dev pointers): logits fp32 [rows, ldz], columns [V, ldz) are padding of any content; y int32 [rows]; outputs
+ * [rows], any of them null.  One pass over the logits; writes nothing else. */
+int cmp_k_score_rows(void* stream, const float* logits, int ldz, const int32_t* y, float* logp, int32_t* rank, float* entropy,
+                     int rows, int V);
+
 /* ---- inference forward: Transformer.call(inputs, training=False) (transformer.py:696-833) -------
  * logits_out: host fp32 [B,T,V]. */
 int cmp_forward_logits(cmp_model* m, const int32_t* x, int B, int T, float* logits_out);

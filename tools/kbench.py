@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at the BASELINE C2 shapes (M = 32*1024 tokens, E=512, H=8, D=64), through the C ABI.
-    python tools/kbench.py [gemm] [attn] [ln] ...      prints one line per kernel: avg us, TFLOP/s or GB/s
+    python tools/kbench.py [gemm] [attn] [ln] [score] ...      prints one line per kernel: avg us, TFLOP/s or GB/s
 Used to iterate on a kernel with a 40-second GPU round trip; bench.py remains the headline measurement."""
 import ctypes as C
 import sys
@@ -189,6 +189,56 @@ def bench_ln():
     print("colsum [M,4E]   %8.1f us  %7.1f GB/s" % (us, M * 4 * E * 2 / us / 1e3))
 
 
+def bench_score():
+    """cmp_k_score_rows at the timed geometry's logits (131 072 rows, V = 390, ldz = 448: 235 MB) against cmp_k_softmax_xent with
+    dlogits = null on the same buffer -- the same single pass over the same bytes -- alternating the two, five repeats each; then
+    one cmp_score call at C2 geometry (B = 128, T = 1024, E = 512, L = 6, H = 8, bf16: the same 131 072 rows) against cmp_eval_step on the same batch."""
+    import time
+    import numpy as np
+    rows, V, ldz = 131072, 390, 448
+    z = torch.randn(rows, ldz, device="cuda") * 3
+    y = torch.randint(0, V, (rows,), device="cuda", dtype=torch.int32)
+    lp, en, rl = (torch.zeros(rows, device="cuda") for _ in range(3))
+    rk, rc = (torch.zeros(rows, device="cuda", dtype=torch.int32) for _ in range(2))
+    def score():
+        rc_ = lib.cmp_k_score_rows(st(), P(z), ldz, P(y), P(lp), P(rk), P(en), rows, V)
+        assert rc_ == 0, lib.cmp_last_error()
+    def xent():
+        rc_ = lib.cmp_k_softmax_xent(st(), P(z), ldz, P(y), None, P(rl), P(rc), rows, V, 1.0 / rows, BF16)
+        assert rc_ == 0, lib.cmp_last_error()
+    t = {"score": [], "xent": []}
+    for _ in range(5):
+        t["xent"].append(timeit(xent))
+        t["score"].append(timeit(score))
+    nbytes = rows * ldz * 4.0
+    for nm in ("xent", "score"):
+        v = sorted(t[nm])
+        print("%-28s rows=%d V=%d ldz=%d  repeats(us) %s  median %8.1f us  %7.1f GB/s" % (
+            "softmax_xent (dlogits=null)" if nm == "xent" else "score_rows", rows, V, ldz, " ".join("%.1f" % x for x in t[nm]), v[2],
+            nbytes / v[2] / 1e3))
+    sx, ss = sorted(t["xent"]), sorted(t["score"])
+    spread = (sx[-1] - sx[0]) / sx[2]
+    print("score / xent (medians) %.4f; yardstick spread (max - min) / median %.4f; accepted up to %.4f" % (ss[2] / sx[2], spread, 1.10 + spread))
+    from composer_amd.transformer import Transformer
+    Bm, Tm = 128, 1024
+    m = Transformer(V, 512, Tm, 6, 8, dtype="bf16", max_batch=Bm, max_seq=Tm)
+    rng = np.random.default_rng(0)
+    x = rng.integers(0, V, (Bm, Tm)).astype(np.int32)
+    yy = rng.integers(0, V, (Bm, Tm)).astype(np.int32)
+    def wall(fn, n=5):
+        fn(); fn()
+        out = []
+        for _ in range(n):
+            t0 = time.perf_counter(); fn(); out.append((time.perf_counter() - t0) * 1e3)
+        return sorted(out)
+    ev = wall(lambda: m.evaluate([(x, yy)]))
+    sc = wall(lambda: m._score_call(x, yy))
+    print("C2 geometry B=%d T=%d, host wall ms (5 calls, sorted): cmp_eval_step %s | cmp_score %s" % (
+        Bm, Tm, " ".join("%.3f" % v for v in ev), " ".join("%.3f" % v for v in sc)))
+    print("cmp_score - cmp_eval_step (medians) %.3f ms; the three [B, T] outputs are %d bytes to the host" % (sc[2] - ev[2], 3 * Bm * Tm * 4))
+    m.close()
+
+
 if __name__ == "__main__":
     GFLAGS = int(os.environ.get("KBENCH_GEMM_FLAGS", "0"))
     what = sys.argv[1:] or ["gemm", "attn", "ln"]
@@ -210,3 +260,5 @@ if __name__ == "__main__":
         bench_attn_fwd()
     if "ln" in what:
         bench_ln()
+    if "score" in what:
+        bench_score()
