@@ -1,7 +1,10 @@
 """The assertions of tests/kernel_arena.py can fail: CPU "kernels" written in torch, indexing a CPU arena through flat pointers the
 way device code does, one correct and six wrong in the ways hand-written tile kernels go wrong.  Each wrong one must be rejected by
 the check it targets (the arena for stores / loads outside the logical window and unwritten elements, the per-element bound for
-arithmetic).  To see that a class of error is caught, edit a copy of `fake_gemm` below -- not the library."""
+arithmetic).  To see that a class of error is caught, edit a copy of `fake_gemm` below -- not the library.
+The same for the optimiser: `fake_adam`, a numpy-fp32 statement of the Adam kernels, correct and wrong in ten ways, against
+`kernel_arena.adam_check`, plus the record of what the older Adam assertions let through."""
+import numpy as np
 import pytest
 import torch
 
@@ -189,3 +192,123 @@ def test_gemm_case_tables_are_pairwise_covering():
         if kind == "forced":
             for (ta, tb), M, N, (K, kz), epi in rows:
                 assert K % 64 == 0 or (ta and not tb) or kz
+
+
+# ------------------------------------------------------------------------------------------ Adam: the bound can fail
+# A numpy-fp32 statement of adam_kernel / adam_dev_kernel (csrc/elementwise.hip), unfused: every product, sum, quotient and square
+# root rounds once to fp32, in the kernel's order.  It runs on a CPU arena like the GPU cases do, with the arrays flush against
+# guards, and is held by KA.adam_check -- the very function tests/test_gpu_adam_update.py applies to the device's results.
+ADAM_HYPER = (1e-3, 0.9, 0.999, 1e-7)
+ADAM_BUGS = ["step+1", "step-1", "eps_in_sqrt", "eps_scaled", "no_eps", "factor_m_only", "v_beta1", "m0_update", "shadow_truncated", "f_touched"]
+
+
+def fake_adam(p, g, m, v, sh, n, lr, beta1, beta2, eps, step, factor, bug=None, f_range=None):
+    f32 = np.float32
+    lr, b1, b2, eps, fac = f32(lr), f32(beta1), f32(beta2), f32(eps), f32(factor)
+    t = float(step + {"step+1": 1, "step-1": -1}.get(bug, 0))
+    with np.errstate(all="ignore"):
+        corr2 = np.sqrt(1.0 - np.power(float(b2), t))
+        alpha = f32(float(lr) * corr2 / (1.0 - np.power(float(b1), t)))           # the host wrapper: float64, rounded once
+        pv, gv, mv, vv = (s.mem()[:n].numpy().copy() for s in (p, g, m, v))
+        gg = gv * fac
+        m1 = b1 * mv + (f32(1) - b1) * gg
+        gq = gv if bug == "factor_m_only" else gg
+        v1 = (b1 if bug == "v_beta1" else b2) * vv + (f32(1) - b2) * gq * gq
+        if bug == "eps_in_sqrt":
+            den = np.sqrt(v1 + eps)
+        elif bug == "eps_scaled":
+            den = np.sqrt(v1) + f32(float(eps) * corr2)
+        elif bug == "no_eps":
+            den = np.sqrt(v1)
+        else:
+            den = np.sqrt(v1) + eps
+        p1 = pv - alpha * (mv if bug == "m0_update" else m1) / den
+    assert p1.dtype == m1.dtype == v1.dtype == np.float32
+    if bug == "f_touched":                                   # one ulp: far inside the bound, only the bitwise claim sees it
+        p1[f_range] = np.nextafter(p1[f_range], f32(np.inf))
+    for s, a in ((p, p1), (m, m1), (v, v1)):
+        s.mem()[:n] = torch.from_numpy(a)
+    pt = torch.from_numpy(p1)
+    sh.mem()[:n] = KA.bf16_truncated(pt) if bug == "shadow_truncated" else pt.to(BF)
+
+
+def run_adam(step, factor, bug=None, lr=ADAM_HYPER[0], inputs=None):
+    inp, seg = inputs or KA.adam_inputs(factor)
+    n = inp["p0"].numel()
+    ar = Arena("cpu", 1 << 20)
+    p, m, v = (ar.vector(inp[k], F32, name=k[0], kind="acc") for k in ("p0", "m0", "v0"))
+    g = ar.vector(inp["g"], F32, name="g")
+    sh = ar.output(BF, 1, n, n, name="shadow")
+    ar.arm()
+    fake_adam(p, g, m, v, sh, n, lr, *ADAM_HYPER[1:], step, factor, bug=bug, f_range=seg["f"])
+    ar.check()
+    return KA.adam_check(inp, seg, p.host()[0], m.host()[0], v.host()[0], sh.host()[0], lr, *ADAM_HYPER[1:], step, factor, "fake adam")
+
+
+def test_adam_inputs_are_what_the_cases_need():
+    inp, seg = KA.adam_inputs(1.0 / 3.0)
+    n = inp["p0"].numel()
+    assert n % 4 == 0 and n % 1024 != 0 and n // 4 > 256 and all((s.stop - s.start) % 4 == 0 for s in seg.values())
+    assert sum(s.stop - s.start for s in seg.values()) == n
+    _, _, v1 = KA.adam_reference(inp["p0"], inp["g"], inp["m0"], inp["v0"], *ADAM_HYPER, 1, 1.0 / 3.0)
+    sq = np.sqrt(v1[seg["d"]])
+    assert sq.min() < 0.03e-7 and (sq < 1e-7).sum() > 100 and (sq > 1e-7).sum() > 100 and 10e-7 < sq.max() <= 32e-7   # both sides of eps, up to 30 eps
+    gf = np.abs(inp["g"][seg["d"]].double().numpy() * float(np.float32(1.0 / 3.0)))
+    assert 0.99e-9 <= gf.min() < 1e-8 and 1e-5 < gf.max() <= 1.01e-4
+    assert inp["g"][seg["g"]].abs().max() > 1e3
+
+
+@pytest.mark.parametrize("factor", [1.0, 0.5, 1.0 / 3.0])
+def test_correct_fake_adam_passes(factor):
+    """The numbers `adam_bounds` quotes: worst error / limit of the unfused numpy-fp32 statement over t = 1, 7, 1000 (and the two
+    steps at which beta^t underflows) -- p 0.50, m 0.31, v 0.38 at most (the run prints them per factor)."""
+    worst = {}
+    for step in (1, 2, 7, 1000, 10 ** 6, 2 ** 31 + 5):
+        w = run_adam(step, factor)
+        worst = {k: max(worst.get(k, 0.0), x) for k, x in w.items()}
+    print("factor", factor, "worst error/limit", worst)
+    assert all(0 < x <= 1.0 for x in worst.values())
+    run_adam(7, factor, lr=0.0)                                  # p bitwise unchanged, m and v moved
+
+
+@pytest.mark.parametrize("step", [1, 7, 1000])
+@pytest.mark.parametrize("bug", ADAM_BUGS)
+def test_wrong_fake_adam_is_rejected(bug, step):
+    """Every variant at every step: by the per-element bound (on p, or on v for the two that spoil v), by the arena's non-finite
+    check (no eps: 0 / 0 in segment f; step - 1 at t = 1: alpha = 0 / 0), by the shadow's bitwise claim, or by segment f's."""
+    match = {"shadow_truncated": "round-to-nearest-even image", "f_touched": "g = m = v = 0 was touched"}.get(bug, r"> limit|is nan|is inf|is -inf")
+    with pytest.raises(AssertionError, match=match):
+        run_adam(step, 0.5, bug=bug)
+
+
+def test_old_metric_would_have_passed_a_wrong_eps_and_a_wrong_step():
+    """The gap, written down.  The older Adam assertions (test_adam_keras_formulation, test_adam_guarded: max|d| / max|ref| < 1e-6 for
+    m, v and p with max|p| about 4, the shadow equal to the rounded p) on their own inputs (v0 ~ U(0, 0.01): sqrt(v) >> eps
+    everywhere) pass eps scaled by sqrt(1 - beta2^t) and no eps at all at t = 1, 7 and 1000, and a step count off by one in either
+    direction at t = 1000."""
+    n = 4096 + 8
+    gen = torch.Generator().manual_seed(9)
+    p0, gr = torch.randn(n, generator=gen), torch.randn(n, generator=gen) * 0.1
+    m0, v0 = torch.randn(n, generator=gen) * 0.01, torch.rand(n, generator=gen) * 0.01
+    inputs = ({"p0": p0, "g": gr, "m0": m0, "v0": v0}, {"f": slice(0, 0)})
+
+    def rel_err(a, b):
+        return ((a.double() - b).abs().max() / (b.abs().max() + 1e-30)).item()
+    for step, bugs in ((1, ("eps_scaled", "no_eps")), (7, ("eps_scaled", "no_eps")), (1000, ("eps_scaled", "no_eps", "step+1", "step-1"))):
+        g64 = gr.double() * 0.5
+        m1 = 0.9 * m0.double() + 0.1 * g64
+        v1 = 0.999 * v0.double() + 0.001 * g64 * g64
+        alpha = 1e-3 * (1 - 0.999 ** step) ** 0.5 / (1 - 0.9 ** step)
+        p1 = p0.double() - alpha * m1 / (v1.sqrt() + 1e-7)
+        for bug in bugs:
+            ar = Arena("cpu", 1 << 20)
+            p, m, v = (ar.vector(t, F32, name=nm, kind="acc") for t, nm in ((p0, "p"), (m0, "m"), (v0, "v")))
+            g = ar.vector(gr, F32, name="g")
+            sh = ar.output(BF, 1, n, n, name="shadow")
+            fake_adam(p, g, m, v, sh, n, *ADAM_HYPER, step, 0.5, bug=bug)
+            assert rel_err(m.host()[0], m1) < 1e-6 and rel_err(v.host()[0], v1) < 1e-6 and rel_err(p.host()[0], p1) < 1e-6, (step, bug)
+            assert torch.equal(sh.host()[0], p.host()[0].to(BF))
+            # ... and the new bound sees each of them on the same old inputs?  Only the wrong step: eps needs the new segments.
+            if bug.startswith("step"):
+                with pytest.raises(AssertionError, match="> limit"):
+                    KA.adam_check(inputs[0], inputs[1], p.host()[0], m.host()[0], v.host()[0], None, *ADAM_HYPER, step, 0.5, "old inputs")
