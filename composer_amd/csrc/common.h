@@ -53,8 +53,8 @@ void prof_stop(int cls, hipStream_t s, double work, double bytes);
 #define PROF_START(cls, s) do { if (g_prof_cls == (cls)) prof_start((cls), (s)); } while (0)
 #define PROF_STOP(cls, s, work, bytes) do { if (g_prof_cls == (cls)) prof_stop((cls), (s), (work), (bytes)); } while (0)
 
-// Per-launch extras of the GEMM launcher (gemm.hip: gemm_run) that the C ABI's cmp_k_gemm does not carry.  The model driver
-// fills one per call, so nothing about a launch lives in process-wide state.
+#include "gemm_plan.h"      // GemmDesc, GemmExtra, LnEpi and the launch plan: host-only, no HIP
+
 // Item-counter workspace of the persistent GEMM kernels (gemm.hip: ItemPuller / sched_next): two alternating counter sets on
 // the device.  One per cmp_ctx (allocated on first use, freed by cmp_ctx_destroy); launches that arrive without a context
 // (cmp_k_gemm) use a process-wide table keyed by (device, stream) under a lock that is held across the launch.
@@ -62,29 +62,6 @@ struct SchedWs {
     uint32_t* dev = nullptr;
     int parity = 0;
     bool dirty = false;          // a launch that used the counters failed: both sets are re-zeroed before the next use
-};
-// LayerNorm folded into the epilogues of the forward GEMMs (gemm.hip: epi_tile<.., LNM, NP>; full 256x256 tiles, bf16).  The
-// statistics of a row travel as PARTIALS: (mean, M2 = sum of squared deviations from that mean) of every 256-column segment of
-// the row, written by the epilogue of the GEMM (or the embedding kernel) that produced the row and merged by whoever consumes
-// it (Chan's parallel update -- never a sum of squares).
-//   consumer, fold (c_attn / c_fc: transformer.py:583-584,591 followed by Conv1D :205-209):
-//       LN(x).W + b = rstd * (x.(gamma o W)) - rstd*mean * colsum(gamma o W) + (beta.W + b)
-//     the GEMM runs on the RAW rows x and the gamma-scaled weight shadow; `cs` = colsum of that shadow, bias = beta.W + b.
-//   consumer, residual (attention c_proj, :587 r = LN1(x) + dropout(proj)): the residual operand is rebuilt from the raw
-//     row, its statistics and gamma / beta.
-//   producer (both c_proj): the epilogue owns a 256-column tile of every output row and emits that segment's partial.
-struct LnEpi {
-    const float* in_part = nullptr;   // [rows][np][2] partial statistics of the LayerNorm input's rows (null: no LayerNorm on the way in)
-    int np = 0;                       // segments per row = E / 256
-    float eps = 0.f;
-    const float* cs = nullptr;        // fold: [N] column sums of the gamma-scaled bf16 weight
-    const float* gamma = nullptr;     // residual rebuild: [N] gamma, beta of the LayerNorm whose output is the residual operand
-    const float* beta = nullptr;
-    float* out_part = nullptr;        // [rows][N / 256][2] partial statistics of the OUTPUT rows (null: not wanted)
-    // Round 6, the backward pass of the fused block path ("scale" mode, with in_part): nothing is normalised, the row's rstd is a
-    // FACTOR -- EPI_GELUGRAD writes rstd o (acc * gelu'(aux)) (the column sums of the unscaled product still go to the launch's colsum);
-    // EPI_RESID adds rstd o resid instead of resid (model.hip: backward).
-    int scale = 0;
 };
 // (mean, rstd) of a row from its np partials of 256 columns each
 __device__ __forceinline__ void ln_merge_parts(const float* __restrict__ p, int np, float eps, float& mean, float& rstd) {
@@ -100,20 +77,6 @@ __device__ __forceinline__ void ln_merge_parts(const float* __restrict__ p, int 
     rstd = __builtin_amdgcn_rsqf(m2 / (256.0f * (float)np) + eps);
 }
 
-struct GemmExtra {
-    LnEpi ln;                    // LayerNorm fused into this launch's epilogue (forward GEMMs of the fused block path, model.hip)
-    float* colsum = nullptr;     // also add the column sums of the output to colsum[0..N) (the bias gradient that goes with an
-                                 // input-gradient GEMM); fused into the epilogue where possible, else a colsum pass after it
-    float* slab_ws = nullptr;    // split-K: per-split fp32 partial tiles + fixed-order reduce instead of float atomics
-    size_t slab_bytes = 0;
-    int role = -1;               // cmp_prof_* timing class: 0 forward, 1 dgrad, 2 wgrad, -1 = by operand layout
-    int max_wgs = 0;             // cap on the persistent kernels' grid (CUs left to a concurrent RCCL kernel); 0 = all 256
-    bool rev = false;            // persistent 256x256 kernel: walk every XCD group's run of tiles from its end (gemm.hip: item_coords)
-    bool dp = false;             // the launch belongs to a data-parallel job: persistent kernels hand their items out dynamically
-    SchedWs* sched = nullptr;    // the calling context's item-counter workspace (a cmp_ctx is single-threaded by contract: no lock)
-    struct WgradWs* wws = nullptr;     // grouped weight gradients: the caller's partial-tile workspace selects the last-arriver form
-                                       // (no float atomics: deterministic mode); null: the float-atomic form (default, faster)
-};
 // Partial-tile workspace of the grouped weight-gradient launches of ONE stream (launches on a stream run one after the other, so
 // every decoder block's launch uses the same slots); grown by wgrad_group_run when an item table needs more, freed by the owner.
 struct WgradWs {
@@ -140,9 +103,7 @@ struct WgradGroup {              // owned by the caller, one per call site whose
 // returns CMP_OK with *handled = false when the shapes do not fit the grouped kernel (the caller then runs the problems one by one)
 int wgrad_group_run(void* stream, WgradGroup* g, const WgradProblem* probs, int nprob, int K, const GemmExtra& ex, bool* handled);
 void wgrad_group_free(WgradGroup* g);
-int gemm_run(void* stream, int dtype, int ta, int tb, int M, int N, int K, const void* A, int lda, const void* Bm, int ldb,
-             void* C, int ldc, const float* bias, int act, void* aux, int ldaux, const void* resid, int ldr, int out_fp32,
-             int splitk, float p_drop, uint64_t seed, uint32_t rng_stream, int flags, const GemmExtra& ex);
+int gemm_run(void* stream, const GemmDesc& d, const GemmExtra& ex);
 // Round 6 (backward pass of the fused block path): the attention backward kernels store rstd o [dQ | dK | dV], rstd being that of the
 // token's row in the LayerNorm whose output fed c_attn (ln_stats_merge_kernel) -- the c_attn weight gradient then
 // runs on the raw rows (elementwise.hip: wgrad_ln_fix_kernel).  The bias gradient stays the column sums of the unscaled gradient.

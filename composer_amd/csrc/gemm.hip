@@ -60,9 +60,6 @@ __device__ __forceinline__ void epilogue_store(const Epilogue& ep, void* C, int 
 // =================================================================================================
 // fp32 (parity mode)
 // =================================================================================================
-#define F_BM 64
-#define F_BN 64
-#define F_BK 16
 #define F_LD 80   // LDS row stride in floats: 80 mod 32 = 16 -> the two k-rows of a 32-lane read group hit disjoint banks
 
 __global__ __launch_bounds__(256) void gemm_f32_kernel(int M, int N, int K, const float* __restrict__ A, int64_t sam,
@@ -148,10 +145,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(int M, int N, int K, cons
 // =================================================================================================
 // bf16
 // =================================================================================================
-#define G_BM 128
-#define G_BN 128
-#define G_BK 64
-#define G_IMG (128 * 64 * 2)   // bytes per operand image
 
 // K-major image [128 rows][64 k]: byte offset of 16-B chunk c (0..7) of row r
 __device__ __forceinline__ int kmaj_off(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
@@ -499,8 +492,7 @@ __device__ __forceinline__ void epi_finish8(const Epilogue& ep, void* C, int ldc
 // previous chunk's STORES to be acknowledged (measured with in-kernel stamps: 18-50k cycles for the 16 chunks of a
 // tile, the store round trip serialised 16 times).  A kind fixes what touches memory inside the loop, the loop is
 // straight-line code, the operand loads run two chunks ahead of their use and the waits are counted: stores are
-// fire-and-forget.
-enum { EPI_GENERIC = 0, EPI_PLAIN = 1, EPI_GELU_AUX = 2, EPI_RESID = 3, EPI_GELUGRAD = 4, EPI_PLAIN32 = 5 };
+// fire-and-forget.  (The EPI_* values and the rule that picks one per launch are in gemm_plan.h.)
 //   EPI_PLAIN32  : C (fp32, ragged last tile column) = acc + bias, with the LayerNorm fold only: ln_f into the tied-logits GEMM of
 //                  the fused block path (transformer.py:811, 818)
 //   EPI_PLAIN    : C = acc (+ bias)                                  c_attn forward; dgrad without epilogue operands
@@ -848,14 +840,6 @@ __device__ __forceinline__ void epi_tile(const Epilogue& ep, bf16_t* __restrict_
         }
     }
 }
-// the kind a launch may use (full tiles only; everything else takes the generic run-time epilogue)
-static int epi_kind_of(const Epilogue& ep, int M, int N, bool swap, bool slabs, int tile = 256) {
-    if (!swap || slabs || ep.out_fp32 || ep.dbg_nostore || ep.atomic || M % tile || N % tile) return EPI_GENERIC;
-    if (ep.act == 1) return (!ep.resid && !ep.drop.thr) ? EPI_GELU_AUX : EPI_GENERIC;
-    if (ep.act == 2) return (!ep.resid && !ep.drop.thr && !ep.bias) ? EPI_GELUGRAD : EPI_GENERIC;
-    if (ep.resid) return EPI_RESID;
-    return ep.drop.thr ? EPI_GENERIC : EPI_PLAIN;
-}
 
 // RING (launches of at most one workgroup per CU -- the reference's default configuration runs GEMMs of 16-64 tiles on 256 CUs): a ring of
 // four k-stages, three in flight, LDS-DMA issued from inline asm behind hand-counted s_waitcnt vmcnt.  The two-stage loop below drains
@@ -1150,9 +1134,6 @@ struct ItemPuller {
 //   * same LDS images / swizzles / direct-to-LDS staging / range-checked descriptors as the 128^2 fast path.
 // LDS: 2 stages x (A 32 KiB + B 32 KiB) = 128 KiB.
 // =================================================================================================
-#define H_BM 256
-#define H_BN 256
-#define H_IMG (256 * 64 * 2)
 __device__ __forceinline__ int cslow_off512(int k, int c) { return k * 512 + ((c ^ (((k & 3) | (((k >> 3) & 1) << 2)) << 1)) << 4); }
 
 template <bool KM, int AUX = 0>
@@ -1460,7 +1441,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_256_kernel(int M, int N, int
 //     -> 32 MFMAs per wave from the current stage;
 //   * the next item's first three stages are issued before the epilogue, which parks accumulators in stage 3.
 // =================================================================================================
-#define P_BK 32
 #define P_IMG (256 * 32 * 2)      // 16 KiB per operand image
 #define P_STAGE (2 * P_IMG)
 
@@ -1964,58 +1944,71 @@ extern "C" int cmp_gemm_set_stamps(void* dev_buf) {
     g_gemm_stamps = (unsigned long long*)dev_buf;
     return CMP_OK;
 }
+// ---- launching a plan (gemm_plan.h).  The helpers below decide nothing: they map the plan's family, layout and epilogue kind to
+// the instantiation and launch it with the plan's grid, LDS bytes and split.
+struct GemmLaunch {
+    hipStream_t s;
+    const GemmPlan& p;
+    const GemmDesc& d;
+    void* C;                         // the output, or the slab workspace of a split-K launch that is reduced afterwards
+    const Epilogue& ep;
+    int64_t slab_stride;             // elements between the slabs of two splits (0: no slabs)
+    unsigned long long* stamps;
+};
+// the kernels' layout parameters as compile-time values: f(A_KM, B_KM)
+template <typename F>
+static void with_layout(bool a_km, bool b_km, F f) {
+    if (a_km && !b_km) f(std::true_type(), std::false_type());
+    else if (a_km) f(std::true_type(), std::true_type());
+    else if (!b_km) f(std::false_type(), std::false_type());
+    else f(std::false_type(), std::true_type());
+}
 template <bool A_KM, bool B_KM, int NWM, int NST>
-static bool launch_p4_cfg(hipStream_t s, bool swap, int M, int N, int K, const bf16_t* a, int lda, const bf16_t* b, int ldb,
-                          void* C, int ldc, const Epilogue& ep, int per, int nsplit, int64_t slab_stride, int max_wgs) {
-    constexpr int BM = 128 * NWM;
-    const size_t smem = (size_t)NST * (BM * P_BK * 2 + 256 * P_BK * 2) + 16;      // + the item slot
+static void launch_p4_cfg(const GemmLaunch& L) {
+    const GemmPlan& p = L.p;
+    const GemmDesc& d = L.d;
     {
         static std::once_flag attr_once;         // (per instantiation; two threads may launch through one library)
-        std::call_once(attr_once, [smem]() {
+        std::call_once(attr_once, [smem = p.smem]() {
             (void)hipFuncSetAttribute((const void*)gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
             (void)hipFuncSetAttribute((const void*)gemm_bf16_p4_kernel<A_KM, B_KM, false, NWM, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         });
     }
-    const int tiles_n = cdiv(N, H_BN), ntiles = tiles_n * cdiv(M, BM);
-    const int grid = std::min(ntiles * nsplit, NWM == 1 ? 2 * max_wgs : max_wgs);   // persistent: one (two) workgroups per CU in use
+    auto run = [&](auto kern, int64_t slab_stride) {
+        kern<<<p.grid_x, p.block, p.smem, L.s>>>(d.M, d.N, d.K, (const bf16_t*)d.A, d.lda, (const bf16_t*)d.B, d.ldb, L.C, d.ldc, L.ep, p.per, p.nsplit,
+                                                  p.tiles_n, p.ntiles, slab_stride, L.stamps);
+    };
+    auto go = [&](auto kern) {                   // the instantiations beyond the two of attr_once
+        allow_smem((const void*)kern, p.smem);
+        run(kern, L.slab_stride);
+    };
     if constexpr (A_KM && !B_KM) {
         // the forward layout carries the compile-time epilogue kinds (and the diagnostic timeline build)
-        const int kind = epi_kind_of(ep, M, N, swap, slab_stride != 0);
-        auto go = [&](auto kern) {
-            allow_smem((const void*)kern, smem);
-            kern<<<grid, 256 * NWM, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, tiles_n, ntiles, slab_stride, g_gemm_stamps);
-        };
-        if (g_gemm_stamps && swap) {
-            if constexpr (NWM == 2) {
-                if (kind == EPI_PLAIN) go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, true, EPI_PLAIN>);
-                else if (kind == EPI_GELU_AUX) go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, true, EPI_GELU_AUX>);
-                else if (kind == EPI_RESID) go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, true, EPI_RESID>);
-                else go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, true, EPI_GENERIC>);
-                return kind == EPI_PLAIN || kind == EPI_GELU_AUX || kind == EPI_RESID;
+        if constexpr (NWM == 2) {
+            if (p.diag) {
+                switch (p.kind) {
+                    case EPI_PLAIN: return go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, true, EPI_PLAIN>);
+                    case EPI_GELU_AUX: return go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, true, EPI_GELU_AUX>);
+                    case EPI_RESID: return go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, true, EPI_RESID>);
+                    default: return go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, true, EPI_GENERIC>);
+                }
             }
         }
-        if (kind == EPI_PLAIN) { go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, false, EPI_PLAIN>); return true; }
-        if (kind == EPI_GELU_AUX) { go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, false, EPI_GELU_AUX>); return true; }
-        if (kind == EPI_RESID) { go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, false, EPI_RESID>); return true; }
-    }
-    if constexpr (!A_KM && !B_KM && NWM == 2) {
-        if (g_gemm_stamps && !swap) {        // diagnostic timeline of the wgrad layout (split-K atomics epilogue)
-            allow_smem((const void*)gemm_bf16_p4_kernel<A_KM, B_KM, false, NWM, NST, true>, smem);
-            gemm_bf16_p4_kernel<A_KM, B_KM, false, NWM, NST, true><<<grid, 256 * NWM, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, tiles_n, ntiles, (int64_t)0, g_gemm_stamps);
-            return false;
+        switch (p.kind) {
+            case EPI_PLAIN: return go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, false, EPI_PLAIN>);
+            case EPI_GELU_AUX: return go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, false, EPI_GELU_AUX>);
+            case EPI_RESID: return go(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST, false, EPI_RESID>);
+            default: break;
         }
     }
-    if (swap)
-        gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST><<<grid, 256 * NWM, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, tiles_n, ntiles, slab_stride, g_gemm_stamps);
-    else
-        gemm_bf16_p4_kernel<A_KM, B_KM, false, NWM, NST><<<grid, 256 * NWM, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, tiles_n, ntiles, (int64_t)0, g_gemm_stamps);
-    return false;
-}
-template <bool A_KM, bool B_KM>
-static bool launch_p4(hipStream_t s, int cfg, bool swap, int M, int N, int K, const bf16_t* a, int lda, const bf16_t* b, int ldb,
-                      void* C, int ldc, const Epilogue& ep, int per, int nsplit, int64_t slab_stride, int max_wgs) {
-    if (cfg == 1) return launch_p4_cfg<A_KM, B_KM, 1, 3>(s, swap, M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, slab_stride, max_wgs);
-    return launch_p4_cfg<A_KM, B_KM, 2, 4>(s, swap, M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, slab_stride, max_wgs);
+    if constexpr (!A_KM && !B_KM && NWM == 2) {
+        if (p.diag) {                            // diagnostic timeline of the wgrad layout (split-K atomics epilogue)
+            allow_smem((const void*)gemm_bf16_p4_kernel<A_KM, B_KM, false, NWM, NST, true>, p.smem);
+            return run(gemm_bf16_p4_kernel<A_KM, B_KM, false, NWM, NST, true>, (int64_t)0);
+        }
+    }
+    if (p.swap) run(gemm_bf16_p4_kernel<A_KM, B_KM, true, NWM, NST>, L.slab_stride);
+    else run(gemm_bf16_p4_kernel<A_KM, B_KM, false, NWM, NST>, (int64_t)0);
 }
 
 // C[i] += sum_s slab[s][i]  (fixed order: reproducible); 16 bytes per lane
@@ -2067,89 +2060,89 @@ extern "C" int cmp_gemm_set_workspace(void* ws, int64_t bytes) {
 }
 
 template <bool A_KM, bool B_KM>
-static bool launch_256(hipStream_t s, int grid, bool swap, int M, int N, int K, const bf16_t* a, int lda, const bf16_t* b, int ldb,
-                       void* C, int ldc, const Epilogue& ep, int per, int nsplit, int tiles_n, int ntiles) {
-    const size_t smem = 4 * H_IMG + 32;                                             // + the scheduler words
+static void launch_256(const GemmLaunch& L) {
+    const GemmPlan& p = L.p;
+    const GemmDesc& d = L.d;
     {
         static std::once_flag attr_once;
-        std::call_once(attr_once, [smem]() {
+        std::call_once(attr_once, [smem = p.smem]() {
             (void)hipFuncSetAttribute((const void*)gemm_bf16_256_kernel<A_KM, B_KM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
             (void)hipFuncSetAttribute((const void*)gemm_bf16_256_kernel<A_KM, B_KM, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         });
     }
+    auto run = [&](auto kern) {
+        kern<<<p.grid_x, p.block, p.smem, L.s>>>(d.M, d.N, d.K, (const bf16_t*)d.A, d.lda, (const bf16_t*)d.B, d.ldb, L.C, d.ldc, L.ep, p.per, p.nsplit,
+                                                  p.tiles_n, p.ntiles);
+    };
     if constexpr (A_KM && B_KM) {        // the dgrad layout carries the compile-time epilogue kinds
-        const int kind = epi_kind_of(ep, M, N, swap, false);
         auto go = [&](auto kern) {
-            allow_smem((const void*)kern, smem);
-            kern<<<grid, 512, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, tiles_n, ntiles);
+            allow_smem((const void*)kern, p.smem);
+            run(kern);
         };
-        const int lnm = (ep.ln.in_part ? 1 : 0) | (ep.ln.out_part ? 2 : 0);
-        if (lnm) {
-            // LayerNorm-fused kinds (gemm_run has checked that the launch fits one): fold into c_attn / c_fc, statistics out of
-            // (and the rebuilt residual into) both c_proj
-#define LN_GO(KIND, LNM_, NP_) do { go(gemm_bf16_256_kernel<A_KM, B_KM, true, KIND, LNM_, NP_>); return true; } while (0)
-#define LN_NP(KIND, LNM_) do { if (ep.ln.np == 2) LN_GO(KIND, LNM_, 2); if (ep.ln.np == 3) LN_GO(KIND, LNM_, 3); } while (0)
-            if (ep.out_fp32 && lnm == 1) LN_NP(EPI_PLAIN32, 1);
-            if (kind == EPI_PLAIN && lnm == 1) LN_NP(EPI_PLAIN, 1);
-            if (kind == EPI_GELU_AUX && lnm == 1) LN_NP(EPI_GELU_AUX, 1);
-            if (kind == EPI_GELUGRAD && lnm == 1 && ep.ln.scale) LN_NP(EPI_GELUGRAD, 5);
-            if (kind == EPI_RESID && lnm == 1 && ep.ln.scale) LN_NP(EPI_RESID, 5);
-            if (kind == EPI_RESID && lnm == 3) LN_NP(EPI_RESID, 3);
-            if (kind == EPI_RESID && lnm == 2) LN_GO(EPI_RESID, 2, 1);
-#undef LN_NP
-#undef LN_GO
-            return false;       // unreachable after gemm_run's check
+#define KIND_256(KIND, LNM_, NP_) case (KIND) * 100 + (LNM_) * 10 + (NP_): return go(gemm_bf16_256_kernel<A_KM, B_KM, true, KIND, LNM_, NP_>)
+#define KIND_256_NP(KIND, LNM_) KIND_256(KIND, LNM_, 2); KIND_256(KIND, LNM_, 3)
+        switch (p.kind * 100 + p.lnm * 10 + p.np) {
+            // LayerNorm-fused kinds: fold into c_attn / c_fc (and ln_f into the logits), statistics out of (and the rebuilt residual
+            // into) both c_proj, the backward pass's scale forms
+            KIND_256_NP(EPI_PLAIN32, 1);
+            KIND_256_NP(EPI_PLAIN, 1);
+            KIND_256_NP(EPI_GELU_AUX, 1);
+            KIND_256_NP(EPI_GELUGRAD, 5);
+            KIND_256_NP(EPI_RESID, 5);
+            KIND_256_NP(EPI_RESID, 3);
+            KIND_256(EPI_RESID, 2, 1);
+            KIND_256(EPI_PLAIN, 0, 1);
+            KIND_256(EPI_RESID, 0, 1);
+            KIND_256(EPI_GELUGRAD, 0, 1);
+            KIND_256(EPI_GELU_AUX, 0, 1);
+            default: break;
         }
-        if (kind == EPI_PLAIN) { go(gemm_bf16_256_kernel<A_KM, B_KM, true, EPI_PLAIN>); return true; }
-        if (kind == EPI_RESID) { go(gemm_bf16_256_kernel<A_KM, B_KM, true, EPI_RESID>); return true; }
-        if (kind == EPI_GELUGRAD) { go(gemm_bf16_256_kernel<A_KM, B_KM, true, EPI_GELUGRAD>); return true; }
-        if (kind == EPI_GELU_AUX) { go(gemm_bf16_256_kernel<A_KM, B_KM, true, EPI_GELU_AUX>); return true; }
+#undef KIND_256_NP
+#undef KIND_256
     }
-    if (swap)
-        gemm_bf16_256_kernel<A_KM, B_KM, true><<<grid, 512, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, tiles_n, ntiles);
-    else
-        gemm_bf16_256_kernel<A_KM, B_KM, false><<<grid, 512, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, tiles_n, ntiles);
-    return false;
+    if (p.swap) run(gemm_bf16_256_kernel<A_KM, B_KM, true>);
+    else run(gemm_bf16_256_kernel<A_KM, B_KM, false>);
 }
 
 template <bool A_KM, bool B_KM>
-static bool launch_fast(hipStream_t s, dim3 grid, size_t smem, bool swap, int M, int N, int K, const bf16_t* a, int lda,
-                        const bf16_t* b, int ldb, void* C, int ldc, const Epilogue& ep, int per, int tiles_n, int ntiles) {
+static void launch_fast(const GemmLaunch& L) {
+    const GemmPlan& p = L.p;
+    const GemmDesc& d = L.d;
+    auto run = [&](auto kern, size_t smem) {
+        kern<<<dim3(p.grid_x, p.grid_y), p.block, smem, L.s>>>(d.M, d.N, d.K, (const bf16_t*)d.A, d.lda, (const bf16_t*)d.B, d.ldb, L.C, d.ldc, L.ep, p.per,
+                                                               p.tiles_n, p.ntiles);
+    };
     if constexpr (A_KM && B_KM) {        // forward (transposed weight shadow) and dgrad layout
-        static const bool kinds_on = [] { const char* e = getenv("COMPOSER_GEMM_FAST_KINDS"); return !(e && e[0] == '0'); }();
-        const int kind = (kinds_on && grid.y == 1) ? epi_kind_of(ep, M, N, swap, false, 128) : EPI_GENERIC;
-        auto go = [&](auto kern) { kern<<<grid, 256, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per, tiles_n, ntiles); };
-        // at most one workgroup per CU and whole k-steps: the four-stage ring (COMPOSER_GEMM_RING=0 off, =<n> from n k-steps on)
-        static const int ring_min = [] { const char* e = getenv("COMPOSER_GEMM_RING"); return e ? atoi(e) : 2; }();       // fewest k-steps that take it
-        if (kind != EPI_GENERIC && ring_min > 0 && ntiles <= 256 && K % G_BK == 0 && K >= std::max(2, ring_min) * G_BK) {
-            constexpr int smem_ring = 4 * 2 * G_IMG;
+        if (p.family == CMP_GEMM_FAM_RING) {
             static const bool attr = [] {
                 bool ok = true;
-                auto set = [&](auto kern) { ok = ok && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem_ring) == hipSuccess; };
+                auto set = [&](auto kern) { ok = ok && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * G_IMG) == hipSuccess; };
                 set(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_PLAIN, true>);
                 set(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_RESID, true>);
                 set(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_GELUGRAD, true>);
                 set(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_GELU_AUX, true>);
                 return ok;
             }();
-            if (attr) {
-                auto gor = [&](auto kern) { kern<<<grid, 256, smem_ring, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per, tiles_n, ntiles); };
-                if (kind == EPI_PLAIN) { gor(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_PLAIN, true>); return true; }
-                if (kind == EPI_RESID) { gor(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_RESID, true>); return true; }
-                if (kind == EPI_GELUGRAD) { gor(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_GELUGRAD, true>); return true; }
-                if (kind == EPI_GELU_AUX) { gor(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_GELU_AUX, true>); return true; }
+            if (attr) {                  // (a runtime that refuses the LDS opt-in gets the two-stage form of the same kind)
+                switch (p.kind) {
+                    case EPI_PLAIN: return run(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_PLAIN, true>, p.smem);
+                    case EPI_RESID: return run(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_RESID, true>, p.smem);
+                    case EPI_GELUGRAD: return run(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_GELUGRAD, true>, p.smem);
+                    case EPI_GELU_AUX: return run(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_GELU_AUX, true>, p.smem);
+                    default: break;
+                }
             }
         }
-        if (kind == EPI_PLAIN) { go(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_PLAIN>); return true; }
-        if (kind == EPI_RESID) { go(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_RESID>); return true; }
-        if (kind == EPI_GELUGRAD) { go(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_GELUGRAD>); return true; }
-        if (kind == EPI_GELU_AUX) { go(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_GELU_AUX>); return true; }
+        switch (p.kind) {
+            case EPI_PLAIN: return run(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_PLAIN>, 4 * G_IMG);
+            case EPI_RESID: return run(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_RESID>, 4 * G_IMG);
+            case EPI_GELUGRAD: return run(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_GELUGRAD>, 4 * G_IMG);
+            case EPI_GELU_AUX: return run(gemm_bf16_fast_kernel<A_KM, B_KM, true, EPI_GELU_AUX>, 4 * G_IMG);
+            default: break;
+        }
     }
-    if (swap)
-        gemm_bf16_fast_kernel<A_KM, B_KM, true><<<grid, 256, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per, tiles_n, ntiles);
-    else
-        gemm_bf16_fast_kernel<A_KM, B_KM, false><<<grid, 256, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per, tiles_n, ntiles);
-    return false;
+    if (p.swap) run(gemm_bf16_fast_kernel<A_KM, B_KM, true>, p.smem);
+    else run(gemm_bf16_fast_kernel<A_KM, B_KM, false>, p.smem);
 }
 
 // =================================================================================================
@@ -2438,10 +2431,15 @@ extern "C" int cmp_k_wgrad_group(void* stream, int nprob, const void* const* A, 
     return CMP_OK;
 }
 
-extern "C" int cmp_k_gemm(void* stream, int dtype, int ta, int tb, int M, int N, int K, const void* A, int lda,
-                          const void* Bm, int ldb, void* C, int ldc, const float* bias, int act, void* aux, int ldaux,
-                          const void* resid, int ldr, int out_fp32, int splitk, float p_drop, uint64_t seed,
-                          uint32_t rng_stream, int flags) {
+// the arguments of cmp_k_gemm behind the stream, in the order of GemmDesc's fields
+#define GEMM_ABI_PARAMS                                                                                                                  \
+    int dtype, int ta, int tb, int M, int N, int K, const void *A, int lda, const void *Bm, int ldb, void *C, int ldc, const float *bias, \
+        int act, void *aux, int ldaux, const void *resid, int ldr, int out_fp32, int splitk, float p_drop, uint64_t seed,                 \
+        uint32_t rng_stream, int flags
+#define GEMM_ABI_DESC \
+    GemmDesc { dtype, ta, tb, M, N, K, A, lda, Bm, ldb, C, ldc, bias, act, aux, ldaux, resid, ldr, out_fp32, splitk, p_drop, seed, rng_stream, flags }
+// consumes this thread's one-shot state (the arming calls above)
+static GemmExtra take_armed() {
     GemmExtra ex;
     ex.colsum = t_colsum_next;
     t_colsum_next = nullptr;
@@ -2449,165 +2447,89 @@ extern "C" int cmp_k_gemm(void* stream, int dtype, int ta, int tb, int M, int N,
     t_ln_next = LnEpi{};
     ex.slab_ws = t_slab_ws;
     ex.slab_bytes = t_slab_bytes;
-    return gemm_run(stream, dtype, ta, tb, M, N, K, A, lda, Bm, ldb, C, ldc, bias, act, aux, ldaux, resid, ldr, out_fp32, splitk,
-                    p_drop, seed, rng_stream, flags, ex);
+    return ex;
+}
+// COMPOSER_GEMM_FAST_KINDS=0: no compile-time kinds on the 128x128 kernel; COMPOSER_GEMM_RING=0: its four-stage ring off, =<n>: from
+// n k-steps on (both read once per process); the stamp buffer per call
+static GemmEnv gemm_env(bool stamps) {
+    static const bool kinds_on = [] { const char* e = getenv("COMPOSER_GEMM_FAST_KINDS"); return !(e && e[0] == '0'); }();
+    static const int ring_min = [] { const char* e = getenv("COMPOSER_GEMM_RING"); return e ? atoi(e) : 2; }();
+    return GemmEnv{kinds_on, ring_min, stamps};
+}
+extern "C" int cmp_k_gemm(void* stream, GEMM_ABI_PARAMS) { return gemm_run(stream, GEMM_ABI_DESC, take_armed()); }
+// the plan of the launch cmp_k_gemm would make of these arguments: no HIP call, nothing dereferenced (tests on a machine without a device)
+extern "C" int cmp_gemm_plan(GEMM_ABI_PARAMS, cmp_gemm_plan_info* out) {
+    CMP_REQUIRE(out != nullptr, "gemm_plan: out is null");
+    const GemmPlan p = gemm_plan(GEMM_ABI_DESC, take_armed(), gemm_env(g_gemm_stamps != nullptr));
+    if (p.status != CMP_OK) {
+        cmp_set_error("%s", p.msg);
+        return p.status;
+    }
+    *out = cmp_gemm_plan_info{p.family, p.a_km, p.b_km, p.swap, p.kind, p.lnm, p.np, p.diag, (int)p.grid_x, (int)p.grid_y, (int)p.grid_z, (int)p.block,
+                              (int64_t)p.smem, p.nk, p.per, p.nsplit, p.tiles_n, p.ntiles, p.slabs, p.reduce_grid, p.colsum_fused, p.colsum_pass,
+                              p.cls, p.sched, p.empty};
+    return CMP_OK;
 }
 
-int gemm_run(void* stream, int dtype, int ta, int tb, int M, int N, int K, const void* A, int lda, const void* Bm, int ldb,
-             void* C, int ldc, const float* bias, int act, void* aux, int ldaux, const void* resid, int ldr, int out_fp32,
-             int splitk, float p_drop, uint64_t seed, uint32_t rng_stream, int flags, const GemmExtra& ex) {
-    if (M == 0 || N == 0) return CMP_OK;
-    CMP_REQUIRE(K > 0, "gemm: K must be positive");
+// plan (gemm_plan.h), then launch: a refusal returns before anything is enqueued
+int gemm_run(void* stream, const GemmDesc& d, const GemmExtra& ex) {
     hipStream_t s = (hipStream_t)stream;
-    const int max_wgs = ex.max_wgs > 0 ? std::min(ex.max_wgs, 256) : 256;
-    float* const g_slab_ws = ex.slab_ws;
-    const size_t g_slab_bytes = ex.slab_ws ? ex.slab_bytes : 0;
-    const int g_gemm_role = ex.role;
-    std::unique_lock<std::mutex> sched_lock;         // held from the counter-set draw to the launch (process-wide table only)
-    SchedWs* sched_used = nullptr;
+    unsigned long long* const stamps = g_gemm_stamps;
+    const GemmPlan p = gemm_plan(d, ex, gemm_env(stamps != nullptr));
+    if (p.status != CMP_OK) {
+        cmp_set_error("%s", p.msg);
+        return p.status;
+    }
+    if (p.empty) return CMP_OK;
+    const bool tiled = p.family != CMP_GEMM_FAM_F32 && p.family != CMP_GEMM_FAM_GENERIC;
     Epilogue ep;
-    ep.bias = bias;
-    ep.act = act;
-    ep.aux = aux;
-    ep.ldaux = ldaux;
-    ep.resid = resid;
-    ep.ldr = ldr;
-    ep.out_fp32 = out_fp32;
-    ep.atomic = splitk > 1 ? 1 : 0;
-    ep.dbg_nostore = (flags & 64) ? 1 : 0;
-    ep.colsum = nullptr;
+    ep.bias = d.bias;
+    ep.act = d.act;
+    ep.aux = d.aux;
+    ep.ldaux = d.ldaux;
+    ep.resid = d.resid;
+    ep.ldr = d.ldr;
+    ep.out_fp32 = d.out_fp32;
+    ep.atomic = (d.splitk > 1 && !p.slabs) ? 1 : 0;
+    ep.dbg_nostore = (d.flags & CMP_GEMM_NOSTORE) ? 1 : 0;
+    ep.colsum = tiled ? ex.colsum : nullptr;     // (fused by the compile-time kinds only; the run-time epilogue ignores it)
+    ep.drop = make_drop(d.p_drop, d.seed, d.rng_stream);
     ep.sched = ep.sched_clear = nullptr;
     ep.ln = ex.ln;
     ep.rev = ex.rev ? 1 : 0;
-    ep.n_cols = N;
-
-    const int lnm = (ex.ln.in_part ? 1 : 0) | (ex.ln.out_part ? 2 : 0);
-    bool ln_done = lnm == 0;         // a launch that asks for a LayerNorm epilogue must reach a kernel that has one
-    float* colsum_out = ex.colsum;
-    if (colsum_out) CMP_REQUIRE(!out_fp32 && splitk <= 1, "gemm: column sums need a plain (non split-K) output in the compute dtype");
-    bool colsum_fused = false;
-    ep.drop = make_drop(p_drop, seed, rng_stream);
-    if (splitk > 1)
-        CMP_REQUIRE(out_fp32 && !bias && act == 0 && !resid && p_drop == 0.f,
-                    "gemm: split-K needs a plain fp32 accumulate epilogue");
-    CMP_REQUIRE(act == 0 || aux != nullptr || act == 1, "gemm: act=2 needs aux");
-    if (dtype == CMP_FP32) {
-        int nk = cdiv(K, F_BK);
-        splitk = std::max(1, std::min(splitk, nk));
-        int per = cdiv(nk, splitk);
-        dim3 grid(cdiv(N, F_BN), cdiv(M, F_BM), cdiv(nk, per));
-        int64_t sam = ta ? 1 : lda, sak = ta ? lda : 1;
-        int64_t sbk = tb ? 1 : ldb, sbn = tb ? ldb : 1;
-        gemm_f32_kernel<<<grid, 256, 0, s>>>(M, N, K, (const float*)A, sam, sak, (const float*)Bm, sbk, sbn, C, ldc, ep, per);
+    ep.n_cols = d.N;
+    std::unique_lock<std::mutex> sched_lock;         // held from the counter-set draw to the launch (process-wide table only)
+    SchedWs* sched_used = nullptr;
+    if (p.cls >= 0) PROF_START(p.cls, s);
+    if (p.sched) CHECK_SCHED(sched_next(s, ep, ex, sched_lock, &sched_used));
+    const GemmLaunch L{s, p, d, p.slabs ? (void*)ex.slab_ws : d.C, ep, p.slabs ? (int64_t)d.M * d.N : 0, stamps};
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+    if (p.family == CMP_GEMM_FAM_F32) {
+        const int64_t sam = d.ta ? 1 : d.lda, sak = d.ta ? d.lda : 1;
+        const int64_t sbk = d.tb ? 1 : d.ldb, sbn = d.tb ? d.ldb : 1;
+        gemm_f32_kernel<<<grid, p.block, 0, s>>>(d.M, d.N, d.K, (const float*)d.A, sam, sak, (const float*)d.B, sbk, sbn, d.C, d.ldc, ep, p.per);
     } else {
-        CMP_REQUIRE(lda % 8 == 0 && ldb % 8 == 0, "gemm(bf16): leading dimensions must be multiples of 8 (lda=%d ldb=%d)", lda, ldb);
-        CMP_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)Bm & 15) == 0, "gemm(bf16): operands must be 16-byte aligned");
-        int nk = cdiv(K, G_BK);
-        const int splitk_req = splitk;
-        splitk = std::max(1, std::min(splitk, nk));
-        int per = cdiv(nk, splitk);
-        dim3 grid(cdiv(N, G_BN), cdiv(M, G_BM), cdiv(nk, per));
-        size_t smem = 4 * G_IMG;
-        const bf16_t* a = (const bf16_t*)A;
-        const bf16_t* b = (const bf16_t*)Bm;
-        // timing class of cmp_prof_*: by role when the caller announced one (the model: 0 forward, 1 dgrad, 2 wgrad),
-        // otherwise by layout (the forward GEMMs read a transposed weight copy, i.e. the dgrad layout)
-        const int cls = g_gemm_role >= 0 ? g_gemm_role : (ta ? 2 : (tb ? 1 : 0));
-        // fast path: direct-to-LDS staging needs every 64-deep k-step of a K-contiguous operand inside its row
-        // (K % 64 == 0, or the caller vouches for zero padding up to a multiple of 64 with CMP_GEMM_KPAD_ZERO) and
-        // 32-bit byte offsets.
-        const bool kpad = (K % 64 == 0) || ((flags & 1) && (ta || lda >= (K + 63) / 64 * 64) && (!tb || ldb >= (K + 63) / 64 * 64));
-        const bool km_ok = (ta && !tb) || kpad;
-        const int64_t a_span = (int64_t)(ta ? K : M) * lda * 2, b_span = (int64_t)(tb ? N : K) * ldb * 2;
-        const bool fast = km_ok && a_span < 0x7FFFFFF0ll && b_span < 0x7FFFFFF0ll && ldc % 8 == 0 && (out_fp32 || N % 8 == 0) &&
-                          (!aux || (ldaux % 8 == 0 && N % 8 == 0)) && (!resid || (ldr % 8 == 0 && N % 8 == 0)) && !(flags & 2);
-        PROF_START(cls, s);
-        // 256x256 persistent tiles once they give most of the chip a tile (or a split-K launch sizes its own item count); the
-        // 128x128 kernel (2 workgroups per CU) below that: at the default config (E=256, B=1: M=1024) the 256-tile kernels ran 4-16
-        // workgroups on 256 CUs (27 us for a 4-tile launch)
-        const int64_t t256 = (int64_t)cdiv(M, 256) * cdiv(N, 256);
-        const bool big = fast && !(flags & 4) && ((flags & (8 | 16)) || ((int64_t)M * N >= 512ll * 512 && (t256 >= 192 || splitk_req > 1)));
-        // measured at the C2 shapes (tools/kbench.py): both-K-contiguous (dgrad) is fastest on the 2-stage BK=64 kernel
-        // (its DMA pieces are whole 128-byte lines); forward and wgrad on the 4-stage BK=32 deep pipeline.
-        const bool prefer_p4 = !(!ta && tb);
-        if ((big && !(flags & 8) && K % 32 == 0 && prefer_p4) || (big && (flags & 16))) {
-            // deep-pipeline kernels: split granularity is a 32-deep k-step.  cfg 1: 128x256 tiles, 2 workgroups per CU
-            // (one's epilogue/store drain overlaps the other's main loop); cfg 2: 256x256, 1 per CU.
-            const int nk32 = cdiv(K, P_BK);
-            const int want = std::max(1, std::min(splitk_req, nk32));
-            const int per32 = cdiv(nk32, want);
-            const int nsplit = cdiv(nk32, per32);
-            const int cfg = (flags & 32) ? 1 : 2;
-            // split-K: partial slabs + reduce when the registered workspace is large enough, else f32 atomics
-            const bool slabs = ep.atomic && nsplit > 1 && ldc == N && (N % 4 == 0) && g_slab_ws &&
-                               (size_t)nsplit * M * N * 4 <= g_slab_bytes && !(flags & 128);
-            CHECK_SCHED(sched_next(s, ep, ex, sched_lock, &sched_used));
-            Epilogue ep2 = ep;
-            if (slabs) ep2.atomic = 0;
-            const bool swap = !ep2.atomic;
-            void* Cdst = slabs ? (void*)g_slab_ws : C;
-            const int64_t sstride = slabs ? (int64_t)M * N : 0;
-            ep2.colsum = colsum_out;
-            if (!ta && !tb) colsum_fused = launch_p4<true, false>(s, cfg, swap, M, N, K, a, lda, b, ldb, Cdst, ldc, ep2, per32, nsplit, sstride, max_wgs);
-            else if (!ta && tb) colsum_fused = launch_p4<true, true>(s, cfg, swap, M, N, K, a, lda, b, ldb, Cdst, ldc, ep2, per32, nsplit, sstride, max_wgs);
-            else if (ta && !tb) colsum_fused = launch_p4<false, false>(s, cfg, swap, M, N, K, a, lda, b, ldb, Cdst, ldc, ep2, per32, nsplit, sstride, max_wgs);
-            else colsum_fused = launch_p4<false, true>(s, cfg, swap, M, N, K, a, lda, b, ldb, Cdst, ldc, ep2, per32, nsplit, sstride, max_wgs);
-            if (slabs) {
-                const int64_t n4 = (int64_t)M * N / 4;
-                gemm_slab_reduce_kernel<<<(int)std::min<int64_t>(cdiv64(n4, 256), 2048), 256, 0, s>>>(g_slab_ws, (float*)C, n4, n4, nsplit);
-            }
-        } else if (big) {
-            const int tiles_n = cdiv(N, H_BN), ntiles = tiles_n * cdiv(M, H_BM);
-            const int nsplit = cdiv(nk, per);
-            const int g1 = std::min(ntiles * nsplit, max_wgs);
-            const bool swap = !ep.atomic;
-            ep.colsum = colsum_out;
-            if (lnm == 1 && out_fp32) {
-                // ln_f into the tied-logits GEMM: fp32 output, the last tile column may be ragged (EPI_PLAIN32)
-                ln_done = !ta && tb && swap && act == 0 && !resid && !ep.drop.thr && M % 256 == 0 && nsplit == 1 && !colsum_out && bias && ex.ln.cs &&
-                          (ex.ln.np == 2 || ex.ln.np == 3) && K == 256 * ex.ln.np;
-            } else if (lnm == 1 && ex.ln.scale) {
-                // the backward pass's scale kinds: rows of 256 * np columns own the statistics, whatever N and K are
-                const int kind = (!ta && tb) ? epi_kind_of(ep, M, N, swap, false) : EPI_GENERIC;
-                ln_done = (ex.ln.np == 2 || ex.ln.np == 3) && nsplit == 1 && (kind == EPI_GELUGRAD || (kind == EPI_RESID && !colsum_out));
-            } else if (lnm) {
-                const int kind = (!ta && tb) ? epi_kind_of(ep, M, N, swap, false) : EPI_GENERIC;
-                const bool in_ok = !(lnm & 1) || (ex.ln.np >= 2 && ex.ln.np <= 3 && (kind == EPI_RESID ? (ex.ln.gamma && ex.ln.beta && N == 256 * ex.ln.np)
-                                                                                                     : (ex.ln.cs && bias && K == 256 * ex.ln.np)));
-                const bool kind_ok = (lnm == 1 && (kind == EPI_PLAIN || kind == EPI_GELU_AUX)) || ((lnm & 2) && kind == EPI_RESID);
-                ln_done = kind_ok && in_ok && nsplit == 1 && !colsum_out;
-            }
-            if (!ln_done) {
-                cmp_set_error("gemm: this launch cannot carry the LayerNorm epilogue that was asked for (M=%d N=%d K=%d ta=%d tb=%d act=%d): "
-                              "bf16, A[M,K] . W^T[N,K], whole 256x256 tiles, 2 or 3 segments of 256 columns", M, N, K, ta, tb, act);
-                return CMP_ERR_INVALID;
-            }
-            CHECK_SCHED(sched_next(s, ep, ex, sched_lock, &sched_used));
-            if (!ta && !tb) colsum_fused = launch_256<true, false>(s, g1, swap, M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, tiles_n, ntiles);
-            else if (!ta && tb) colsum_fused = launch_256<true, true>(s, g1, swap, M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, tiles_n, ntiles);
-            else if (ta && !tb) colsum_fused = launch_256<false, false>(s, g1, swap, M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, tiles_n, ntiles);
-            else colsum_fused = launch_256<false, true>(s, g1, swap, M, N, K, a, lda, b, ldb, C, ldc, ep, per, nsplit, tiles_n, ntiles);
-        } else if (fast) {
-            const int tiles_n = cdiv(N, G_BN), ntiles = tiles_n * cdiv(M, G_BM);
-            dim3 g1(ntiles, cdiv(nk, per));
-            const bool swap = !ep.atomic;
-            ep.colsum = colsum_out;           // (fused by the compile-time kinds only; the run-time epilogue ignores it)
-            if (!ta && !tb) launch_fast<true, false>(s, g1, smem, swap, M, N, K, a, lda, b, ldb, C, ldc, ep, per, tiles_n, ntiles);
-            else if (!ta && tb) colsum_fused = launch_fast<true, true>(s, g1, smem, swap, M, N, K, a, lda, b, ldb, C, ldc, ep, per, tiles_n, ntiles);
-            else if (ta && !tb) launch_fast<false, false>(s, g1, smem, swap, M, N, K, a, lda, b, ldb, C, ldc, ep, per, tiles_n, ntiles);
-            else launch_fast<false, true>(s, g1, smem, swap, M, N, K, a, lda, b, ldb, C, ldc, ep, per, tiles_n, ntiles);
-        } else
-        // A_KM = !ta ; B_KM = tb
-        if (!ta && !tb) gemm_bf16_kernel<true, false><<<grid, 256, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per);
-        else if (!ta && tb) gemm_bf16_kernel<true, true><<<grid, 256, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per);
-        else if (ta && !tb) gemm_bf16_kernel<false, false><<<grid, 256, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per);
-        else gemm_bf16_kernel<false, true><<<grid, 256, smem, s>>>(M, N, K, a, lda, b, ldb, C, ldc, ep, per);
-        {   // algorithmic HBM bytes: A, B (+ bias, gelu' operand, residual) in; C (+ the stored pre-activation) out, once each
-            const double oe = out_fp32 ? 4.0 : 2.0;
-            const double gb = 2.0 * ((double)M * K + (double)K * N) + oe * M * N + (bias ? 4.0 * N : 0.0) + (aux ? 2.0 * M * N : 0.0) +
-                              (resid ? 2.0 * M * N : 0.0);
-            PROF_STOP(cls, s, 2.0 * M * N * K, gb);
+#define LAYOUT(...) with_layout(p.a_km, p.b_km, [&](auto a_km, auto b_km) { constexpr bool A_KM = decltype(a_km)::value, B_KM = decltype(b_km)::value; __VA_ARGS__; })
+        switch (p.family) {
+            case CMP_GEMM_FAM_P4_128: LAYOUT(launch_p4_cfg<A_KM, B_KM, 1, 3>(L)); break;
+            case CMP_GEMM_FAM_P4_256: LAYOUT(launch_p4_cfg<A_KM, B_KM, 2, 4>(L)); break;
+            case CMP_GEMM_FAM_TILE256: LAYOUT(launch_256<A_KM, B_KM>(L)); break;
+            case CMP_GEMM_FAM_TILE128:
+            case CMP_GEMM_FAM_RING: LAYOUT(launch_fast<A_KM, B_KM>(L)); break;
+            default:
+                LAYOUT(gemm_bf16_kernel<A_KM, B_KM><<<grid, p.block, p.smem, s>>>(d.M, d.N, d.K, (const bf16_t*)d.A, d.lda, (const bf16_t*)d.B, d.ldb, d.C,
+                                                                                   d.ldc, ep, p.per));
         }
+#undef LAYOUT
+        if (p.slabs) {   // C[i] += the slabs, in a fixed order
+            const int64_t n4 = (int64_t)d.M * d.N / 4;
+            gemm_slab_reduce_kernel<<<p.reduce_grid, 256, 0, s>>>(ex.slab_ws, (float*)d.C, n4, n4, p.nsplit);
+        }
+        // algorithmic HBM bytes: A, B (+ bias, gelu' operand, residual) in; C (+ the stored pre-activation) out, once each
+        const double mn = (double)d.M * d.N;
+        const double gb = 2.0 * ((double)d.M * d.K + (double)d.K * d.N) + (d.out_fp32 ? 4.0 : 2.0) * mn + (d.bias ? 4.0 * d.N : 0.0) +
+                          (d.aux ? 2.0 * mn : 0.0) + (d.resid ? 2.0 * mn : 0.0);
+        PROF_STOP(p.cls, s, 2.0 * mn * d.K, gb);
     }
     {
         const hipError_t le = hipGetLastError();
@@ -2618,7 +2540,6 @@ int gemm_run(void* stream, int dtype, int ta, int tb, int M, int N, int K, const
         }
     }
     if (sched_lock.owns_lock()) sched_lock.unlock();
-    CMP_REQUIRE(ln_done, "gemm: a LayerNorm epilogue was asked of a launch that went to a kernel without one (M=%d N=%d K=%d dtype=%d flags=%d)", M, N, K, dtype, flags);
-    if (colsum_out && !colsum_fused) return cmp_k_colsum(stream, C, ldc, colsum_out, M, N, dtype);
+    if (p.colsum_pass) return cmp_k_colsum(stream, d.C, d.ldc, ex.colsum, d.M, d.N, d.dtype);
     return CMP_OK;
 }

@@ -722,7 +722,7 @@ static bool ln_fused_ok(const cmp_model* m, int M, int past_len, bool training) 
     if (training && m->ln_fused_mode != 2 && m->ln_fused_mode != 3) return false;
     if (!m->cfg.use_layer_norm || m->dtype != CMP_BF16 || m->slab || past_len) return false;
     if (m->Ea != m->E || m->E % 256 || m->E < 512 || m->E > 768 || !m->act[0].ln1_part) return false;   // 2 or 3 segments (the fold images' LDS)
-    if (M % 256 || (int64_t)(M / 256) * (m->E / 256) < 192) return false;      // gemm_run's `big`: the N = E GEMMs too
+    if (M % 256 || (int64_t)(M / 256) * (m->E / 256) < GEMM_BIG_MIN_TILES) return false;      // gemm_plan's `big`: the N = E GEMMs too
     if (m->fwd_pos_ids || m->fwd_type_ids || m->fwd_amask || m->fwd_probs_out) return false;
     return true;
 }
@@ -746,24 +746,52 @@ static int ln_bwd(cmp_model* m, const void* dy, const void* x, const float* gamm
                              dmask, colsum, p_drop, m->drop_seed(), rng_stream, m->slab != nullptr, fz, m->fused_last, prescaled);
 }
 
-#define GEMM_REV (1 << 20)      // gemm() flag (model.hip only): GemmExtra::rev
-static int gemm(cmp_model* m, int ta, int tb, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C,
-                int ldc, const float* bias, int act, void* aux, int ldaux, const void* resid, int ldr, int out_fp32,
-                int splitk, float p_drop, uint32_t rng_stream, int flags = 0, float* colsum = nullptr, const LnEpi* ln = nullptr) {
+// The GEMM launches of the model as launch records (gemm_plan.h: GemmDesc); the dtype and the dropout seed are the model's.
+// y[M,N] = x[M,K] . W (+ bias): W as its transposed copy / against the stored weight of a dgrad [N,K] (tb = 1), or as stored [K,N]
+static GemmDesc xw(int tb, int M, int N, int K, const void* x, const void* W, void* y, const float* bias = nullptr) {
+    GemmDesc d;
+    d.tb = tb; d.M = M; d.N = N; d.K = K;
+    d.A = x; d.lda = K;
+    d.B = W; d.ldb = tb ? K : N;
+    d.C = y; d.ldc = N;
+    d.bias = bias;
+    return d;
+}
+// dW[Mw,Nw] (fp32, accumulated into) += A^T . B over the M tokens, A stored [M,Mw], B stored [M,Nw]: split-K
+static GemmDesc wgrad_desc(int Mw, int Nw, int M, const void* A, int lda, const void* B, int ldb, float* dW, int splitk) {
+    GemmDesc d;
+    d.ta = 1; d.M = Mw; d.N = Nw; d.K = M;
+    d.A = A; d.lda = lda;
+    d.B = B; d.ldb = ldb;
+    d.C = dW; d.ldc = Nw;
+    d.out_fp32 = 1; d.splitk = splitk;
+    return d;
+}
+// epilogues: aux [M,N] = the pre-activation, y = gelu(aux); y *= gelu'(aux); y = dropout(y) + resid [M,N]; fp32 y with its own stride
+static GemmDesc with_gelu(GemmDesc d, void* aux) { d.act = 1; d.aux = aux; d.ldaux = d.N; return d; }
+static GemmDesc with_gelu_grad(GemmDesc d, void* aux) { d.act = 2; d.aux = aux; d.ldaux = d.N; return d; }
+static GemmDesc with_resid(GemmDesc d, const void* resid, float p_drop = 0.f, uint32_t rng_stream = 0) {
+    d.resid = resid; d.ldr = d.N; d.p_drop = p_drop; d.rng_stream = rng_stream;
+    return d;
+}
+static GemmDesc f32_out(GemmDesc d, int ldc) { d.out_fp32 = 1; d.ldc = ldc; return d; }
+static GemmDesc with_flags(GemmDesc d, int flags) { d.flags = flags; return d; }
+// adds the model's context: deterministic slabs, role, max_wgs, dp, sched, and the deterministic column-sum pass
+static int gemm(cmp_model* m, GemmDesc d, float* colsum = nullptr, const LnEpi* ln = nullptr, bool rev = false) {
     const bool det = m->slab != nullptr;                               // COMPOSER_DETERMINISTIC=1
+    d.dtype = m->dtype;
+    d.seed = m->drop_seed();
     GemmExtra ex;
     if (ln) ex.ln = *ln;
-    ex.rev = (flags & GEMM_REV) != 0;
-    flags &= ~GEMM_REV;
+    ex.rev = rev;
     ex.colsum = det ? nullptr : colsum;                                // fused column sums are float atomics
-    if (splitk > 1 && det) { ex.slab_ws = (float*)m->slab; ex.slab_bytes = (size_t)m->slab_bytes; }
-    ex.role = m->gemm_role >= 0 ? m->gemm_role : (ta ? 2 : 1);         // forward announces 0; backward: A^T = wgrad, else dgrad
+    if (d.splitk > 1 && det) { ex.slab_ws = (float*)m->slab; ex.slab_bytes = (size_t)m->slab_bytes; }
+    ex.role = m->gemm_role >= 0 ? m->gemm_role : (d.ta ? 2 : 1);       // forward announces 0; backward: A^T = wgrad, else dgrad
     ex.max_wgs = m->ctx->dp_on() ? m->ctx->gemm_max_wgs : 0;              // leave CUs to the concurrent all-reduce kernels
     ex.dp = m->ctx->dp_on();                                   // RCCL kernels may hold CUs: dynamic item scheduling
     ex.sched = &m->ctx->gemm_sched;
-    CHECK_RC(gemm_run(m->ctx->stream, m->dtype, ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, act, aux, ldaux, resid, ldr,
-                      out_fp32, splitk, p_drop, m->drop_seed(), rng_stream, flags, ex));
-    if (det && colsum) CHECK_RC(colsum_det(m, C, ldc, colsum, M, N));
+    CHECK_RC(gemm_run(m->ctx->stream, d, ex));
+    if (det && colsum) CHECK_RC(colsum_det(m, d.C, d.ldc, colsum, d.M, d.N));
     return CMP_OK;
 }
 
@@ -827,7 +855,7 @@ int model_forward(cmp_model* m, const int32_t* x_dev, int B, int T, bool trainin
     // wrote walks every XCD's run of tiles the other way round, so it starts on the rows still in that XCD's L2 (C2 inference
     // forward 7.22 -> 7.18 ms; COMPOSER_GEMM_ALT=0: all forwards)
     static const int alt_mode = [] { const char* e = getenv("COMPOSER_GEMM_ALT"); return e ? atoi(e) : 1; }();
-    const int RV[4] = {alt_mode == 2 ? GEMM_REV : 0, alt_mode == 1 ? GEMM_REV : 0, alt_mode == 2 ? GEMM_REV : 0, alt_mode == 1 ? GEMM_REV : 0};
+    const bool RV[4] = {alt_mode == 2, alt_mode == 1, alt_mode == 2, alt_mode == 1};
     // timing class 9: the decoder-block stack of this pass as one span (bench.py `forward.*.blocks_only_ms`: the attention + FFN
     // forward north_star prices, without embedding, ln_f, logits, loss and the host side of the call)
     PROF_START(9, s);
@@ -838,25 +866,24 @@ int model_forward(cmp_model* m, const int32_t* x_dev, int B, int T, bool trainin
         const float* fold = m->lnfold + i * m->fold_stride;
         LnEpi l;
         l.in_part = a.ln1_part; l.np = E / 256; l.eps = m->cfg.ln_eps; l.cs = fold;
-        CHECK_RC(gemm(m, 0, 1, M, 3 * E, E, m->xs[i], E, W(o.attn_w), E, a.qkv, 3 * E, fold + 3 * E, 0, nullptr, 0, nullptr, 0, 0, 1, 0.f,
-                      0, RV[0], nullptr, &l));                                        // qkv = ln_1(x).Wattn + b   :583-584, 417
+        CHECK_RC(gemm(m, xw(1, M, 3 * E, E, m->xs[i], W(o.attn_w), a.qkv, fold + 3 * E), nullptr, &l, RV[0]));   // qkv = ln_1(x).Wattn + b   :583-584, 417
         CHECK_RC(attn_fwd_run(s, a.qkv, a.att, a.lse, B, Tt, m->H, m->D, attn_scale(m), dt, pa, m->drop_seed(), drop_stream(step, i, 1),
                               nullptr));
         l = LnEpi();
         l.in_part = a.ln1_part; l.np = E / 256; l.eps = m->cfg.ln_eps; l.gamma = m->P + o.ln1_g; l.beta = m->P + o.ln1_b;
         l.out_part = a.ln2_part;
-        CHECK_RC(gemm(m, 0, 1, M, E, E, a.att, E, W(o.proj_w), E, a.r, E, m->P + o.proj_b, 0, nullptr, 0, m->xs[i], E, 0, 1, pr,
-                      drop_stream(step, i, 2), RV[1], nullptr, &l));                  // r = ln_1(x) + dropout(proj)  :587
+        CHECK_RC(gemm(m, with_resid(xw(1, M, E, E, a.att, W(o.proj_w), a.r, m->P + o.proj_b), m->xs[i], pr, drop_stream(step, i, 2)),
+                      nullptr, &l, RV[1]));                                           // r = ln_1(x) + dropout(proj)  :587
         l = LnEpi();
         l.in_part = a.ln2_part; l.np = E / 256; l.eps = m->cfg.ln_eps; l.cs = fold + 6 * E;
-        CHECK_RC(gemm(m, 0, 1, M, 4 * E, E, a.r, E, W(o.fc_w), E, a.g, 4 * E, fold + 10 * E, 1, training ? a.fc : nullptr, 4 * E, nullptr,
-                      0, 0, 1, 0.f, 0, RV[2], nullptr, &l));                          // g = gelu(ln_2(r).Wfc + b)    :591, 504
+        CHECK_RC(gemm(m, with_gelu(xw(1, M, 4 * E, E, a.r, W(o.fc_w), a.g, fold + 10 * E), training ? a.fc : nullptr),
+                      nullptr, &l, RV[2]));                                           // g = gelu(ln_2(r).Wfc + b)    :591, 504
         l = LnEpi();
         // (the last block's statistics feed ln_f, folded into the logits GEMM on inference passes; a training pass keeps the ln_f
         //  kernel: its output hf is an operand of the tied weight gradient)
         l.out_part = i + 1 < m->L ? m->act[i + 1].ln1_part : (training ? nullptr : m->lnf_part);
-        CHECK_RC(gemm(m, 0, 1, M, E, 4 * E, a.g, 4 * E, W(o.pr_w), 4 * E, m->xs[i + 1], E, m->P + o.pr_b, 0, nullptr, 0, a.r, E, 0, 1, pr,
-                      drop_stream(step, i, 3), RV[3], nullptr, l.out_part ? &l : nullptr));   // x = r + dropout(mlp)  :594
+        CHECK_RC(gemm(m, with_resid(xw(1, M, E, 4 * E, a.g, W(o.pr_w), m->xs[i + 1], m->P + o.pr_b), a.r, pr, drop_stream(step, i, 3)),
+                      nullptr, l.out_part ? &l : nullptr, RV[3]));                    // x = r + dropout(mlp)  :594
     }
     for (int i = 0; !fused && i < m->L; i++) {
         const LayerOff& o = m->lo[i];
@@ -864,8 +891,7 @@ int model_forward(cmp_model* m, const int32_t* x_dev, int B, int T, bool trainin
         if (ln)   // transformer.py:583-584 -- the LN output REPLACES the residual stream
             CHECK_RC(cmp_k_layernorm_fwd(s, m->xs[i], m->P + o.ln1_g, m->P + o.ln1_b, a.u, a.ln1_mean, a.ln1_rstd, M, E,
                                          m->cfg.ln_eps, dt));
-        CHECK_RC(gemm(m, 0, wt, M, 3 * Ea, E, a.u, E, W(o.attn_w), wt ? E : 3 * Ea, Tp ? m->dqkv : a.qkv, 3 * Ea, m->P + o.attn_b, 0,
-                      nullptr, 0, nullptr, 0, 0, 1, 0.f, 0));
+        CHECK_RC(gemm(m, xw(wt, M, 3 * Ea, E, a.u, W(o.attn_w), Tp ? m->dqkv : a.qkv, m->P + o.attn_b)));
         if (Tp) CHECK_RC(rows_copy(m, m->dqkv, a.qkv, B, T, 3 * Ea, T, 0, 3 * Ea, Tt, Tp, 3 * Ea));  // concat([past, new]) :423-426
         CHECK_RC(attn_fwd_run(s, a.qkv, a.att, a.lse, B, Tt, m->H, m->D, attn_scale(m), dt, pa, m->drop_seed(),
                               drop_stream(step, i, 1), m->fwd_amask));
@@ -877,16 +903,15 @@ int model_forward(cmp_model* m, const int32_t* x_dev, int B, int T, bool trainin
         }
         const void* att = a.att;
         if (Tp) { CHECK_RC(rows_copy(m, a.att, m->tmpE, B, T, Ea, Tt, Tp, Ea, T, 0, Ea)); att = m->tmpE; }
-        CHECK_RC(gemm(m, 0, wt, M, E, Ea, att, Ea, W(o.proj_w), wt ? Ea : E, a.r, E, m->P + o.proj_b, 0, nullptr, 0, a.u, E, 0, 1, pr,
-                      drop_stream(step, i, 2)));                                   // r = u + dropout(proj)  :587
+        CHECK_RC(gemm(m, with_resid(xw(wt, M, E, Ea, att, W(o.proj_w), a.r, m->P + o.proj_b), a.u, pr,
+                                    drop_stream(step, i, 2))));                    // r = u + dropout(proj)  :587
         if (ln)
             CHECK_RC(cmp_k_layernorm_fwd(s, a.r, m->P + o.ln2_g, m->P + o.ln2_b, a.n, a.ln2_mean, a.ln2_rstd, M, E,
                                          m->cfg.ln_eps, dt));
         // the pre-activation (a.fc) is only needed by the backward pass
-        CHECK_RC(gemm(m, 0, wt, M, 4 * E, E, a.n, E, W(o.fc_w), wt ? E : 4 * E, a.g, 4 * E, m->P + o.fc_b, 1, training ? a.fc : nullptr,
-                      4 * E, nullptr, 0, 0, 1, 0.f, 0));                                              // g = gelu(fc)           :504
-        CHECK_RC(gemm(m, 0, wt, M, E, 4 * E, a.g, 4 * E, W(o.pr_w), wt ? 4 * E : E, m->xs[i + 1], E, m->P + o.pr_b, 0, nullptr, 0, a.r, E,
-                      0, 1, pr, drop_stream(step, i, 3)));                         // x = r + dropout(mlp)   :594
+        CHECK_RC(gemm(m, with_gelu(xw(wt, M, 4 * E, E, a.n, W(o.fc_w), a.g, m->P + o.fc_b), training ? a.fc : nullptr)));   // g = gelu(fc)           :504
+        CHECK_RC(gemm(m, with_resid(xw(wt, M, E, 4 * E, a.g, W(o.pr_w), m->xs[i + 1], m->P + o.pr_b), a.r, pr,
+                                    drop_stream(step, i, 3))));                    // x = r + dropout(mlp)   :594
     }
     PROF_STOP(9, s, (double)M * m->L * (24.0 * E * E + 2.0 * E * Tt), 0.0);        // (causal attention on the unmasked half)
     static const bool lnf_fold_on = [] { const char* e = getenv("COMPOSER_LNF_FOLD"); return !(e && e[0] == '0'); }();
@@ -898,15 +923,14 @@ int model_forward(cmp_model* m, const int32_t* x_dev, int B, int T, bool trainin
         m->hf_valid = false;
         // (CMP_GEMM_TILE256: the fold epilogue exists on the persistent 256x256 kernel only, and [M, V] has fewer tiles than the
         //  blocks' [M, E] launches that ln_fused_ok sized the path by -- E = 768, V = 390 at 16 384 tokens: 192 against 128)
-        CHECK_RC(gemm(m, 0, 1, M, m->V, E, m->xs[m->L], E, m->wte_lnf, E, m->logits, m->ldz, m->lnf_fold + m->lnf_npad, 0, nullptr, 0, nullptr,
-                      0, 1, 1, 0.f, 0, CMP_GEMM_TILE256, nullptr, &l));
+        CHECK_RC(gemm(m, with_flags(f32_out(xw(1, M, m->V, E, m->xs[m->L], m->wte_lnf, m->logits, m->lnf_fold + m->lnf_npad), m->ldz),
+                                    CMP_GEMM_TILE256), nullptr, &l));
         return CMP_OK;
     }
     CHECK_RC(cmp_k_layernorm_fwd(s, m->xs[m->L], m->P + m->off_lnf_g, m->P + m->off_lnf_b, m->hf, m->lnf_mean, m->lnf_rstd, M,
                                  E, m->cfg.ln_eps, dt));                           // :811 (always applied)
     m->hf_valid = true;
-    CHECK_RC(gemm(m, 0, 1, M, m->V, E, m->hf, E, m->w(m->off_wte), E, m->logits, m->ldz, nullptr, 0, nullptr, 0, nullptr, 0, 1,
-                  1, 0.f, 0));                                                     // tied logits            :818
+    CHECK_RC(gemm(m, f32_out(xw(1, M, m->V, E, m->hf, m->w(m->off_wte), m->logits), m->ldz)));   // tied logits            :818
     return CMP_OK;
 }
 
@@ -985,11 +1009,11 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
         const bool p4 = dt == CMP_BF16 && t256 <= 64 && M >= 65536 && M % 32 == 0;       // (at 32 768 tokens the two forms tie)
         const int tsplit = p4 ? std::max(2, std::min(256 / t256, M / 1024)) : std::max(2, wgrad_splits(M, V, E));
         const int tflags = p4 ? CMP_GEMM_P4 : 0;
-        CHECK_RC(gemm(m, 1, 0, V, E, M, m->dlogits, m->ldz, m->hf, E, m->G + m->off_wte, E, nullptr, 0, nullptr, 0, nullptr, 0, 1,
-                      tsplit, 0.f, 0, tflags));
+        CHECK_RC(gemm(m, with_flags(wgrad_desc(V, E, M, m->dlogits, m->ldz, m->hf, E, m->G + m->off_wte, tsplit), tflags)));
     }
-    CHECK_RC(gemm(m, 0, 0, M, E, V, m->dlogits, m->ldz, m->w(m->off_wte), E, m->tmpE, E, nullptr, 0, nullptr, 0, nullptr, 0, 0,
-                  1, 0.f, 0, CMP_GEMM_KPAD_ZERO));    // dlogits rows are zero-padded to ldz (softmax_xent kernel)
+    GemmDesc dhf = with_flags(xw(0, M, E, V, m->dlogits, m->w(m->off_wte), m->tmpE), CMP_GEMM_KPAD_ZERO);
+    dhf.lda = m->ldz;                                 // dlogits rows are zero-padded to ldz (softmax_xent kernel)
+    CHECK_RC(gemm(m, dhf));
     // dx of every LayerNorm backward below is the gradient of the previous residual branch's dropout output, so the
     // kernel also emits that branch's masked gradient (dmask) and bias gradient (column sums)
     CHECK_RC(ln_bwd(m, m->tmpE, m->xs[m->L], m->P + m->off_lnf_g, m->lnf_mean, m->lnf_rstd, nullptr, m->dx,
@@ -1038,26 +1062,24 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
         LnBwdFused fz;
         fz.np = E / 256; fz.eps = m->cfg.ln_eps;
         auto wgrad = [&](int Mw, int Nw, const void* A, int lda, const void* Bm, int ldb, float* Cw) {
-            return gemm(m, 1, 0, Mw, Nw, M, A, lda, Bm, ldb, Cw, Nw, nullptr, 0, nullptr, 0, nullptr, 0, 1, std::max(2, wgrad_splits(M, Mw, Nw)), 0.f, 0);
+            return gemm(m, wgrad_desc(Mw, Nw, M, A, lda, Bm, ldb, Cw, std::max(2, wgrad_splits(M, Mw, Nw))));
         };
         if (!group_now) CHECK_RC(wgrad(4 * E, E, a.g, 4 * E, dmo, E, m->G + o.pr_w));
         if (!dmo_ready) CHECK_RC(colsum_any(m, dmo, E, m->G + o.pr_b, M, E));
         LnEpi ls;
         ls.np = E / 256; ls.eps = m->cfg.ln_eps; ls.scale = 1;
         ls.in_part = a.ln2_part;
-        CHECK_RC(gemm(m, 0, 1, M, 4 * E, E, dmo, E, m->w(o.pr_w), E, m->dfc, 4 * E, nullptr, 2, a.fc, 4 * E, nullptr, 0, 0, 1,
-                      0.f, 0, 0, m->G + o.fc_b, raw ? &ls : nullptr));      // dfc = (dmo.Wpr^T) * gelu'(fc) [raw: rstd_2 o that]; b_fc grad = column sums of dfc
+        CHECK_RC(gemm(m, with_gelu_grad(xw(1, M, 4 * E, E, dmo, m->w(o.pr_w), m->dfc), a.fc), m->G + o.fc_b,
+                      raw ? &ls : nullptr));                                // dfc = (dmo.Wpr^T) * gelu'(fc) [raw: rstd_2 o that]; b_fc grad = column sums of dfc
         if (!group_now) CHECK_RC(wgrad(E, 4 * E, a.n, E, m->dfc, 4 * E, m->G + o.fc_w));
         void* const dao_mask = group_now ? m->dmask2 : m->dmask;
         if (ln) {
-            CHECK_RC(gemm(m, 0, 1, M, E, 4 * E, m->dfc, 4 * E, m->w(o.fc_w), 4 * E, m->tmpE, E, nullptr, 0, nullptr, 0, nullptr,
-                          0, 0, 1, 0.f, 0));                                       // dn
+            CHECK_RC(gemm(m, xw(1, M, E, 4 * E, m->dfc, m->w(o.fc_w), m->tmpE)));   // dn
             fz.part = a.ln2_part; fz.beta = m->P + o.ln2_b; fz.yout = a.n;
             CHECK_RC(ln_bwd(m, m->tmpE, a.r, m->P + o.ln2_g, a.ln2_mean, a.ln2_rstd, m->dx, m->dr, m->G + o.ln2_g, m->G + o.ln2_b, M,
                             dao_mask, m->G + o.proj_b, pr, drop_stream(step, i, 2), (fused && !raw) ? &fz : nullptr, raw));   // dr = dx + LN2'(dn); dao, b_proj grad
         } else {
-            CHECK_RC(gemm(m, 0, 1, M, E, 4 * E, m->dfc, 4 * E, m->w(o.fc_w), 4 * E, m->dr, E, nullptr, 0, nullptr, 0, m->dx, E,
-                          0, 1, 0.f, 0));                                          // dr = dx + dn
+            CHECK_RC(gemm(m, with_resid(xw(1, M, E, 4 * E, m->dfc, m->w(o.fc_w), m->dr), m->dx)));   // dr = dx + dn
         }
         // ---- attention: r = u + dropout(att.Wproj+b)
         const void* dao = m->dr;
@@ -1069,8 +1091,7 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
         }
         if (!group_now) CHECK_RC(wgrad(Ea, E, a.att, Ea, dao, E, m->G + o.proj_w));
         if (!ln) CHECK_RC(colsum_any(m, dao, E, m->G + o.proj_b, M, E));
-        CHECK_RC(gemm(m, 0, 1, M, Ea, E, dao, E, m->w(o.proj_w), E, m->tmpE, Ea, nullptr, 0, nullptr, 0, nullptr, 0, 0, 1, 0.f,
-                      0));                                                         // datt
+        CHECK_RC(gemm(m, xw(1, M, Ea, E, dao, m->w(o.proj_w), m->tmpE)));          // datt
         const bool det = m->slab != nullptr;     // the fused bias sums are float atomics: a separate fixed-order pass instead
         AttnLnRows alr;
         if (raw) alr.rstd = a.ln1_rstd;
@@ -1110,8 +1131,8 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
         }
         if (ln) {
             ls.in_part = a.ln1_part;
-            CHECK_RC(gemm(m, 0, 1, M, E, 3 * Ea, m->dqkv, 3 * Ea, m->w(o.attn_w), 3 * Ea, m->tmpE, E, nullptr, 0, nullptr, 0, m->dr,
-                          E, 0, 1, 0.f, 0, 0, nullptr, raw ? &ls : nullptr));      // du = dr + dqkv.Wattn^T  [raw: rstd_1 o du]
+            CHECK_RC(gemm(m, with_resid(xw(1, M, E, 3 * Ea, m->dqkv, m->w(o.attn_w), m->tmpE), m->dr), nullptr,
+                          raw ? &ls : nullptr));                                   // du = dr + dqkv.Wattn^T  [raw: rstd_1 o du]
             // dx_in = LN1'(du): no skip connection around LN1; feeds layer i-1's MLP branch (or the embedding for i = 0)
             fz.part = a.ln1_part; fz.beta = m->P + o.ln1_b; fz.yout = a.u;
             void* const next_mask = fused ? dmk[cur ^ 1] : m->dmask;
@@ -1125,8 +1146,7 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
             dmo_ready = true;
         } else {
             dmo_ready = false;
-            CHECK_RC(gemm(m, 0, 1, M, E, 3 * Ea, m->dqkv, 3 * Ea, m->w(o.attn_w), 3 * Ea, m->dx, E, nullptr, 0, nullptr, 0, m->dr, E,
-                          0, 1, 0.f, 0));
+            CHECK_RC(gemm(m, with_resid(xw(1, M, E, 3 * Ea, m->dqkv, m->w(o.attn_w), m->dx), m->dr)));
         }
         if (allreduce) CHECK_RC(bucket_ready(m, i, o.begin, o.end, lr, update));
     }

@@ -465,6 +465,8 @@ int cmp_k_gemm(void* stream, int dtype, int ta, int tb, int M, int N, int K,
 #define CMP_GEMM_TILE256 8      /* tests/bench: force the persistent 256x256 2-stage kernel */
 #define CMP_GEMM_P4 16          /* tests/bench: force the persistent deep-pipeline (BK=32) kernel */
 #define CMP_GEMM_P4_128 32      /* with CMP_GEMM_P4: 128x256 tile / 4 waves / 3 stages / 2 workgroups per CU instead of 256x256 / 8 waves / 4 stages */
+#define CMP_GEMM_NOSTORE 64     /* timing experiment only: run the whole epilogue but skip the global stores */
+#define CMP_GEMM_ATOMICS 128    /* split-K: f32 atomics even where the registered slab workspace would do (cmp_gemm_set_workspace) */
 /* ONE launch for up to 8 split-K weight gradients that contract over the same K rows -- the four Conv1D weight gradients of a
  * decoder block (tf.GradientTape through transformer.py:205-209) contract over the tokens: C_i[M_i, N_i] (fp32, ACCUMULATED into
  * with f32 atomics) += A_i^T . B_i, A_i bf16 stored [K, M_i] (lda_i), B_i bf16 stored [K, N_i] (ldb_i).  Requirements
@@ -526,7 +528,7 @@ int cmp_k_layernorm_bwd_parts(void* stream, const void* dy, const void* x, const
 int cmp_model_path_info(cmp_model* m, int* fused, int64_t* wgrad_table_builds);
 /* Registers a device workspace for split-K reductions: with it, split-K launches write per-split fp32 partial tiles and
  * fold them in a fixed order (reproducible, no float atomics); without it (or if too small: splitk*M*N*4 bytes) they
- * accumulate with f32 atomics.  flags & 128 forces the atomic path. */
+ * accumulate with f32 atomics.  CMP_GEMM_ATOMICS forces the atomic path. */
 int cmp_gemm_set_workspace(void* ws_dev, int64_t bytes);
 /* One-shot: the next cmp_k_gemm (plain output in the compute dtype) also adds the column sums of its output to
  * out[0..N) -- the bias gradient that goes with an input-gradient GEMM (transformer.py:916-920 via tf.GradientTape).
@@ -535,6 +537,40 @@ int cmp_gemm_colsum_next(float* out);
 /* diagnostic only: a device buffer of 500 uint64 receives (id, s_memtime) pairs from one workgroup of the next
  * deep-pipeline GEMM launches (tools/gemm_timeline.py); pass NULL to switch it off. */
 int cmp_gemm_set_stamps(void* dev_buf);
+/* Host-only window on the launcher's decision (CPU tests): the plan of the launch that cmp_k_gemm would make of the same
+ * arguments.  Consumes the calling thread's armed one-shot state (cmp_gemm_colsum_next, cmp_gemm_ln_next,
+ * cmp_gemm_ln_scale_next; reads cmp_gemm_set_workspace) exactly as the next cmp_k_gemm would, dereferences nothing and calls
+ * no HIP function: it works without a device, operand pointers may be any non-null 16-byte-aligned value.  A launch cmp_k_gemm
+ * would refuse returns the same status and sets the same cmp_last_error() text. */
+enum {
+    CMP_GEMM_FAM_F32 = 0,        /* fp32 parity kernel, 64x64x16 */
+    CMP_GEMM_FAM_GENERIC = 1,    /* bf16, register-staged: any shape */
+    CMP_GEMM_FAM_TILE128 = 2,    /* bf16 128x128 direct-to-LDS, two stages */
+    CMP_GEMM_FAM_RING = 3,       /* ... its four-stage ring (at most 256 tiles, whole k-steps, a compile-time epilogue kind) */
+    CMP_GEMM_FAM_TILE256 = 4,    /* bf16 persistent 256x256, two stages of 64 */
+    CMP_GEMM_FAM_P4_256 = 5,     /* bf16 persistent deep pipeline (k-steps of 32), 256x256 */
+    CMP_GEMM_FAM_P4_128 = 6      /* ... 128x256, two workgroups per CU */
+};
+typedef struct cmp_gemm_plan_info {
+    int32_t family;              /* CMP_GEMM_FAM_* */
+    int32_t a_km, b_km;          /* A / B stored K-contiguous (ta == 0 / tb == 1) */
+    int32_t swap;                /* non-atomic epilogue */
+    int32_t kind;                /* epilogue: 0 run-time, 1 plain, 2 gelu + aux, 3 residual, 4 gelu', 5 plain fp32 (LayerNorm fold) */
+    int32_t lnm, np;             /* LayerNorm mode and segments of the persistent 256x256 kernel (0, 1: none) */
+    int32_t diag;                /* timeline-stamp build (cmp_gemm_set_stamps) */
+    int32_t grid_x, grid_y, grid_z, block;
+    int64_t smem;                /* dynamic LDS bytes */
+    int32_t nk, per, nsplit;     /* k-steps of the family's depth, k-steps per split, splits */
+    int32_t tiles_n, ntiles;
+    int32_t slabs, reduce_grid;  /* split-K through workspace slabs + fixed-order reduce (else f32 atomics) */
+    int32_t colsum_fused, colsum_pass;   /* armed column sums: in the epilogue, or a cmp_k_colsum pass after the launch */
+    int32_t cls;                 /* cmp_prof_* timing class, -1: not timed */
+    int32_t sched;               /* the launch draws an item-counter set */
+    int32_t empty;               /* M == 0 or N == 0: nothing is launched */
+} cmp_gemm_plan_info;
+int cmp_gemm_plan(int dtype, int ta, int tb, int M, int N, int K, const void* A, int lda, const void* Bm, int ldb, void* C,
+                  int ldc, const float* bias, int act, void* aux, int ldaux, const void* resid, int ldr, int out_fp32, int splitk,
+                  float p_drop, uint64_t seed, uint32_t rng_stream, int flags, cmp_gemm_plan_info* out);
 int cmp_k_colsum(void* stream, const void* X, int ldx, float* out, int rows, int cols, int dtype);
 /* causal attention on qkv [B,T,3E] (head-merged, transformer.py:417): o [B,T,E], lse fp32 [B,H,T] */
 int cmp_k_attn_fwd(void* stream, const void* qkv, void* o, float* lse, int B, int T, int H, int D,

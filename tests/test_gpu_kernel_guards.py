@@ -57,15 +57,16 @@ def rounded(t, dtype):
 
 
 # ------------------------------------------------------------------------------------------ GEMM
-# Kernel families: (dtype, flags).  gemm_run's dispatch (gemm.hip) takes a forced kernel (flags 4 / 8 / 16 / 48) only when the
+# Kernel families: (dtype, flags).  The launcher's plan (csrc/gemm_plan.h) takes a forced kernel (flags 4 / 8 / 16 / 48) only when the
 # shape is `fast`: K % 64 == 0, or (ta && !tb), or CMP_GEMM_KPAD_ZERO with both K-contiguous strides >= K rounded up to 64; ldc,
-# ldaux, ldr multiples of 8; N % 8 == 0 unless out_fp32 -- otherwise it silently runs the generic kernel.  Every M, N and every
+# ldaux, ldr multiples of 8; N % 8 == 0 unless out_fp32 -- otherwise it runs the generic kernel (tests/test_gemm_plan_host.py
+# asserts on the CPU that every row reaches the family it is meant for).  Every M, N and every
 # stride below is a multiple of 8, so `fast` is decided by K and the layout alone: FORCED_ROWS holds only rows that qualify (each
 # names why), FREE_ROWS says per row which kernel flags 0 picks, FP32_ROWS always run gemm_f32_kernel (these shapes are never `big`: M * N < 512 * 512).
 FAMILIES = [(FP32, 0), (BF16, 0), (BF16, 2), (BF16, 4), (BF16, 8), (BF16, 16), (BF16, 48)]
 FAMILY_IDS = ["fp32", "bf16-auto", "bf16-generic", "bf16-tile128", "bf16-tile256", "bf16-p4-256", "bf16-p4-128"]
-# flags 4: gemm_bf16_fast_kernel (128x128 direct-to-LDS); 8: launch_256 (persistent 256x256, 2-stage BK=64); 16: launch_p4 cfg 2
-# (deep pipeline 256x256, BK=32); 48: launch_p4 cfg 1 (128x256).
+# flags 4: gemm_bf16_fast_kernel (128x128 direct-to-LDS); 8: gemm_bf16_256_kernel (persistent 256x256, 2-stage BK=64); 16:
+# gemm_bf16_p4_kernel<.., 2, 4> (deep pipeline 256x256, BK=32); 48: gemm_bf16_p4_kernel<.., 1, 3> (128x256).
 LAYOUTS = [(0, 0), (0, 1), (1, 0), (1, 1)]
 EPILOGUES = ["none", "bias", "gelu", "gelugrad", "resid", "drop", "f32"]
 
@@ -111,6 +112,15 @@ FREE_ROWS = [
     (1, 1, 264, 264, 200, 1, "resid"),   # flags 0: 128x128 direct-to-LDS; flags 2: generic
     (1, 1,   8, 136,  64, 0, "bias"),    # flags 0: 128x128 direct-to-LDS; flags 2: generic
     (1, 1, 264, 264,  64, 0, "drop"),    # flags 0: 128x128 direct-to-LDS; flags 2: generic
+]
+# FREE_ROWS row by row: the kernel family flags 0 picks (the comments above, as data; flags 2 always picks "generic").  Asserted on the
+# CPU against the launcher's plan by tests/test_gemm_plan_host.py.
+FREE_AUTO = [
+    "generic", "generic", "generic", "generic", "generic", "tile128", "tile128",
+    "tile128", "tile128", "tile128", "generic", "generic", "generic", "generic",
+    "tile128", "tile128", "tile128", "tile128", "tile128", "tile128", "tile128",
+    "tile128", "tile128", "tile128", "tile128", "tile128", "tile128", "tile128",
+    "generic", "generic", "generic", "tile128", "tile128", "tile128", "tile128",
 ]
 FP32_ROWS = [
     (0, 0,   8, 264,  64, 0, "gelu"),    # gemm_f32_kernel (64x64x16 tiles: whole k-steps)
@@ -233,22 +243,28 @@ def stage_ab(ar, dtype, ta, tb, M, N, K, kz, pa, pb, o):
     return A, B
 
 
-def launch_gemm(lib, dtype, ta, tb, M, N, K, A, B, Cs, bias=None, act=0, aux=None, resid=None, out_fp32=0, splitk=1, p=0.0,
-                seed=0, rng=0, flags=0):
-    ck(lib, lib.cmp_k_gemm(stream(), dtype, ta, tb, M, N, K, P(A), A.ld, P(B), B.ld, P(Cs), Cs.ld, P(bias), act, P(aux),
-                           aux.ld if aux is not None else 0, P(resid), resid.ld if resid is not None else 0, out_fp32, splitk,
-                           p, seed, rng, flags))
+def gemm_args(dtype, ta, tb, M, N, K, A, B, Cs, bias=None, act=0, aux=None, resid=None, out_fp32=0, splitk=1, p=0.0,
+              seed=0, rng=0, flags=0):
+    """The arguments of cmp_k_gemm behind the stream (cmp_gemm_plan takes the same list)."""
+    return (dtype, ta, tb, M, N, K, P(A), A.ld, P(B), B.ld, P(Cs), Cs.ld, P(bias), act, P(aux),
+            aux.ld if aux is not None else 0, P(resid), resid.ld if resid is not None else 0, out_fp32, splitk, p, seed, rng, flags)
+
+
+def launch_gemm(lib, *a, **kw):
+    ck(lib, lib.cmp_k_gemm(stream(), *gemm_args(*a, **kw)))
 
 
 GELU_ALLOWANCE = {}       # (what, dtype) -> the largest fp32-evaluation allowance a case used (printed with -s)
 WORST = {}                # (dtype, flags) -> the largest error / limit any GEMM element reached (printed with -s)
 
 
-def gemm_case(lib, dtype, flags, ta, tb, M, N, K, kz, epi, padded):
+def stage_gemm_case(dtype, flags, ta, tb, M, N, K, kz, epi, padded, device="cuda"):
+    """The arena and the cmp_k_gemm arguments of one table row: (arena, logical operands, C, aux, arguments).  On device "cpu" the
+    same strides, flags and epilogue operands with host pointers (tests/test_gemm_plan_host.py plans them, nothing runs)."""
     o = logical_ops(dtype, M, N, K)
     dt = tdt(dtype)
     pa, pb, pc, pu, pr = (8, 16, 16, 8, 8) if padded else (0, 0, 0, 0, 0)        # lda, ldb, ldc, ldaux, ldr: not all equal
-    ar = Arena("cuda", 3 << 20)
+    ar = Arena(device, 3 << 20)
     A, B = stage_ab(ar, dtype, ta, tb, M, N, K, kz, pa, pb, o)
     out_f32 = epi == "f32"
     bf16_out = dtype == BF16 and not out_f32
@@ -268,8 +284,15 @@ def gemm_case(lib, dtype, flags, ta, tb, M, N, K, kz, epi, padded):
         kw["act"] = 2
     if epi == "drop":
         kw.update(p=0.25, seed=77, rng=9)
+    return ar, o, Cs, aux, gemm_args(dtype, ta, tb, M, N, K, A, B, Cs, **kw)
+
+
+def gemm_case(lib, dtype, flags, ta, tb, M, N, K, kz, epi, padded):
+    ar, o, Cs, aux, args = stage_gemm_case(dtype, flags, ta, tb, M, N, K, kz, epi, padded)
+    out_f32 = epi == "f32"
+    bf16_out = dtype == BF16 and not out_f32
     ar.arm()
-    launch_gemm(lib, dtype, ta, tb, M, N, K, A, B, Cs, **kw)
+    ck(lib, lib.cmp_k_gemm(stream(), *args))
     ar.check()
     what = "gemm dtype=%d flags=%d ta=%d tb=%d M=%d N=%d K=%d kz=%d %s %s" % (dtype, flags, ta, tb, M, N, K, kz, epi, "padded" if padded else "exact")
     out, ref, S, f = Cs.host(), o["ref"], o["S"], o["f"]
@@ -325,6 +348,19 @@ def test_gemm_guarded(lib, family, ta, tb):
           {k: "%.2g" % v for k, v in GELU_ALLOWANCE.items() if k[1] == dtype}))
 
 
+SPLIT_K_MODES = ("slab", "none", "atomic")
+
+
+def stage_split_k(lib, dtype, flags, ta, tb, M, N, K, o, padded, splitk, mode, device="cuda"):
+    """One launch of the split-K test: registers the slab workspace (or none) and returns (arena, C, cmp_k_gemm arguments)."""
+    ar = Arena(device, 8 << 20)
+    A, B = stage_ab(ar, dtype, ta, tb, M, N, K, 0, 8 if padded else 0, 16 if padded else 0, o)
+    Cs = ar.accumulator(o["c0"], F32, M, N, N + (16 if padded else 0), name="C")
+    ws = ar.scratch(splitk * M * N * 4, name="slab workspace")
+    ck(lib, lib.cmp_gemm_set_workspace(P(ws) if mode != "none" else None, ws.nbytes if mode != "none" else 0))
+    return ar, Cs, gemm_args(dtype, ta, tb, M, N, K, A, B, Cs, out_fp32=1, splitk=splitk, flags=flags | (128 if mode == "atomic" else 0))
+
+
 @pytest.mark.parametrize("ta,tb", [(1, 0), (0, 0)])
 @pytest.mark.parametrize("family", FAMILIES, ids=FAMILY_IDS)
 def test_gemm_split_k_guarded(lib, family, ta, tb):
@@ -339,14 +375,10 @@ def test_gemm_split_k_guarded(lib, family, ta, tb):
     try:
         for padded in (True, False):
             for splitk in (2, 8):
-                for mode in ("slab", "none", "atomic"):
-                    ar = Arena("cuda", 8 << 20)
-                    A, B = stage_ab(ar, dtype, ta, tb, M, N, K, 0, 8 if padded else 0, 16 if padded else 0, o)
-                    Cs = ar.accumulator(o["c0"], F32, M, N, N + (16 if padded else 0), name="C")
-                    ws = ar.scratch(splitk * M * N * 4, name="slab workspace")
-                    ck(lib, lib.cmp_gemm_set_workspace(P(ws) if mode != "none" else None, ws.nbytes if mode != "none" else 0))
+                for mode in SPLIT_K_MODES:
+                    ar, Cs, args = stage_split_k(lib, dtype, flags, ta, tb, M, N, K, o, padded, splitk, mode)
                     ar.arm()
-                    launch_gemm(lib, dtype, ta, tb, M, N, K, A, B, Cs, out_fp32=1, splitk=splitk, flags=flags | (128 if mode == "atomic" else 0))
+                    ck(lib, lib.cmp_k_gemm(stream(), *args))
                     ar.check()
                     KA.assert_within(Cs.host(), ref, o["f"] * S, False, "split-K dtype=%d flags=%d ta=%d tb=%d splitk=%d %s %s"
                                      % (dtype, flags, ta, tb, splitk, mode, "padded" if padded else "exact"))

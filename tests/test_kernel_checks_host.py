@@ -170,7 +170,8 @@ def test_store_before_the_first_row_is_rejected_by_the_front_guard():
 def test_gemm_case_tables_are_pairwise_covering():
     """The explicit GEMM case tables of tests/test_gpu_kernel_guards.py, each against the valid set of the families that run it
     (rows_of): every pair of values of (layout, M, N, K, epilogue) that the family can run together occurs in some row, and a forced
-    family's rows all qualify for gemm_run's `fast` dispatch.  fp32 runs no CMP_GEMM_KPAD_ZERO rows and has its own table."""
+    family's rows all qualify for the launcher's `fast` dispatch (restated here; tests/test_gemm_plan_host.py asserts the planned
+    family itself).  fp32 runs no CMP_GEMM_KPAD_ZERO rows and has its own table."""
     import test_gpu_kernel_guards as G
 
     def ks(lay, kind):
