@@ -17,72 +17,22 @@
 // [N][K] so that a wave reads one output column as a contiguous, 16-B-per-lane stream).
 // Sampling: temperature <= 0 -> argmax, lowest index on ties (tf.argmax); otherwise Gumbel-max over
 // logits/temperature == a draw from softmax(logits/temperature) (tf.random.categorical, cli.py:671-673).
+//
+// This file also holds what the batched chain (decode_batch.hip) shares with this one (declared in decode_common.h): the weight
+// transposes, the row buffers, the prefill of one row, the slide, the begin-time checks and the read-backs of both chains.
 #include "model.h"
 #include "decode_common.h"
-
-struct DecState {        // device-resident loop state
-    int pos;             // position id of the token about to be consumed
-    int token;           // that token
-    int produced;        // number of ids written to ids[]
-    int advance;         // 1: kv mode (pos += 1 per step), 0: literal (pos stays 0)
-    unsigned rng;        // sampling counter
-    int cap;             // capacity of ids[]
-    int W;               // wpe rows
-    float temperature;   // <= 0: greedy.  Temperature and seed live here (not in kernel arguments) so that the captured per-token
-    unsigned seed;       // graph does not depend on them and survives from one cmp_decode_begin to the next
-    int top_k;           // truncated sampling (decode_common.h): 0 or >= V: off
-    float top_p;         // 1: off
-    DecGrammar gr;       // event grammar (decode_common.h): layout, rules and the fold of prompt ++ ids so far
-};
-
-struct DecLayerW {
-    float *attn_wT, *proj_wT, *fc_wT, *pr_wT;
-    float *kc, *vc;      // [H][W][D]
-};
-
-struct DecodeState {
-    DecState* st = nullptr;
-    int32_t* ids = nullptr;
-    float *x = nullptr, *u = nullptr, *qkv = nullptr, *att = nullptr, *r = nullptr, *g = nullptr, *logits = nullptr;
-    std::vector<DecLayerW> lw;
-    std::vector<void*> allocs;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    int mode = 0;
-    float temperature = 0.f;
-    int top_k = 0;
-    float top_p = 1.f;
-    uint64_t seed = 0;
-    int produced = 0, returned = 0, cap = 0, pos = 0;
-    bool begun = false;
-    bool built = false;                 // buffers allocated, chain captured (reused by later cmp_decode_begin calls)
-    int64_t weights_version = -1;       // cmp_model::param_version the transposed decode weights were made from
-    bool graph_on = false;
-    // sliding-window mode (cmp_decode_begin_slide): the prompt stays on the device beside the generated ids, so that the tail a
-    // slide re-encodes is gathered without a host round trip
-    int32_t* prompt = nullptr;          // [W]
-    unsigned* banw = nullptr;           // static bans of the event grammar, ceil(V / 32) words at a fixed address (zero: none)
-    int P = 0, keep = 0;                // keep == 0: plain kv / literal decode
-    int64_t row_slides = 0, fwd_calls = 0;
-};
 
 void decode_state_free(DecodeState* d) {
     if (!d) return;
     if (d->exec) hipGraphExecDestroy(d->exec);
     if (d->graph) hipGraphDestroy(d->graph);
-    for (void* p : d->allocs) hipFree(p);
+    dec_rows_free(d->rows);
+    for (void* p : d->w.allocs) hipFree(p);
     delete d;
 }
 
-template <typename Tp> static int dalloc(DecodeState* d, Tp** p, size_t bytes) {
-    void* q = nullptr;
-    HIP_CHECK(hipMalloc(&q, bytes ? bytes : 16));
-    d->allocs.push_back(q);
-    *p = (Tp*)q;
-    return CMP_OK;
-}
-
-// out[n][k] = in[k][n]
+// out[n][k] = in[k][n]: the transposed weights of both chains
 __global__ void transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int K, int N) {
     __shared__ float tile[32][33];
     int n0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
@@ -353,7 +303,7 @@ __global__ __launch_bounds__(256) void dec_gemv2_kernel(const float* __restrict_
 template <int D>
 __global__ __launch_bounds__(256) void dec_attn2_kernel(const float* __restrict__ qkv, float* __restrict__ kcT,
                                                         float* __restrict__ vc, float* __restrict__ part,
-                                                        const DecState* __restrict__ st, int E, int W, float scale) {
+                                                        const DecRow* __restrict__ st, int E, int W, float scale) {
     constexpr int CH = D / 4;                       // 16-byte chunks per row
     constexpr int CPL = CH / 2;                     // K chunks per lane of a key pair
     constexpr int KPI = 64 / CH;                    // V rows per wave-instruction
@@ -442,22 +392,28 @@ __global__ __launch_bounds__(256) void dec_attn2_kernel(const float* __restrict_
     }
 }
 
-// K rows of the prompt into the chunk-major cache of dec_attn2_kernel
+// K / V rows of a prefill or a re-encode into the caches of both chains' attention kernels (K chunk-major): qkv [nb][T][3E], row
+// blockIdx.y of it into the caches of row rl.row[r0 + blockIdx.y]
 template <typename T>
-__global__ void cache_fill2_kernel(const T* __restrict__ qkv, float* __restrict__ kcT, float* __restrict__ vc, int P, int E,
-                                   int H, int D, int W) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= P * E) return;
-    int t = i / E, e = i % E, h = e / D, d = e % D;
-    kcT[(((int64_t)h * (D / 4) + (d >> 2)) * W + t) * 4 + (d & 3)] = to_f32<T>(qkv[(int64_t)t * 3 * E + E + e]);
-    vc[((int64_t)h * W + t) * D + d] = to_f32<T>(qkv[(int64_t)t * 3 * E + 2 * E + e]);
+__global__ void decb_cache_fill_kernel(const T* __restrict__ qkv, float* __restrict__ kcT, float* __restrict__ vc, int Tn, int E,
+                                      int D, int W, DecRowList rl, int r0) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Tn * E) return;
+    const int b = rl.row[r0 + blockIdx.y];
+    const T* q = qkv + (int64_t)blockIdx.y * Tn * 3 * E;
+    float* kr = kcT + (int64_t)b * W * E;
+    float* vr = vc + (int64_t)b * W * E;
+    const int t = i / E, e = i % E, h = e / D, d = e % D;
+    kr[(((int64_t)h * (D / 4) + (d >> 2)) * W + t) * 4 + (d & 3)] = to_f32<T>(q[(int64_t)t * 3 * E + E + e]);
+    vr[((int64_t)h * W + t) * D + d] = to_f32<T>(q[(int64_t)t * 3 * E + 2 * E + e]);
 }
 
-// next id from logits[V], then the next input embedding
+// next id from logits[V], then the next input embedding (first: the position stays; the begin's own first draw goes through
+// decb_sample_kernel, as every row of the batched chain's does)
 __global__ __launch_bounds__(256) void dec_sample2_kernel(const float* __restrict__ logits, int ldz_row_off, int V,
-                                                          DecState* __restrict__ st,
-                                                          int32_t* __restrict__ ids, const float* __restrict__ wte,
-                                                          const float* __restrict__ wpe, float* __restrict__ x, int E,
+                                                          DecRow* __restrict__ st,
+                                                          int32_t* __restrict__ ids, int capI, const float* __restrict__ wte,
+                                                          const float* __restrict__ wpe, float* __restrict__ x, int E, int Wn,
                                                           int first, const unsigned* __restrict__ banw) {
     extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
@@ -470,7 +426,7 @@ __global__ __launch_bounds__(256) void dec_sample2_kernel(const float* __restric
     const int top_k = st->top_k;
     const float top_p = st->top_p;
     const unsigned seed = st->seed;
-    const int pos0 = st->pos, adv = st->advance, nprod = st->produced, capI = st->cap, Wn = st->W;
+    const int pos0 = st->pos, adv = st->advance, nprod = st->produced;
     int pos = first ? pos0 : (adv ? pos0 + 1 : 0);
     const int posc = min(pos, Wn - 1);     // host refuses to step past the table; never index outside it
     // the position row does not depend on the sampled id: requested now, consumed after the argmax
@@ -584,65 +540,83 @@ extern "C" int cmp_decode_grammar(cmp_model* m, int batched, const cmp_event_gra
     return CMP_OK;
 }
 
-int decode_grammar_state(cmp_model* m, int row, uint32_t sounding[4], int32_t* pedal, int64_t* time_steps) {
-    DecodeState* d = m->dec;
-    if (!d || !d->begun) {
-        cmp_set_error("decode_grammar_state: call cmp_decode_begin first");
-        return CMP_ERR_STATE;
-    }
-    CMP_REQUIRE(row == 0, "decode_grammar_state: row %d of the batch-1 chain (row 0 only)", row);
+static const DecRows* dec_rows_of(const cmp_model* m, int batched) {
+    if (batched) return m->decb ? &m->decb->rows : nullptr;
+    return m->dec ? &m->dec->rows : nullptr;
+}
+static const char* dec_begin_name(int batched) { return batched ? "cmp_decode_batch_begin" : "cmp_decode_begin"; }
+
+extern "C" int cmp_decode_grammar_state(cmp_model* m, int batched, int row, uint32_t sounding[4], int32_t* pedal, int64_t* time_steps) {
+    CMP_REQUIRE(m && sounding && pedal && time_steps, "decode_grammar_state: null argument");
+    const DecRows* R = dec_rows_of(m, batched);
+    CHECK_RC(dec_require_begun("decode_grammar_state", R && R->begun, dec_begin_name(batched)));
+    if (batched) CMP_REQUIRE(row >= 0 && row < R->B, "decode_grammar_state: row %d outside the batch of %d rows", row, R->B);
+    else CMP_REQUIRE(row == 0, "decode_grammar_state: row %d of the batch-1 chain (row 0 only)", row);
     HIP_CHECK(hipSetDevice(m->ctx->device));
     HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
-    DecState h;
-    HIP_CHECK(hipMemcpy(&h, d->st, sizeof(h), hipMemcpyDeviceToHost));
+    DecRow h;
+    HIP_CHECK(hipMemcpy(&h, R->st + row, sizeof(h), hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; i++) sounding[i] = h.gr.sounding[i];
     *pedal = h.gr.pedal;
     *time_steps = h.gr.time_steps;
     return CMP_OK;
 }
 
-extern "C" int cmp_decode_grammar_state(cmp_model* m, int batched, int row, uint32_t sounding[4], int32_t* pedal, int64_t* time_steps) {
-    CMP_REQUIRE(m && sounding && pedal && time_steps, "decode_grammar_state: null argument");
-    return batched ? decode_batch_grammar_state(m, row, sounding, pedal, time_steps)
-                   : decode_grammar_state(m, row, sounding, pedal, time_steps);
+extern "C" int cmp_decode_slide_stats(cmp_model* m, int batched, int64_t* row_slides, int64_t* forward_calls) {
+    CMP_REQUIRE(m && row_slides && forward_calls, "decode_slide_stats: null argument");
+    const DecRows* R = dec_rows_of(m, batched);
+    CHECK_RC(dec_require_begun("decode_slide_stats", R && R->begun, dec_begin_name(batched)));
+    *row_slides = R->row_slides;
+    *forward_calls = R->fwd_calls;
+    return CMP_OK;
 }
 
-// Sliding window (cmp_decode_begin_slide).  The re-encode input of a slide: the last `keep` tokens of prompt ++ ids, t0 = the
-// index of the first of them in that sequence.
-__global__ void dec_slide_gather_kernel(const int32_t* __restrict__ prompt, int P, const int32_t* __restrict__ ids, int t0, int keep,
-                                        int32_t* __restrict__ out) {
+// ---- sliding window (cmp_decode_begin_slide / cmp_decode_batch_begin_slide) ----
+// The re-encode input [nb][keep] of the rows rl.row[r0 + blockIdx.y]: the last `keep` tokens of the row's prompt ++ ids, of which
+// `produced` ids exist (the same count for every row of a batch).
+__global__ void dec_slide_gather_kernel(const int32_t* __restrict__ prompts, const int32_t* __restrict__ plen,
+                                        const int32_t* __restrict__ ids, int cap, int W, int produced, int keep, DecRowList rl,
+                                        int r0, int32_t* __restrict__ out) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= keep) return;
-    const int j = t0 + g;
-    out[g] = j < P ? prompt[j] : ids[j - P];
+    const int b = rl.row[r0 + blockIdx.y];
+    const int P = plen[b];
+    const int j = P + produced - keep + g;
+    out[(int64_t)blockIdx.y * keep + g] = j < P ? prompts[(int64_t)b * W + j] : ids[(int64_t)b * cap + (j - P)];
 }
 
-// The draw of a slide: from the re-encode's last logits row, as cmp_decode_begin draws its first id from the prompt's last row --
-// but the draw counter, the produced count and the seed carry on.  The token drawn is consumed next at position `keep`; the row
-// is copied to where cmp_decode_logits_get reads.
-__global__ __launch_bounds__(256) void dec_slide_sample_kernel(const float* __restrict__ z, int V, DecState* __restrict__ st,
-                                                               int32_t* __restrict__ ids, const float* __restrict__ wte,
-                                                               const float* __restrict__ wpe, float* __restrict__ x, int E, int keep,
-                                                               float* __restrict__ zout, const unsigned* __restrict__ banw) {
+// The draw of a slide for row b = rl.row[r0 + blockIdx.x], from the last row of its re-encode (logits [nb][keep][ldz]): as the
+// first id of a begin, but the row's draw counter, produced count and seed carry on.  The token is consumed next at position
+// `keep`; the logits row goes to where cmp_decode_logits_get / cmp_decode_batch_logits_get read; the hold is over.
+__global__ __launch_bounds__(256) void dec_slide_sample_kernel(const float* __restrict__ logits, int ldz, int V, DecRow* __restrict__ st,
+                                                               DecRowList rl, int r0, int32_t* __restrict__ ids, int cap,
+                                                               const float* __restrict__ wte, const float* __restrict__ wpe,
+                                                               float* __restrict__ x, int E, int keep, float* __restrict__ zout,
+                                                               const unsigned* __restrict__ banw) {
     extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
     __shared__ int bi[4];
-    const int tid = threadIdx.x;
-    const unsigned ctr = st->rng;
-    const int nprod = st->produced, capI = st->cap;
-    const GramRegs g0 = grammar_read(&st->gr);
-    const int id = sample_block_grammar(z, V, st->temperature, st->top_k, st->top_p, st->seed, ctr, bv, bi, trunc_lds, g0, banw);
-    __syncthreads();                    // every thread has read the state before thread 0 moves it on
+    const int tid = threadIdx.x, b = rl.row[r0 + blockIdx.x];
+    const float* z = logits + ((int64_t)blockIdx.x * keep + keep - 1) * ldz;
+    DecRow* rs = st + b;
+    const unsigned ctr = rs->rng;
+    const int nprod = rs->produced;
+    const GramRegs g0 = grammar_read(&rs->gr);
+    const int id = sample_block_grammar(z, V, rs->temperature, rs->top_k, rs->top_p, rs->seed, ctr, bv, bi, trunc_lds, g0, banw);
+    __syncthreads();                       // every thread has read the state before thread 0 moves it on
     if (tid == 0) {
-        if (nprod < capI) ids[nprod] = id;
-        st->produced = nprod + 1;
-        st->rng = ctr + 1;
-        st->token = id;
-        st->pos = keep;
-        grammar_advance(&st->gr, g0, id);
+        if (nprod < cap) ids[(int64_t)b * cap + nprod] = id;
+        rs->produced = nprod + 1;
+        rs->rng = ctr + 1;
+        rs->token = id;
+        rs->pos = keep;
+        rs->hold = 0;
+        grammar_advance(&rs->gr, g0, id);
     }
-    for (int e = tid; e < E; e += 256) x[e] = wte[(int64_t)id * E + e] + wpe[(int64_t)keep * E + e];
-    for (int c = tid; c < V; c += 256) zout[c] = z[c];
+    float* xr = x + (int64_t)b * E;
+    for (int e = tid; e < E; e += 256) xr[e] = wte[(int64_t)id * E + e] + wpe[(int64_t)keep * E + e];
+    float* zo = zout + (int64_t)b * ldz;
+    for (int c = tid; c < V; c += 256) zo[c] = z[c];
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -683,54 +657,217 @@ static int launch_gemv2(hipStream_t s, int act, int in_mode, const float* x, con
     return CMP_OK;
 }
 
-static int launch_attn2(hipStream_t s, cmp_model* m, DecodeState* d, const DecLayerW& w, float scale) {
+static int launch_attn2(hipStream_t s, cmp_model* m, const DecRows& R, int layer, float scale) {
     dim3 grid(m->H, ATT_SPLITS);
+    float *kc = R.kc[layer], *vc = R.vc[layer];
     switch (m->D) {
-        case 16: dec_attn2_kernel<16><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
-        case 32: dec_attn2_kernel<32><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
-        case 64: dec_attn2_kernel<64><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
-        case 128: dec_attn2_kernel<128><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
+        case 16: dec_attn2_kernel<16><<<grid, 256, 0, s>>>(R.qkv, kc, vc, R.att, R.st, m->Ea, m->W, scale); break;
+        case 32: dec_attn2_kernel<32><<<grid, 256, 0, s>>>(R.qkv, kc, vc, R.att, R.st, m->Ea, m->W, scale); break;
+        case 64: dec_attn2_kernel<64><<<grid, 256, 0, s>>>(R.qkv, kc, vc, R.att, R.st, m->Ea, m->W, scale); break;
+        case 128: dec_attn2_kernel<128><<<grid, 256, 0, s>>>(R.qkv, kc, vc, R.att, R.st, m->Ea, m->W, scale); break;
         default: CMP_REQUIRE(false, "decode attention: head size %d has no kernel (16, 32, 64, 128)", m->D);
     }
     KERNEL_CHECK();
     return CMP_OK;
 }
 
-// one token: consumes d->x (embedding of st->token at st->pos), produces the next id and the next d->x
+// one token: consumes R.x (embedding of st->token at st->pos), produces the next id and the next R.x
 static int enqueue_token_step(cmp_model* m, DecodeState* d) {
     hipStream_t s = m->ctx->stream;
+    const DecRows& R = d->rows;
     const int E = m->E, Ea = m->Ea, L = m->L;
     const bool ln = m->cfg.use_layer_norm != 0;
     const float eps = m->cfg.ln_eps;
     const float scale = m->cfg.scale_attention ? 1.0f / sqrtf((float)m->Dl) : 1.0f;
     for (int i = 0; i < L; i++) {
         const LayerOff& o = m->lo[i];
-        const DecLayerW& w = d->lw[i];
-        CHECK_RC(launch_gemv2(s, 0, ln ? 1 : 0, d->x, m->P + o.ln1_g, m->P + o.ln1_b, eps, w.attn_wT, m->P + o.attn_b, nullptr,
-                              d->qkv, d->u, E, 3 * Ea, m->D));
-        CHECK_RC(launch_attn2(s, m, d, w, scale));
-        CHECK_RC(launch_gemv2(s, 0, 2, d->att, nullptr, nullptr, eps, w.proj_wT, m->P + o.proj_b, d->u, d->r, nullptr, Ea, E, m->D));
-        CHECK_RC(launch_gemv2(s, 1, ln ? 1 : 0, d->r, m->P + o.ln2_g, m->P + o.ln2_b, eps, w.fc_wT, m->P + o.fc_b, nullptr, d->g,
+        const DecLayerW& w = d->w.lw[i];
+        CHECK_RC(launch_gemv2(s, 0, ln ? 1 : 0, R.x, m->P + o.ln1_g, m->P + o.ln1_b, eps, w.attn_wT, m->P + o.attn_b, nullptr,
+                              R.qkv, R.u, E, 3 * Ea, m->D));
+        CHECK_RC(launch_attn2(s, m, R, i, scale));
+        CHECK_RC(launch_gemv2(s, 0, 2, R.att, nullptr, nullptr, eps, w.proj_wT, m->P + o.proj_b, R.u, R.r, nullptr, Ea, E, m->D));
+        CHECK_RC(launch_gemv2(s, 1, ln ? 1 : 0, R.r, m->P + o.ln2_g, m->P + o.ln2_b, eps, w.fc_wT, m->P + o.fc_b, nullptr, R.g,
                               nullptr, E, 4 * E, m->D));
-        CHECK_RC(launch_gemv2(s, 0, 0, d->g, nullptr, nullptr, eps, w.pr_wT, m->P + o.pr_b, d->r, d->x, nullptr, 4 * E, E, m->D));
+        CHECK_RC(launch_gemv2(s, 0, 0, R.g, nullptr, nullptr, eps, w.pr_wT, m->P + o.pr_b, R.r, R.x, nullptr, 4 * E, E, m->D));
     }
-    CHECK_RC(launch_gemv2(s, 0, 1, d->x, m->P + m->off_lnf_g, m->P + m->off_lnf_b, eps, m->P + m->off_wte, nullptr, nullptr,
-                          d->logits, nullptr, E, m->V, m->D));
-    dec_sample2_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(d->logits, 0, m->V, d->st, d->ids, m->P + m->off_wte,
-                                                             m->P + m->off_wpe, d->x, E, 0, d->banw);
+    CHECK_RC(launch_gemv2(s, 0, 1, R.x, m->P + m->off_lnf_g, m->P + m->off_lnf_b, eps, m->P + m->off_wte, nullptr, nullptr,
+                          R.logits, nullptr, E, m->V, m->D));
+    dec_sample2_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(R.logits, 0, m->V, R.st, R.ids, R.cap, m->P + m->off_wte,
+                                                             m->P + m->off_wpe, R.x, E, m->W, 0, d->w.banw);
     KERNEL_CHECK();
     return CMP_OK;
 }
 
+// ---- what both chains do around their per-token chains (decode_common.h) ----
+bool dec_graph_enabled() {
+    const char* e = getenv("COMPOSER_NO_GRAPH");
+    return !(e && e[0] == '1');
+}
+
+int dec_check_prompt(const char* who, int row, const int32_t* ids, int P, int V, int W) {
+    char at[96];
+    if (row < 0) snprintf(at, sizeof at, "%s", who);
+    else snprintf(at, sizeof at, "%s: row %d", who, row);
+    CMP_REQUIRE(P <= W, "%s: prompt length %d exceeds window_size %d", at, P, W);
+    for (int i = 0; i < P; i++) CMP_REQUIRE(ids[i] >= 0 && ids[i] < V, "%s: prompt id %d out of range [0,%d)", at, ids[i], V);
+    return CMP_OK;
+}
+
+int dec_check_keep(const char* who, int keep, int W) {
+    CMP_REQUIRE(keep >= 1 && keep <= W - 1, "%s: keep=%d outside [1, window_size - 1 = %d]", who, keep, W - 1);
+    return CMP_OK;
+}
+
+int dec_require_begun(const char* who, bool begun, const char* begin_fn) {
+    if (begun) return CMP_OK;
+    cmp_set_error("%s: call %s first", who, begin_fn);
+    return CMP_ERR_STATE;
+}
+
+int dec_weights_refresh(cmp_model* m, DecWeights& w) {
+    const int E = m->E, Ea = m->Ea, L = m->L;
+    if (w.lw.empty()) {
+        w.lw.resize(L);
+        for (DecLayerW& l : w.lw) {
+            CHECK_RC(dec_alloc(w.allocs, &l.attn_wT, (size_t)3 * Ea * E * 4));
+            CHECK_RC(dec_alloc(w.allocs, &l.proj_wT, (size_t)Ea * E * 4));
+            CHECK_RC(dec_alloc(w.allocs, &l.fc_wT, (size_t)4 * E * E * 4));
+            CHECK_RC(dec_alloc(w.allocs, &l.pr_wT, (size_t)4 * E * E * 4));
+        }
+    }
+    if (!w.banw) CHECK_RC(dec_alloc(w.allocs, &w.banw, (size_t)grammar_words(m->V) * 4));
+    if (w.version == m->param_version) return CMP_OK;
+    for (int i = 0; i < L; i++) {
+        const LayerOff& o = m->lo[i];
+        const DecLayerW& l = w.lw[i];
+        auto tr = [&](const float* in, float* out, int K, int N) {
+            dim3 grid(cdiv(N, 32), cdiv(K, 32));
+            transpose_kernel<<<grid, 256, 0, m->ctx->stream>>>(in, out, K, N);
+        };
+        tr(m->P + o.attn_w, l.attn_wT, E, 3 * Ea);
+        tr(m->P + o.proj_w, l.proj_wT, Ea, E);
+        tr(m->P + o.fc_w, l.fc_wT, E, 4 * E);
+        tr(m->P + o.pr_w, l.pr_wT, 4 * E, E);
+        KERNEL_CHECK();
+    }
+    w.version = m->param_version;
+    return CMP_OK;
+}
+
+void dec_rows_free(DecRows& R) {
+    for (void* p : R.allocs) hipFree(p);
+    R.allocs.clear();
+    R.kc.clear();
+    R.vc.clear();
+    R.capB = 0;
+}
+
+int dec_rows_alloc(cmp_model* m, DecRows& R, int B) {
+    dec_rows_free(R);
+    const int E = m->E, Ea = m->Ea, W = m->W;
+    const size_t Bz = (size_t)B;
+    std::vector<void*>& al = R.allocs;
+    CHECK_RC(dec_alloc(al, &R.st, Bz * sizeof(DecRow)));
+    CHECK_RC(dec_alloc(al, &R.ids, Bz * R.cap * 4));
+    CHECK_RC(dec_alloc(al, &R.x, Bz * E * 4));
+    CHECK_RC(dec_alloc(al, &R.u, Bz * E * 4));
+    CHECK_RC(dec_alloc(al, &R.qkv, Bz * 3 * Ea * 4));
+    CHECK_RC(dec_alloc(al, &R.att, Bz * m->H * ATT_SPLITS * PSTRIDE(m->D) * 4));      // split-key attention partials
+    CHECK_RC(dec_alloc(al, &R.r, Bz * E * 4));
+    CHECK_RC(dec_alloc(al, &R.g, Bz * 4 * E * 4));
+    CHECK_RC(dec_alloc(al, &R.logits, Bz * m->ldz * 4));
+    CHECK_RC(dec_alloc(al, &R.prompts, Bz * W * 4));
+    CHECK_RC(dec_alloc(al, &R.plen, Bz * 4));
+    R.kc.assign(m->L, nullptr);
+    R.vc.assign(m->L, nullptr);
+    for (int i = 0; i < m->L; i++) {
+        CHECK_RC(dec_alloc(al, &R.kc[i], Bz * W * Ea * 4));
+        CHECK_RC(dec_alloc(al, &R.vc[i], Bz * W * Ea * 4));
+    }
+    R.capB = B;
+    return CMP_OK;
+}
+
+DecRow dec_row_init(int mode, int P, unsigned seed, float temperature, int top_k, float top_p, const DecGrammarCfg& c,
+                    const int32_t* prompt) {
+    DecRow h = {};
+    h.pos = (mode == CMP_DECODE_KV) ? P : 0;     // position of the first generated token when it is fed back
+    h.advance = (mode == CMP_DECODE_KV) ? 1 : 0;
+    h.seed = seed;
+    h.temperature = temperature;
+    h.top_k = top_k;
+    h.top_p = top_p;
+    h.gr = grammar_begin(c, prompt, P);
+    return h;
+}
+
+// K / V rows of the forward pass just enqueued (nc sequences of T tokens) into the caches of rows rl.row[r0 .. r0 + nc)
+static int dec_cache_fill(cmp_model* m, const DecRows& R, int T, const DecRowList& rl, int r0, int nc) {
+    hipStream_t s = m->ctx->stream;
+    const dim3 grid(cdiv(T * m->Ea, 256), nc);
+    for (int i = 0; i < m->L; i++) {
+        if (m->dtype == CMP_BF16)
+            decb_cache_fill_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)m->act[i].qkv, R.kc[i], R.vc[i], T, m->Ea, m->D, m->W, rl, r0);
+        else
+            decb_cache_fill_kernel<float><<<grid, 256, 0, s>>>((const float*)m->act[i].qkv, R.kc[i], R.vc[i], T, m->Ea, m->D, m->W, rl, r0);
+        KERNEL_CHECK();
+    }
+    return CMP_OK;
+}
+
+// Prefill of row b, whose DecRow is already on the device: the whole prompt through the batched forward (Transformer.call with
+// past=None), its K / V rows into the row's caches (kv mode), the first id from the last prompt row (cli.py:673 `[-1, 0]`).  The
+// host prompt upload is stream-ordered, so the stream is drained before the next row's ids may overwrite the staging buffer.
+int dec_prefill_row(cmp_model* m, DecRows& R, const DecWeights& w, int b, const int32_t* prompt, int P) {
+    hipStream_t s = m->ctx->stream;
+    CHECK_RC(ensure_workspace(m, 1, P));
+    HIP_CHECK(hipMemcpyAsync(m->x_dev, prompt, (size_t)P * 4, hipMemcpyHostToDevice, s));
+    if (R.keep > 0) HIP_CHECK(hipMemcpyAsync(R.prompts + (int64_t)b * m->W, m->x_dev, (size_t)P * 4, hipMemcpyDeviceToDevice, s));
+    CHECK_RC(model_forward(m, m->x_dev, 1, P, false, 0));
+    if (R.mode == CMP_DECODE_KV) {
+        DecRowList rl = {};
+        rl.row[0] = (unsigned char)b;
+        CHECK_RC(dec_cache_fill(m, R, P, rl, 0, 1));
+    }
+    CHECK_RC(decb_launch_sample(m, R, w, m->logits + (int64_t)(P - 1) * m->ldz, 1, b, 1));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return CMP_OK;
+}
+
+// The slide of the nb rows of rl (all at pos == W; on the batched chain held during the replay just enqueued) INSTEAD of their
+// per-token step: gather the tails, re-encode them, refill the caches, draw.  The tails go through the forward pass together, as
+// many rows per call as the workspace holds.  An fp32 forward is the same arithmetic per row whatever rows share the call (one
+// GEMM kernel, no split-K, per-row attention and LayerNorm); the bf16 forward picks its GEMM kernels by the token count, so a
+// bf16 model re-encodes one row per call, as its prefill does, and a row stays independent of its neighbours.
+int dec_enqueue_slide(cmp_model* m, DecRows& R, const DecWeights& w, const DecRowList& rl, int nb) {
+    hipStream_t s = m->ctx->stream;
+    const int keep = R.keep;
+    const int64_t ws_rows = ((int64_t)m->capB * m->capT) / keep;
+    const int per = m->dtype == CMP_BF16 ? 1 : (int)std::max<int64_t>(1, std::min<int64_t>(ws_rows, nb));
+    for (int r0 = 0; r0 < nb; r0 += per) {
+        const int nc = std::min(per, nb - r0);
+        dec_slide_gather_kernel<<<dim3(cdiv(keep, 256), nc), 256, 0, s>>>(R.prompts, R.plen, R.ids, R.cap, m->W, R.produced, keep, rl,
+                                                                         r0, m->x_dev);
+        KERNEL_CHECK();
+        CHECK_RC(model_forward(m, m->x_dev, nc, keep, false, 0));
+        CHECK_RC(dec_cache_fill(m, R, keep, rl, r0, nc));
+        dec_slide_sample_kernel<<<nc, 256, trunc_lds_bytes(m->V), s>>>(m->logits, m->ldz, m->V, R.st, rl, r0, R.ids, R.cap, m->P + m->off_wte,
+                                                                       m->P + m->off_wpe, R.x, m->E, keep, R.logits, w.banw);
+        KERNEL_CHECK();
+        R.fwd_calls++;
+    }
+    R.row_slides += nb;
+    return CMP_OK;
+}
+
+// ---- the batch-1 chain's entry points ----
 // keep > 0: sliding-window mode (cmp_decode_begin_slide), kv mode otherwise unchanged
 static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mode, float temperature, int top_k, float top_p,
                              uint64_t seed, int keep) {
     CMP_REQUIRE(m && prompt && P > 0, "decode_begin: prompt must hold at least one id");
     CMP_REQUIRE(mode == CMP_DECODE_LITERAL || mode == CMP_DECODE_KV, "decode_begin: bad mode %d", mode);
     CHECK_RC(sampling_check("decode_begin", m->V, temperature, top_k, top_p));
-    CMP_REQUIRE(P <= m->W, "decode_begin: prompt length %d exceeds window_size %d", P, m->W);
-    for (int i = 0; i < P; i++)
-        CMP_REQUIRE(prompt[i] >= 0 && prompt[i] < m->V, "decode_begin: prompt id %d out of range [0,%d)", prompt[i], m->V);
+    CHECK_RC(dec_check_prompt("decode_begin", -1, prompt, P, m->V, m->W));
     HIP_CHECK(hipSetDevice(m->ctx->device));
     hipStream_t s = m->ctx->stream;
     // the workspace never grows after its first sizing: a slide re-encodes `keep` tokens through it, so it is sized (or found too
@@ -739,130 +876,39 @@ static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mod
     // The decode state (buffers, KV caches, transposed fp32 weights, the captured per-token chain) is built once per model
     // and reused by later calls: of the 7.6 ms a call used to spend here before the first token (45 hipMalloc / hipFree, 24
     // transposes, capture + instantiate: 6 % of a 1024-token generate) what is left is the prefill.  The transposes are
-    // redone when a parameter has changed since (cmp_model::param_version); the chain is re-captured only when the kernel
-    // generation or the graph switch changes (temperature, seed and mode live in the device-side state).
-    const bool graph_on = [] { const char* e = getenv("COMPOSER_NO_GRAPH"); return !(e && e[0] == '1'); }();
+    // redone when a parameter has changed since (cmp_model::param_version); the chain is re-captured only when the graph
+    // switch changes (temperature, seed and mode live in the device-side state).
+    const bool graph_on = dec_graph_enabled();
     DecodeState* d = m->dec;
-    if (d && !d->built) {                       // an earlier call failed part-way (an allocation, the capture): start over
+    // an earlier call failed part-way (an allocation, the capture), or the graph switch has changed: start over
+    if (d && (!d->built || d->graph_on != graph_on)) {
         HIP_CHECK(hipStreamSynchronize(s));
         decode_state_free(d);
         m->dec = d = nullptr;
     }
-    if (d && d->built && (d->graph_on != graph_on)) {
-        HIP_CHECK(hipStreamSynchronize(s));
-        decode_state_free(d);
-        m->dec = d = nullptr;
-    }
-    if (!d) {
-        d = new DecodeState();
-        m->dec = d;
-    }
-    d->begun = false;
-    d->mode = mode;
-    d->temperature = temperature;
-    d->top_k = top_k;
-    d->top_p = top_p;
-    d->seed = seed;
-    d->cap = 1 << 16;
-    const int E = m->E, Ea = m->Ea, L = m->L, W = m->W;
-    if (!d->built) {
-        CHECK_RC(dalloc(d, &d->st, sizeof(DecState)));
-        CHECK_RC(dalloc(d, &d->ids, (size_t)d->cap * 4));
-        CHECK_RC(dalloc(d, &d->x, (size_t)E * 4));
-        CHECK_RC(dalloc(d, &d->u, (size_t)E * 4));
-        CHECK_RC(dalloc(d, &d->qkv, (size_t)3 * Ea * 4));
-        CHECK_RC(dalloc(d, &d->att, (size_t)m->H * ATT_SPLITS * PSTRIDE(m->D) * 4));  // split-key attention partials
-        CHECK_RC(dalloc(d, &d->r, (size_t)E * 4));
-        CHECK_RC(dalloc(d, &d->g, (size_t)4 * E * 4));
-        CHECK_RC(dalloc(d, &d->logits, (size_t)m->ldz * 4));
-        CHECK_RC(dalloc(d, &d->banw, (size_t)grammar_words(m->V) * 4));
-        d->lw.resize(L);
-        for (int i = 0; i < L; i++) {
-            DecLayerW& w = d->lw[i];
-            CHECK_RC(dalloc(d, &w.attn_wT, (size_t)3 * Ea * E * 4));
-            CHECK_RC(dalloc(d, &w.proj_wT, (size_t)Ea * E * 4));
-            CHECK_RC(dalloc(d, &w.fc_wT, (size_t)4 * E * E * 4));
-            CHECK_RC(dalloc(d, &w.pr_wT, (size_t)4 * E * E * 4));
-            CHECK_RC(dalloc(d, &w.kc, (size_t)W * Ea * 4));
-            CHECK_RC(dalloc(d, &w.vc, (size_t)W * Ea * 4));
-        }
-    }
-    d->keep = keep;
-    d->P = P;
-    d->row_slides = d->fwd_calls = 0;
-    if (keep > 0 && !d->prompt) CHECK_RC(dalloc(d, &d->prompt, (size_t)W * 4));
-    if (d->weights_version != m->param_version) {
-        for (int i = 0; i < L; i++) {
-            const LayerOff& o = m->lo[i];
-            DecLayerW& w = d->lw[i];
-            auto tr = [&](const float* in, float* out, int K, int N) {
-                dim3 grid(cdiv(N, 32), cdiv(K, 32));
-                transpose_kernel<<<grid, 256, 0, s>>>(in, out, K, N);
-            };
-            tr(m->P + o.attn_w, w.attn_wT, E, 3 * Ea);
-            tr(m->P + o.proj_w, w.proj_wT, Ea, E);
-            tr(m->P + o.fc_w, w.fc_wT, E, 4 * E);
-            tr(m->P + o.pr_w, w.pr_wT, 4 * E, E);
-            KERNEL_CHECK();
-        }
-        d->weights_version = m->param_version;
-    }
-    // prefill: the whole prompt through the batched forward (Transformer.call with past=None)
-    CHECK_RC(ensure_workspace(m, 1, P));
-    HIP_CHECK(hipMemcpyAsync(m->x_dev, prompt, (size_t)P * 4, hipMemcpyHostToDevice, s));
-    if (keep > 0) HIP_CHECK(hipMemcpyAsync(d->prompt, m->x_dev, (size_t)P * 4, hipMemcpyDeviceToDevice, s));
-    CHECK_RC(model_forward(m, m->x_dev, 1, P, false, 0));
-    if (mode == CMP_DECODE_KV) {
-        for (int i = 0; i < L; i++) {
-            int grid = cdiv(P * Ea, 256);
-            {
-                if (m->dtype == CMP_BF16)
-                    cache_fill2_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)m->act[i].qkv, d->lw[i].kc, d->lw[i].vc, P, Ea, m->H, m->D, W);
-                else
-                    cache_fill2_kernel<float><<<grid, 256, 0, s>>>((const float*)m->act[i].qkv, d->lw[i].kc, d->lw[i].vc, P, Ea, m->H, m->D, W);
-            }
-            KERNEL_CHECK();
-        }
-    }
-    DecState h = {};
-    h.pos = (mode == CMP_DECODE_KV) ? P : 0;     // position of the first generated token when it is fed back
-    h.token = 0;
-    h.produced = 0;
-    h.advance = (mode == CMP_DECODE_KV) ? 1 : 0;
-    h.rng = 0;
-    h.cap = d->cap;
-    h.W = W;
-    h.temperature = temperature;
-    h.seed = (unsigned)seed;
-    h.top_k = top_k;
-    h.top_p = top_p;
-    h.gr = grammar_begin(m->gram[0], prompt, P);
-    HIP_CHECK(grammar_upload(m->gram[0], m->V, d->banw, s));
-    HIP_CHECK(hipMemcpyAsync(d->st, &h, sizeof(h), hipMemcpyHostToDevice, s));
-    // first id from the last prompt row (cli.py:673 `[-1, 0]`)
-    dec_sample2_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(m->logits, (P - 1) * m->ldz, m->V, d->st, d->ids, m->P + m->off_wte,
-                                                             m->P + m->off_wpe, d->x, E, 1, d->banw);
-    KERNEL_CHECK();
-    HIP_CHECK(hipStreamSynchronize(s));
-    d->produced = 1;
-    d->returned = 0;
+    if (!d) m->dec = d = new DecodeState();
+    DecRows& R = d->rows;
+    R.begun = false;
+    if (!d->built) CHECK_RC(dec_rows_alloc(m, R, 1));
+    CHECK_RC(dec_weights_refresh(m, d->w));
+    R.B = 1;
+    R.mode = mode;
+    R.keep = keep;
+    R.row_slides = R.fwd_calls = 0;
+    const DecRow h = dec_row_init(mode, P, (unsigned)seed, temperature, top_k, top_p, m->gram[0], prompt);
+    HIP_CHECK(grammar_upload(m->gram[0], m->V, d->w.banw, s));
+    HIP_CHECK(hipMemcpyAsync(R.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
+    if (keep > 0) HIP_CHECK(hipMemcpyAsync(R.plen, &P, 4, hipMemcpyHostToDevice, s));
+    CHECK_RC(dec_prefill_row(m, R, d->w, 0, prompt, P));
+    R.produced = 1;
+    R.returned = 0;
     d->pos = h.pos;
-    // capture the per-token chain once per decode state
-    if (!d->built) {
-        if (graph_on) {
-            HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            int rc = enqueue_token_step(m, d);
-            hipGraph_t g = nullptr;
-            hipError_t e = hipStreamEndCapture(s, &g);
-            if (rc != CMP_OK) return rc;
-            HIP_CHECK(e);
-            d->graph = g;
-            HIP_CHECK(hipGraphInstantiate(&d->exec, g, nullptr, nullptr, 0));
-        }
+    if (!d->built) {                            // the per-token chain, captured once per decode state
+        if (graph_on) CHECK_RC(dec_capture(s, [&] { return enqueue_token_step(m, d); }, &d->graph, &d->exec));
         d->graph_on = graph_on;
         d->built = true;
     }
-    d->begun = true;
+    R.begun = true;
     return CMP_OK;
 }
 
@@ -877,7 +923,7 @@ extern "C" int cmp_decode_begin_ex(cmp_model* m, const int32_t* prompt, int P, i
     CMP_REQUIRE(m, "decode_begin_ex: null model");
     if (keep != 0) {
         CMP_REQUIRE(mode == CMP_DECODE_KV, "decode_begin_ex: keep=%d goes with CMP_DECODE_KV", keep);
-        CMP_REQUIRE(keep >= 1 && keep <= m->W - 1, "decode_begin_ex: keep=%d outside [1, window_size - 1 = %d]", keep, m->W - 1);
+        CHECK_RC(dec_check_keep("decode_begin_ex", keep, m->W));
     }
     return decode_begin_impl(m, prompt, P, mode, temperature, top_k, top_p, seed, keep);
 }
@@ -886,97 +932,54 @@ extern "C" int cmp_decode_begin_ex(cmp_model* m, const int32_t* prompt, int P, i
 // and the next id is drawn from that pass (composer_hip.h: the contract c(n))
 extern "C" int cmp_decode_begin_slide(cmp_model* m, const int32_t* prompt, int P, int keep, float temperature, uint64_t seed) {
     CMP_REQUIRE(m, "decode_begin_slide: null model");
-    CMP_REQUIRE(keep >= 1 && keep <= m->W - 1, "decode_begin_slide: keep=%d outside [1, window_size - 1 = %d]", keep, m->W - 1);
+    CHECK_RC(dec_check_keep("decode_begin_slide", keep, m->W));
     return decode_begin_impl(m, prompt, P, CMP_DECODE_KV, temperature, 0, 1.0f, seed, keep);
-}
-
-// One slide INSTEAD of a per-token step (the captured chain is not touched): gather the tail, re-encode it, refill the caches,
-// draw.  d->produced ids exist; the sequence so far is prompt ++ ids[0 .. produced).
-static int enqueue_slide(cmp_model* m, DecodeState* d) {
-    hipStream_t s = m->ctx->stream;
-    const int keep = d->keep, Ea = m->Ea, W = m->W;
-    dec_slide_gather_kernel<<<cdiv(keep, 256), 256, 0, s>>>(d->prompt, d->P, d->ids, d->P + d->produced - keep, keep, m->x_dev);
-    KERNEL_CHECK();
-    CHECK_RC(model_forward(m, m->x_dev, 1, keep, false, 0));
-    for (int i = 0; i < m->L; i++) {
-        const int grid = cdiv(keep * Ea, 256);
-        if (m->dtype == CMP_BF16)
-            cache_fill2_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)m->act[i].qkv, d->lw[i].kc, d->lw[i].vc, keep, Ea, m->H, m->D, W);
-        else
-            cache_fill2_kernel<float><<<grid, 256, 0, s>>>((const float*)m->act[i].qkv, d->lw[i].kc, d->lw[i].vc, keep, Ea, m->H, m->D, W);
-        KERNEL_CHECK();
-    }
-    dec_slide_sample_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(m->logits + (int64_t)(keep - 1) * m->ldz, m->V, d->st, d->ids, m->P + m->off_wte,
-                                              m->P + m->off_wpe, d->x, m->E, keep, d->logits, d->banw);
-    KERNEL_CHECK();
-    d->row_slides++;
-    d->fwd_calls++;
-    return CMP_OK;
-}
-
-int decode_slide_stats(DecodeState* d, int64_t* row_slides, int64_t* forward_calls) {
-    if (!d || !d->begun) {
-        cmp_set_error("decode_slide_stats: call cmp_decode_begin first");
-        return CMP_ERR_STATE;
-    }
-    *row_slides = d->row_slides;
-    *forward_calls = d->fwd_calls;
-    return CMP_OK;
-}
-
-extern "C" int cmp_decode_slide_stats(cmp_model* m, int batched, int64_t* row_slides, int64_t* forward_calls) {
-    CMP_REQUIRE(m && row_slides && forward_calls, "decode_slide_stats: null argument");
-    return batched ? decode_batch_slide_stats(m->decb, row_slides, forward_calls) : decode_slide_stats(m->dec, row_slides, forward_calls);
 }
 
 extern "C" int cmp_decode_steps(cmp_model* m, int n, int32_t* ids_out) {
     CMP_REQUIRE(m && ids_out && n >= 0, "decode_steps: bad arguments");
     DecodeState* d = m->dec;
-    if (!d || !d->begun) {
-        cmp_set_error("decode_steps: call cmp_decode_begin first");
-        return CMP_ERR_STATE;
-    }
+    CHECK_RC(dec_require_begun("decode_steps", d && d->rows.begun, "cmp_decode_begin"));
+    DecRows& R = d->rows;
     HIP_CHECK(hipSetDevice(m->ctx->device));
     hipStream_t s = m->ctx->stream;
-    const int need = d->returned + n;
-    CMP_REQUIRE(need <= d->cap, "decode_steps: more than %d ids per decode_begin", d->cap);
-    while (d->produced < need) {
-        if (d->keep > 0 && d->pos >= m->W) {        // the window is full: this id comes from a re-encode of the tail
-            CHECK_RC(enqueue_slide(m, d));
-            d->produced++;
-            d->pos = d->keep;
+    const int need = R.returned + n;
+    CMP_REQUIRE(need <= R.cap, "decode_steps: more than %d ids per decode_begin", R.cap);
+    while (R.produced < need) {
+        if (R.keep > 0 && d->pos >= m->W) {         // the window is full: this id comes from a re-encode of the tail
+            const DecRowList row0 = {};             // (the captured chain is not touched)
+            CHECK_RC(dec_enqueue_slide(m, R, d->w, row0, 1));
+            R.produced++;
+            d->pos = R.keep;
             continue;
         }
-        if (d->mode == CMP_DECODE_KV)
+        if (R.mode == CMP_DECODE_KV)
             CMP_REQUIRE(d->pos < m->W, "decode_steps: position %d outside the wpe table (window_size %d): "
                         "prompt_len + length - 1 must be <= window_size in kv-cache mode", d->pos, m->W);
         if (d->exec) HIP_CHECK(hipGraphLaunch(d->exec, s));
         else CHECK_RC(enqueue_token_step(m, d));
-        d->produced++;
-        if (d->mode == CMP_DECODE_KV) d->pos++;
+        R.produced++;
+        if (R.mode == CMP_DECODE_KV) d->pos++;
     }
-    HIP_CHECK(hipMemcpyAsync(ids_out, d->ids + d->returned, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(ids_out, R.ids + R.returned, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    d->returned = need;
+    R.returned = need;
     return CMP_OK;
 }
 
-// The logits the most recent per-token step drew its id from (d->logits, ldz padding stripped): host fp32 [V].  Read-only, outside
+// The logits the most recent per-token step drew its id from (R.logits, ldz padding stripped): host fp32 [V].  Read-only, outside
 // the per-token chain.  The first id of a decode comes from the prefill's logits (cmp_forward_logits shows those), so there is
 // nothing to read before the first step has run.
 extern "C" int cmp_decode_logits_get(cmp_model* m, float* host_out) {
     CMP_REQUIRE(m && host_out, "decode_logits_get: null argument");
     DecodeState* d = m->dec;
-    if (!d || !d->begun) {
-        cmp_set_error("decode_logits_get: call cmp_decode_begin first");
-        return CMP_ERR_STATE;
-    }
-    if (d->produced < 2) {
+    CHECK_RC(dec_require_begun("decode_logits_get", d && d->rows.begun, "cmp_decode_begin"));
+    if (d->rows.produced < 2) {
         cmp_set_error("decode_logits_get: no per-token step has run yet (the first id is drawn from the prefill's logits)");
         return CMP_ERR_STATE;
     }
     HIP_CHECK(hipSetDevice(m->ctx->device));
     HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
-    HIP_CHECK(hipMemcpy(host_out, d->logits, (size_t)m->V * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(host_out, d->rows.logits, (size_t)m->V * 4, hipMemcpyDeviceToHost));
     return CMP_OK;
 }

@@ -14,62 +14,10 @@
 // Sliding-window mode (cmp_decode_batch_begin_slide): a row whose cache is full sits out the replay (DecRow::hold) and draws
 // that step's id from a re-encode of its last `keep` tokens; rows that slide at the same step share forward calls.
 //
-// State lives apart from the batch-1 DecodeState (m->dec): own transposed weights, buffers, KV caches and captured chains.
+// State lives apart from the batch-1 DecodeState (m->dec): own transposed weights, buffers, KV caches and captured chains.  What
+// surrounds the chain -- row state, prefill of a row, slide, checks, capture -- is decode.hip's, shared through decode_common.h.
 #include "model.h"
 #include "decode_common.h"
-
-#include <map>
-
-#define DECB_MAX_ROWS 256
-
-struct DecRow {          // device-resident per-row loop state (the captured chain does not depend on it)
-    int pos;             // position id of the token about to be consumed
-    int token;           // that token
-    int produced;        // ids written to this row's slot of ids[]
-    int advance;         // 1: kv mode (pos += 1 per step), 0: literal (pos stays 0)
-    unsigned rng;        // sampling counter
-    unsigned seed;       // (uint32)(seed + b)
-    float temperature;   // <= 0: greedy
-    int hold;            // sliding-window mode: 1 while the row sits out a replay (its cache is full, pos == W): attention neither
-                         // appends nor reads, the sampler leaves the row alone; the row's slide, run after the replay, clears it
-    int top_k;           // truncated sampling (decode_common.h), per row: 0 or >= V: off
-    float top_p;         // 1: off
-    DecGrammar gr;       // event grammar (decode_common.h): layout, rules and the fold of the row's prompt ++ ids so far
-};
-
-struct DecRowList {      // rows of one slide, by value in the kernel arguments: no host buffer has to outlive an enqueued step
-    unsigned char row[DECB_MAX_ROWS];
-};
-
-struct DecBatchLayerW {
-    float *attn_wT, *proj_wT, *fc_wT, *pr_wT;
-    float *kc, *vc;      // [capB] x the batch-1 layouts: K [H][D/4][W][4], V [H][W][D]
-};
-
-struct DecodeBatchState {
-    int capB = 0;                       // rows the row buffers and caches hold
-    int cap = 0;                        // ids per row
-    DecRow* st = nullptr;
-    int32_t* ids = nullptr;             // [capB][cap]
-    float *x = nullptr, *u = nullptr, *qkv = nullptr, *att = nullptr, *r = nullptr, *g = nullptr, *logits = nullptr;
-    std::vector<DecBatchLayerW> lw;
-    std::vector<void*> row_allocs;      // sized by capB (replaced when a larger B is asked for)
-    std::vector<void*> w_allocs;        // transposed weights (independent of B)
-    unsigned* banw = nullptr;           // static bans of the event grammar, ceil(V / 32) words shared by all rows (in w_allocs: its
-                                        // address outlives every captured chain)
-    std::map<int, std::pair<hipGraph_t, hipGraphExec_t>> graphs;     // captured chain per B
-    bool graph_on = true;
-    int64_t weights_version = -1;
-    int B = 0, mode = 0;
-    int produced = 0, returned = 0;
-    std::vector<int> pos;               // host mirror of each row's position (kv-mode window check; which rows slide at which step)
-    bool begun = false;
-    // sliding-window mode (cmp_decode_batch_begin_slide): every row's prompt and its length stay on the device beside its ids
-    int32_t* prompts = nullptr;         // [capB][W]
-    int32_t* plen = nullptr;            // [capB]
-    int keep = 0;                       // 0: plain kv / literal decode
-    int64_t row_slides = 0, fwd_calls = 0;
-};
 
 static void decb_drop_graphs(DecodeBatchState* d) {
     for (auto& kv : d->graphs) {
@@ -79,43 +27,12 @@ static void decb_drop_graphs(DecodeBatchState* d) {
     d->graphs.clear();
 }
 
-static void decb_free_rows(DecodeBatchState* d) {
-    decb_drop_graphs(d);
-    for (void* p : d->row_allocs) hipFree(p);
-    d->row_allocs.clear();
-    for (auto& w : d->lw) w.kc = w.vc = nullptr;
-    d->capB = 0;
-}
-
 void decode_batch_state_free(DecodeBatchState* d) {
     if (!d) return;
-    decb_free_rows(d);
-    for (void* p : d->w_allocs) hipFree(p);
+    decb_drop_graphs(d);
+    dec_rows_free(d->rows);
+    for (void* p : d->w.allocs) hipFree(p);
     delete d;
-}
-
-template <typename Tp> static int balloc(std::vector<void*>& list, Tp** p, size_t bytes) {
-    void* q = nullptr;
-    HIP_CHECK(hipMalloc(&q, bytes ? bytes : 16));
-    list.push_back(q);
-    *p = (Tp*)q;
-    return CMP_OK;
-}
-
-// out[n][k] = in[k][n] (the batch-1 transpose, here for the batch state's own copies)
-__global__ void decb_transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int K, int N) {
-    __shared__ float tile[32][33];
-    int n0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
-    int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-    for (int j = ty; j < 32; j += 8) {
-        int k = k0 + j, n = n0 + tx;
-        tile[j][tx] = (k < K && n < N) ? in[(int64_t)k * N + n] : 0.f;
-    }
-    __syncthreads();
-    for (int j = ty; j < 32; j += 8) {
-        int n = n0 + j, k = k0 + tx;
-        if (n < N && k < K) out[(int64_t)n * K + k] = tile[tx][j];
-    }
 }
 
 // Y[b][n] = act( IN(X)[b,:] . Wt[n,:] + bias[n] ) + resid[b][n] for b < B, on v_mfma_f32_16x16x4_f32.
@@ -343,17 +260,6 @@ __global__ __launch_bounds__(256) void decb_attn_kernel(const float* __restrict_
     }
 }
 
-// the prompt's K / V rows of one row's prefill into that row's caches
-template <typename T>
-__global__ void decb_cache_fill_kernel(const T* __restrict__ qkv, float* __restrict__ kcT, float* __restrict__ vc, int P, int E,
-                                       int D, int W) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= P * E) return;
-    int t = i / E, e = i % E, h = e / D, d = e % D;
-    kcT[(((int64_t)h * (D / 4) + (d >> 2)) * W + t) * 4 + (d & 3)] = to_f32<T>(qkv[(int64_t)t * 3 * E + E + e]);
-    vc[((int64_t)h * W + t) * D + d] = to_f32<T>(qkv[(int64_t)t * 3 * E + 2 * E + e]);
-}
-
 // Row b = row0 + blockIdx.x: next id from logits row blockIdx.x (stride ldz), then the row's next input embedding.  first: the
 // draw from the prefill's last row (the position stays where cmp_decode_batch_begin put it).
 __global__ __launch_bounds__(256) void decb_sample_kernel(const float* __restrict__ logits, int ldz, int V, DecRow* __restrict__ st,
@@ -388,73 +294,10 @@ __global__ __launch_bounds__(256) void decb_sample_kernel(const float* __restric
     for (int e = tid; e < E; e += 256) xr[e] = wte[(int64_t)id * E + e] + wpe[(int64_t)posc * E + e];
 }
 
-// ---- sliding window (cmp_decode_batch_begin_slide) ----
-// rows rl.row[0 .. nb) sit out the next replay
+// sliding window (cmp_decode_batch_begin_slide): rows rl.row[0 .. nb) sit out the next replay
 __global__ void decb_hold_kernel(DecRow* __restrict__ st, DecRowList rl, int nb) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nb) st[rl.row[i]].hold = 1;
-}
-
-// The re-encode input [nb][keep] of the rows rl.row[r0 + blockIdx.y]: the last `keep` tokens of the row's prompt ++ ids, of which
-// `produced` ids exist (the same count for every row of the batch).
-__global__ void decb_slide_gather_kernel(const int32_t* __restrict__ prompts, const int32_t* __restrict__ plen,
-                                         const int32_t* __restrict__ ids, int cap, int W, int produced, int keep, DecRowList rl,
-                                         int r0, int32_t* __restrict__ out) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= keep) return;
-    const int b = rl.row[r0 + blockIdx.y];
-    const int P = plen[b];
-    const int j = P + produced - keep + g;
-    out[(int64_t)blockIdx.y * keep + g] = j < P ? prompts[(int64_t)b * W + j] : ids[(int64_t)b * cap + (j - P)];
-}
-
-// decb_cache_fill_kernel for the nb rows of one re-encode: qkv [nb][keep][3E], row blockIdx.y into the caches of rl.row[r0 + blockIdx.y]
-template <typename T>
-__global__ void decb_slide_fill_kernel(const T* __restrict__ qkv, float* __restrict__ kcT, float* __restrict__ vc, int keep, int E,
-                                       int D, int W, DecRowList rl, int r0) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= keep * E) return;
-    const int b = rl.row[r0 + blockIdx.y];
-    const T* q = qkv + (int64_t)blockIdx.y * keep * 3 * E;
-    float* kr = kcT + (int64_t)b * W * E;
-    float* vr = vc + (int64_t)b * W * E;
-    const int t = i / E, e = i % E, h = e / D, d = e % D;
-    kr[(((int64_t)h * (D / 4) + (d >> 2)) * W + t) * 4 + (d & 3)] = to_f32<T>(q[(int64_t)t * 3 * E + E + e]);
-    vr[((int64_t)h * W + t) * D + d] = to_f32<T>(q[(int64_t)t * 3 * E + 2 * E + e]);
-}
-
-// The draw of a slide for row b = rl.row[r0 + blockIdx.x], from the last row of its re-encode (logits [nb][keep][ldz]): as the
-// first id of a begin, but the row's draw counter, produced count and seed carry on.  The token is consumed next at position
-// `keep`; the logits row goes to where cmp_decode_batch_logits_get reads; the hold is over.
-__global__ __launch_bounds__(256) void decb_slide_sample_kernel(const float* __restrict__ logits, int ldz, int V, DecRow* __restrict__ st,
-                                                                DecRowList rl, int r0, int32_t* __restrict__ ids, int cap,
-                                                                const float* __restrict__ wte, const float* __restrict__ wpe,
-                                                                float* __restrict__ x, int E, int keep, float* __restrict__ zout,
-                                                                const unsigned* __restrict__ banw) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
-    __shared__ float bv[4];
-    __shared__ int bi[4];
-    const int tid = threadIdx.x, b = rl.row[r0 + blockIdx.x];
-    const float* z = logits + ((int64_t)blockIdx.x * keep + keep - 1) * ldz;
-    DecRow* rs = st + b;
-    const unsigned ctr = rs->rng;
-    const int nprod = rs->produced;
-    const GramRegs g0 = grammar_read(&rs->gr);
-    const int id = sample_block_grammar(z, V, rs->temperature, rs->top_k, rs->top_p, rs->seed, ctr, bv, bi, trunc_lds, g0, banw);
-    __syncthreads();                       // every thread has read the state before thread 0 moves it on
-    if (tid == 0) {
-        if (nprod < cap) ids[(int64_t)b * cap + nprod] = id;
-        rs->produced = nprod + 1;
-        rs->rng = ctr + 1;
-        rs->token = id;
-        rs->pos = keep;
-        rs->hold = 0;
-        grammar_advance(&rs->gr, g0, id);
-    }
-    float* xr = x + (int64_t)b * E;
-    for (int e = tid; e < E; e += 256) xr[e] = wte[(int64_t)id * E + e] + wpe[(int64_t)keep * E + e];
-    float* zo = zout + (int64_t)b * ldz;
-    for (int c = tid; c < V; c += 256) zo[c] = z[c];
 }
 
 // row b of logits [B][ldz] -> ids_out[b], seed (uint32)(seed + b), draw counter `counter`
@@ -523,69 +366,51 @@ static int launch_proj(hipStream_t s, int act, int in_mode, const float* x, cons
     return CMP_OK;
 }
 
-static int launch_attn(hipStream_t s, cmp_model* m, DecodeBatchState* d, const DecBatchLayerW& w, float scale, int B) {
+static int launch_attn(hipStream_t s, cmp_model* m, const DecRows& R, int layer, float scale, int B) {
     dim3 grid(m->H, ATT_SPLITS, B);
+    float *kc = R.kc[layer], *vc = R.vc[layer];
     switch (m->D) {
-        case 16: decb_attn_kernel<16><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
-        case 32: decb_attn_kernel<32><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
-        case 64: decb_attn_kernel<64><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
-        case 128: decb_attn_kernel<128><<<grid, 256, 0, s>>>(d->qkv, w.kc, w.vc, d->att, d->st, m->Ea, m->W, scale); break;
+        case 16: decb_attn_kernel<16><<<grid, 256, 0, s>>>(R.qkv, kc, vc, R.att, R.st, m->Ea, m->W, scale); break;
+        case 32: decb_attn_kernel<32><<<grid, 256, 0, s>>>(R.qkv, kc, vc, R.att, R.st, m->Ea, m->W, scale); break;
+        case 64: decb_attn_kernel<64><<<grid, 256, 0, s>>>(R.qkv, kc, vc, R.att, R.st, m->Ea, m->W, scale); break;
+        case 128: decb_attn_kernel<128><<<grid, 256, 0, s>>>(R.qkv, kc, vc, R.att, R.st, m->Ea, m->W, scale); break;
         default: CMP_REQUIRE(false, "decode_batch attention: head size %d has no kernel (16, 32, 64, 128)", m->D);
     }
     KERNEL_CHECK();
     return CMP_OK;
 }
 
-// one token for every row: consumes d->x (row b: embedding of its token at its position), produces the next ids and d->x
+int decb_launch_sample(cmp_model* m, DecRows& R, const DecWeights& w, const float* logits, int nrows, int row0, int first) {
+    decb_sample_kernel<<<nrows, 256, trunc_lds_bytes(m->V), m->ctx->stream>>>(logits, m->ldz, m->V, R.st, row0, R.ids, R.cap, m->P + m->off_wte,
+                                                                            m->P + m->off_wpe, R.x, m->E, m->W, first, w.banw);
+    KERNEL_CHECK();
+    return CMP_OK;
+}
+
+// one token for every row: consumes R.x (row b: embedding of its token at its position), produces the next ids and R.x
 static int enqueue_batch_step(cmp_model* m, DecodeBatchState* d, int B) {
     hipStream_t s = m->ctx->stream;
+    DecRows& R = d->rows;
     const int E = m->E, Ea = m->Ea, L = m->L;
     const bool ln = m->cfg.use_layer_norm != 0;
     const float eps = m->cfg.ln_eps;
     const float scale = m->cfg.scale_attention ? 1.0f / sqrtf((float)m->Dl) : 1.0f;
     for (int i = 0; i < L; i++) {
         const LayerOff& o = m->lo[i];
-        const DecBatchLayerW& w = d->lw[i];
-        CHECK_RC(launch_proj(s, 0, ln ? 1 : 0, d->x, m->P + o.ln1_g, m->P + o.ln1_b, eps, w.attn_wT, m->P + o.attn_b, nullptr,
-                             d->qkv, 3 * Ea, d->u, E, 3 * Ea, m->D, B));
-        CHECK_RC(launch_attn(s, m, d, w, scale, B));
-        CHECK_RC(launch_proj(s, 0, 2, d->att, nullptr, nullptr, eps, w.proj_wT, m->P + o.proj_b, d->u, d->r, E, nullptr, Ea, E,
+        const DecLayerW& w = d->w.lw[i];
+        CHECK_RC(launch_proj(s, 0, ln ? 1 : 0, R.x, m->P + o.ln1_g, m->P + o.ln1_b, eps, w.attn_wT, m->P + o.attn_b, nullptr,
+                             R.qkv, 3 * Ea, R.u, E, 3 * Ea, m->D, B));
+        CHECK_RC(launch_attn(s, m, R, i, scale, B));
+        CHECK_RC(launch_proj(s, 0, 2, R.att, nullptr, nullptr, eps, w.proj_wT, m->P + o.proj_b, R.u, R.r, E, nullptr, Ea, E,
                              m->D, B));
-        CHECK_RC(launch_proj(s, 1, ln ? 1 : 0, d->r, m->P + o.ln2_g, m->P + o.ln2_b, eps, w.fc_wT, m->P + o.fc_b, nullptr, d->g,
+        CHECK_RC(launch_proj(s, 1, ln ? 1 : 0, R.r, m->P + o.ln2_g, m->P + o.ln2_b, eps, w.fc_wT, m->P + o.fc_b, nullptr, R.g,
                              4 * E, nullptr, E, 4 * E, m->D, B));
-        CHECK_RC(launch_proj(s, 0, 0, d->g, nullptr, nullptr, eps, w.pr_wT, m->P + o.pr_b, d->r, d->x, E, nullptr, 4 * E, E, m->D,
+        CHECK_RC(launch_proj(s, 0, 0, R.g, nullptr, nullptr, eps, w.pr_wT, m->P + o.pr_b, R.r, R.x, E, nullptr, 4 * E, E, m->D,
                              B));
     }
-    CHECK_RC(launch_proj(s, 0, 1, d->x, m->P + m->off_lnf_g, m->P + m->off_lnf_b, eps, m->P + m->off_wte, nullptr, nullptr,
-                         d->logits, m->ldz, nullptr, E, m->V, m->D, B));
-    decb_sample_kernel<<<B, 256, trunc_lds_bytes(m->V), s>>>(d->logits, m->ldz, m->V, d->st, 0, d->ids, d->cap, m->P + m->off_wte, m->P + m->off_wpe,
-                                         d->x, E, m->W, 0, d->banw);
-    KERNEL_CHECK();
-    return CMP_OK;
-}
-
-static int decb_alloc_rows(cmp_model* m, DecodeBatchState* d, int B) {
-    decb_free_rows(d);
-    const int E = m->E, Ea = m->Ea, W = m->W;
-    const size_t Bz = (size_t)B;
-    std::vector<void*>& al = d->row_allocs;
-    CHECK_RC(balloc(al, &d->st, Bz * sizeof(DecRow)));
-    CHECK_RC(balloc(al, &d->ids, Bz * d->cap * 4));
-    CHECK_RC(balloc(al, &d->x, Bz * E * 4));
-    CHECK_RC(balloc(al, &d->u, Bz * E * 4));
-    CHECK_RC(balloc(al, &d->qkv, Bz * 3 * Ea * 4));
-    CHECK_RC(balloc(al, &d->att, Bz * m->H * ATT_SPLITS * PSTRIDE(m->D) * 4));
-    CHECK_RC(balloc(al, &d->r, Bz * E * 4));
-    CHECK_RC(balloc(al, &d->g, Bz * 4 * E * 4));
-    CHECK_RC(balloc(al, &d->logits, Bz * m->ldz * 4));
-    CHECK_RC(balloc(al, &d->prompts, Bz * W * 4));
-    CHECK_RC(balloc(al, &d->plen, Bz * 4));
-    for (auto& w : d->lw) {
-        CHECK_RC(balloc(al, &w.kc, Bz * W * Ea * 4));
-        CHECK_RC(balloc(al, &w.vc, Bz * W * Ea * 4));
-    }
-    d->capB = B;
-    return CMP_OK;
+    CHECK_RC(launch_proj(s, 0, 1, R.x, m->P + m->off_lnf_g, m->P + m->off_lnf_b, eps, m->P + m->off_wte, nullptr, nullptr,
+                         R.logits, m->ldz, nullptr, E, m->V, m->D, B));
+    return decb_launch_sample(m, R, d->w, R.logits, B, 0, 0);
 }
 
 // keep > 0: sliding-window mode (cmp_decode_batch_begin_slide), kv mode otherwise unchanged
@@ -603,11 +428,7 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
     for (int b = 0; b < B; b++) {
         CMP_REQUIRE(lens[b] >= 1, "decode_batch_begin: row %d is empty", b);
         CMP_REQUIRE(lens[b] <= ld, "decode_batch_begin: row %d: length %d exceeds the leading dimension %d", b, lens[b], ld);
-        CMP_REQUIRE(lens[b] <= m->W, "decode_batch_begin: row %d: prompt length %d exceeds window_size %d", b, lens[b], m->W);
-        for (int i = 0; i < lens[b]; i++) {
-            const int v = prompts[(int64_t)b * ld + i];
-            CMP_REQUIRE(v >= 0 && v < m->V, "decode_batch_begin: row %d: prompt id %d out of range [0,%d)", b, v, m->V);
-        }
+        CHECK_RC(dec_check_prompt("decode_batch_begin", b, prompts + (int64_t)b * ld, lens[b], m->V, m->W));
     }
     HIP_CHECK(hipSetDevice(m->ctx->device));
     hipStream_t s = m->ctx->stream;
@@ -618,117 +439,48 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
         for (int b = 0; b < B; b++) maxP = std::max(maxP, lens[b]);
         CHECK_RC(ensure_workspace(m, 1, std::max(maxP, keep)));
     }
-    const bool graph_on = [] { const char* e = getenv("COMPOSER_NO_GRAPH"); return !(e && e[0] == '1'); }();
+    const bool graph_on = dec_graph_enabled();
     DecodeBatchState* d = m->decb;
-    if (!d) {
-        d = new DecodeBatchState();
-        m->decb = d;
-        d->cap = 1 << 16;
-    }
-    d->begun = false;
-    const int E = m->E, Ea = m->Ea, L = m->L, W = m->W;
-    if (d->lw.empty()) {
-        d->lw.resize(L);
-        for (auto& w : d->lw) {
-            CHECK_RC(balloc(d->w_allocs, &w.attn_wT, (size_t)3 * Ea * E * 4));
-            CHECK_RC(balloc(d->w_allocs, &w.proj_wT, (size_t)Ea * E * 4));
-            CHECK_RC(balloc(d->w_allocs, &w.fc_wT, (size_t)4 * E * E * 4));
-            CHECK_RC(balloc(d->w_allocs, &w.pr_wT, (size_t)4 * E * E * 4));
-            w.kc = w.vc = nullptr;
-        }
-    }
-    if (!d->banw) CHECK_RC(balloc(d->w_allocs, &d->banw, (size_t)grammar_words(m->V) * 4));
+    if (!d) m->decb = d = new DecodeBatchState();
+    DecRows& R = d->rows;
+    R.begun = false;
     if (d->graph_on != graph_on) {
         HIP_CHECK(hipStreamSynchronize(s));
         decb_drop_graphs(d);
         d->graph_on = graph_on;
     }
-    if (B > d->capB) {                          // the captured chains hold the old buffers: they go with them
+    if (B > R.capB) {                           // the captured chains hold the old buffers: they go with them
         HIP_CHECK(hipStreamSynchronize(s));
-        const int rc = decb_alloc_rows(m, d, B);
-        if (rc != CMP_OK) { decb_free_rows(d); return rc; }
+        decb_drop_graphs(d);
+        const int rc = dec_rows_alloc(m, R, B);
+        if (rc != CMP_OK) { dec_rows_free(R); return rc; }
     }
-    if (d->weights_version != m->param_version) {
-        for (int i = 0; i < L; i++) {
-            const LayerOff& o = m->lo[i];
-            DecBatchLayerW& w = d->lw[i];
-            auto tr = [&](const float* in, float* out, int K, int N) {
-                dim3 grid(cdiv(N, 32), cdiv(K, 32));
-                decb_transpose_kernel<<<grid, 256, 0, s>>>(in, out, K, N);
-            };
-            tr(m->P + o.attn_w, w.attn_wT, E, 3 * Ea);
-            tr(m->P + o.proj_w, w.proj_wT, Ea, E);
-            tr(m->P + o.fc_w, w.fc_wT, E, 4 * E);
-            tr(m->P + o.pr_w, w.pr_wT, 4 * E, E);
-            KERNEL_CHECK();
-        }
-        d->weights_version = m->param_version;
-    }
-    std::vector<DecRow> h(B, DecRow{});
+    CHECK_RC(dec_weights_refresh(m, d->w));
+    R.mode = mode;
+    R.keep = keep;
+    R.row_slides = R.fwd_calls = 0;
+    std::vector<DecRow> h(B);
     d->pos.assign(B, 0);
     for (int b = 0; b < B; b++) {
-        h[b].pos = (mode == CMP_DECODE_KV) ? lens[b] : 0;     // position of the row's first generated token when it is fed back
-        h[b].token = 0;
-        h[b].produced = 0;
-        h[b].advance = (mode == CMP_DECODE_KV) ? 1 : 0;
-        h[b].rng = 0;
-        h[b].seed = (unsigned)(seed + (uint64_t)b);
-        h[b].temperature = temperature ? temperature[b] : temperature0;
-        h[b].hold = 0;
-        h[b].top_k = top_k ? top_k[b] : 0;
-        h[b].top_p = top_p ? top_p[b] : 1.0f;
-        h[b].gr = grammar_begin(m->gram[1], prompts + (int64_t)b * ld, lens[b]);
+        h[b] = dec_row_init(mode, lens[b], (unsigned)(seed + (uint64_t)b), temperature ? temperature[b] : temperature0,
+                            top_k ? top_k[b] : 0, top_p ? top_p[b] : 1.0f, m->gram[1], prompts + (int64_t)b * ld);
         d->pos[b] = h[b].pos;
     }
-    d->keep = keep;
-    d->row_slides = d->fwd_calls = 0;
-    HIP_CHECK(grammar_upload(m->gram[1], m->V, d->banw, s));
-    HIP_CHECK(hipMemcpyAsync(d->st, h.data(), (size_t)B * sizeof(DecRow), hipMemcpyHostToDevice, s));
-    if (keep > 0) HIP_CHECK(hipMemcpyAsync(d->plen, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
-    // prefill, one row at a time through the batch-1 path's forward call; the host prompt upload is stream-ordered, so the
-    // stream is drained before the next row's ids overwrite the staging buffer
-    for (int b = 0; b < B; b++) {
-        const int P = lens[b];
-        CHECK_RC(ensure_workspace(m, 1, P));
-        HIP_CHECK(hipMemcpyAsync(m->x_dev, prompts + (int64_t)b * ld, (size_t)P * 4, hipMemcpyHostToDevice, s));
-        if (keep > 0) HIP_CHECK(hipMemcpyAsync(d->prompts + (int64_t)b * W, m->x_dev, (size_t)P * 4, hipMemcpyDeviceToDevice, s));
-        CHECK_RC(model_forward(m, m->x_dev, 1, P, false, 0));
-        if (mode == CMP_DECODE_KV) {
-            for (int i = 0; i < L; i++) {
-                float* kc = d->lw[i].kc + (int64_t)b * W * Ea;
-                float* vc = d->lw[i].vc + (int64_t)b * W * Ea;
-                const int grid = cdiv(P * Ea, 256);
-                if (m->dtype == CMP_BF16)
-                    decb_cache_fill_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)m->act[i].qkv, kc, vc, P, Ea, m->D, W);
-                else
-                    decb_cache_fill_kernel<float><<<grid, 256, 0, s>>>((const float*)m->act[i].qkv, kc, vc, P, Ea, m->D, W);
-                KERNEL_CHECK();
-            }
-        }
-        // first id from the row's last prompt position (cli.py:673 `[-1, 0]`), seed + b, draw counter 0
-        decb_sample_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(m->logits + (int64_t)(P - 1) * m->ldz, m->ldz, m->V, d->st, b, d->ids, d->cap,
-                                             m->P + m->off_wte, m->P + m->off_wpe, d->x, E, W, 1, d->banw);
-        KERNEL_CHECK();
-        HIP_CHECK(hipStreamSynchronize(s));
-    }
-    d->B = B;
-    d->mode = mode;
-    d->produced = 1;
-    d->returned = 0;
+    HIP_CHECK(grammar_upload(m->gram[1], m->V, d->w.banw, s));
+    HIP_CHECK(hipMemcpyAsync(R.st, h.data(), (size_t)B * sizeof(DecRow), hipMemcpyHostToDevice, s));
+    if (keep > 0) HIP_CHECK(hipMemcpyAsync(R.plen, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    // prefill, one row at a time through the batch-1 chain's own call: a row's first id is the batch-1 first id for seed + b
+    for (int b = 0; b < B; b++) CHECK_RC(dec_prefill_row(m, R, d->w, b, prompts + (int64_t)b * ld, lens[b]));
+    R.B = B;
+    R.produced = 1;
+    R.returned = 0;
     if (graph_on && !d->graphs.count(B)) {      // the per-token chain, captured once per B on one linear stream
-        HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue_batch_step(m, d, B);
         hipGraph_t g = nullptr;
-        hipError_t e = hipStreamEndCapture(s, &g);
-        if (rc != CMP_OK) { if (g) hipGraphDestroy(g); return rc; }
-        HIP_CHECK(e);
         hipGraphExec_t ex = nullptr;
-        hipError_t ei = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-        if (ei != hipSuccess) hipGraphDestroy(g);
-        HIP_CHECK(ei);
+        CHECK_RC(dec_capture(s, [&] { return enqueue_batch_step(m, d, B); }, &g, &ex));
         d->graphs[B] = {g, ex};
     }
-    d->begun = true;
+    R.begun = true;
     return CMP_OK;
 }
 
@@ -745,7 +497,7 @@ extern "C" int cmp_decode_batch_begin_ex(cmp_model* m, const int32_t* prompts, c
     CMP_REQUIRE(m, "decode_batch_begin_ex: null model");
     if (keep != 0) {
         CMP_REQUIRE(mode == CMP_DECODE_KV, "decode_batch_begin_ex: keep=%d goes with CMP_DECODE_KV", keep);
-        CMP_REQUIRE(keep >= 1 && keep <= m->W - 1, "decode_batch_begin_ex: keep=%d outside [1, window_size - 1 = %d]", keep, m->W - 1);
+        CHECK_RC(dec_check_keep("decode_batch_begin_ex", keep, m->W));
     }
     return decode_batch_begin_impl(m, prompts, lens, B, ld, mode, 1.0f, temperature, top_k, top_p, seed, keep);
 }
@@ -753,91 +505,30 @@ extern "C" int cmp_decode_batch_begin_ex(cmp_model* m, const int32_t* prompts, c
 extern "C" int cmp_decode_batch_begin_slide(cmp_model* m, const int32_t* prompts, const int32_t* lens, int B, int ld, int keep,
                                             float temperature, uint64_t seed) {
     CMP_REQUIRE(m, "decode_batch_begin_slide: null model");
-    CMP_REQUIRE(keep >= 1 && keep <= m->W - 1, "decode_batch_begin_slide: keep=%d outside [1, window_size - 1 = %d]", keep, m->W - 1);
+    CHECK_RC(dec_check_keep("decode_batch_begin_slide", keep, m->W));
     return decode_batch_begin_impl(m, prompts, lens, B, ld, CMP_DECODE_KV, temperature, nullptr, nullptr, nullptr, seed, keep);
-}
-
-// The slide of the nb rows of rl (all at pos == W, held during the replay just enqueued): their tails go through the forward pass
-// together, as many rows per call as the workspace holds.  An fp32 forward is the same arithmetic per row whatever rows share the
-// call (one GEMM kernel, no split-K, per-row attention and LayerNorm); the bf16 forward picks its GEMM kernels by the token
-// count, so a bf16 model re-encodes one row per call, as its prefill does, and a row stays independent of its neighbours.
-static int enqueue_batch_slide(cmp_model* m, DecodeBatchState* d, const DecRowList& rl, int nb) {
-    hipStream_t s = m->ctx->stream;
-    const int keep = d->keep, Ea = m->Ea, W = m->W;
-    const int64_t ws_rows = ((int64_t)m->capB * m->capT) / keep;
-    const int per = m->dtype == CMP_BF16 ? 1 : (int)std::max<int64_t>(1, std::min<int64_t>(ws_rows, nb));
-    for (int r0 = 0; r0 < nb; r0 += per) {
-        const int nc = std::min(per, nb - r0);
-        decb_slide_gather_kernel<<<dim3(cdiv(keep, 256), nc), 256, 0, s>>>(d->prompts, d->plen, d->ids, d->cap, W, d->produced, keep, rl,
-                                                                          r0, m->x_dev);
-        KERNEL_CHECK();
-        CHECK_RC(model_forward(m, m->x_dev, nc, keep, false, 0));
-        for (int i = 0; i < m->L; i++) {
-            const dim3 grid(cdiv(keep * Ea, 256), nc);
-            if (m->dtype == CMP_BF16)
-                decb_slide_fill_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)m->act[i].qkv, d->lw[i].kc, d->lw[i].vc, keep, Ea, m->D, W, rl, r0);
-            else
-                decb_slide_fill_kernel<float><<<grid, 256, 0, s>>>((const float*)m->act[i].qkv, d->lw[i].kc, d->lw[i].vc, keep, Ea, m->D, W, rl, r0);
-            KERNEL_CHECK();
-        }
-        decb_slide_sample_kernel<<<nc, 256, trunc_lds_bytes(m->V), s>>>(m->logits, m->ldz, m->V, d->st, rl, r0, d->ids, d->cap, m->P + m->off_wte,
-                                                    m->P + m->off_wpe, d->x, m->E, keep, d->logits, d->banw);
-        KERNEL_CHECK();
-        d->fwd_calls++;
-    }
-    d->row_slides += nb;
-    return CMP_OK;
-}
-
-int decode_batch_slide_stats(DecodeBatchState* d, int64_t* row_slides, int64_t* forward_calls) {
-    if (!d || !d->begun) {
-        cmp_set_error("decode_slide_stats: call cmp_decode_batch_begin first");
-        return CMP_ERR_STATE;
-    }
-    *row_slides = d->row_slides;
-    *forward_calls = d->fwd_calls;
-    return CMP_OK;
-}
-
-int decode_batch_grammar_state(cmp_model* m, int row, uint32_t sounding[4], int32_t* pedal, int64_t* time_steps) {
-    DecodeBatchState* d = m->decb;
-    if (!d || !d->begun) {
-        cmp_set_error("decode_grammar_state: call cmp_decode_batch_begin first");
-        return CMP_ERR_STATE;
-    }
-    CMP_REQUIRE(row >= 0 && row < d->B, "decode_grammar_state: row %d outside the batch of %d rows", row, d->B);
-    HIP_CHECK(hipSetDevice(m->ctx->device));
-    HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
-    DecRow h;
-    HIP_CHECK(hipMemcpy(&h, d->st + row, sizeof(h), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 4; i++) sounding[i] = h.gr.sounding[i];
-    *pedal = h.gr.pedal;
-    *time_steps = h.gr.time_steps;
-    return CMP_OK;
 }
 
 extern "C" int cmp_decode_batch_steps(cmp_model* m, int n, int32_t* ids_out) {
     CMP_REQUIRE(m && n >= 0 && (ids_out || n == 0), "decode_batch_steps: bad arguments");
     DecodeBatchState* d = m->decb;
-    if (!d || !d->begun) {
-        cmp_set_error("decode_batch_steps: call cmp_decode_batch_begin first");
-        return CMP_ERR_STATE;
-    }
+    CHECK_RC(dec_require_begun("decode_batch_steps", d && d->rows.begun, "cmp_decode_batch_begin"));
+    DecRows& R = d->rows;
     HIP_CHECK(hipSetDevice(m->ctx->device));
     hipStream_t s = m->ctx->stream;
-    const int B = d->B;
-    const int need = d->returned + n;
-    CMP_REQUIRE(need <= d->cap, "decode_batch_steps: more than %d ids per row per decode_batch_begin", d->cap);
+    const int B = R.B;
+    const int need = R.returned + n;
+    CMP_REQUIRE(need <= R.cap, "decode_batch_steps: more than %d ids per row per decode_batch_begin", R.cap);
     auto it = d->graphs.find(B);
     hipGraphExec_t ex = (d->graph_on && it != d->graphs.end()) ? it->second.second : nullptr;
     // kv mode: refused before any step runs, so a refused call consumes nothing (the last step consumes position pos + todo - 1)
-    const int todo = std::max(0, need - d->produced);
-    if (d->mode == CMP_DECODE_KV && d->keep == 0 && todo > 0)
+    const int todo = std::max(0, need - R.produced);
+    if (R.mode == CMP_DECODE_KV && R.keep == 0 && todo > 0)
         for (int b = 0; b < B; b++)
             CMP_REQUIRE(d->pos[b] + todo - 1 < m->W, "decode_batch_steps: row %d: position %d outside the wpe table (window_size %d): "
                         "prompt_len + length - 1 must be <= window_size in kv-cache mode", b, d->pos[b] + todo - 1, m->W);
-    while (d->produced < need) {
-        if (d->keep > 0) {
+    while (R.produced < need) {
+        if (R.keep > 0) {
             // rows whose cache is full draw this step's id from a re-encode of their tail; they sit out the replay, which
             // still runs all B rows (one capture per B).  When every row slides there is nothing to replay.
             DecRowList rl = {};
@@ -846,47 +537,45 @@ extern "C" int cmp_decode_batch_steps(cmp_model* m, int n, int32_t* ids_out) {
                 if (d->pos[b] >= m->W) rl.row[nb++] = (unsigned char)b;
             if (nb > 0) {
                 if (nb < B) {
-                    decb_hold_kernel<<<1, DECB_MAX_ROWS, 0, s>>>(d->st, rl, nb);
+                    decb_hold_kernel<<<1, DECB_MAX_ROWS, 0, s>>>(R.st, rl, nb);
                     KERNEL_CHECK();
                     if (ex) HIP_CHECK(hipGraphLaunch(ex, s));
                     else CHECK_RC(enqueue_batch_step(m, d, B));
                 }
-                CHECK_RC(enqueue_batch_slide(m, d, rl, nb));
+                CHECK_RC(dec_enqueue_slide(m, R, d->w, rl, nb));
                 for (int b = 0; b < B; b++) d->pos[b]++;
-                for (int i = 0; i < nb; i++) d->pos[rl.row[i]] = d->keep;
-                d->produced++;
+                for (int i = 0; i < nb; i++) d->pos[rl.row[i]] = R.keep;
+                R.produced++;
                 continue;
             }
         }
         if (ex) HIP_CHECK(hipGraphLaunch(ex, s));
         else CHECK_RC(enqueue_batch_step(m, d, B));
-        d->produced++;
-        if (d->mode == CMP_DECODE_KV)
+        R.produced++;
+        if (R.mode == CMP_DECODE_KV)
             for (int b = 0; b < B; b++) d->pos[b]++;
     }
     if (n > 0)
-        HIP_CHECK(hipMemcpy2DAsync(ids_out, (size_t)n * 4, d->ids + d->returned, (size_t)d->cap * 4, (size_t)n * 4, B,
+        HIP_CHECK(hipMemcpy2DAsync(ids_out, (size_t)n * 4, R.ids + R.returned, (size_t)R.cap * 4, (size_t)n * 4, B,
                                    hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    d->returned = need;
+    R.returned = need;
     return CMP_OK;
 }
 
-// The logits the most recent per-token step drew every row's id from (d->logits [B][ldz], padding stripped): host fp32 [B][V].
+// The logits the most recent per-token step drew every row's id from (R.logits [B][ldz], padding stripped): host fp32 [B][V].
 // Read-only, outside the per-token chain; nothing to read before the first step has run (the first ids come from the prefills).
 extern "C" int cmp_decode_batch_logits_get(cmp_model* m, float* host_out) {
     CMP_REQUIRE(m && host_out, "decode_batch_logits_get: null argument");
     DecodeBatchState* d = m->decb;
-    if (!d || !d->begun) {
-        cmp_set_error("decode_batch_logits_get: call cmp_decode_batch_begin first");
-        return CMP_ERR_STATE;
-    }
-    if (d->produced < 2) {
+    CHECK_RC(dec_require_begun("decode_batch_logits_get", d && d->rows.begun, "cmp_decode_batch_begin"));
+    const DecRows& R = d->rows;
+    if (R.produced < 2) {
         cmp_set_error("decode_batch_logits_get: no per-token step has run yet (the first ids are drawn from the prefills' logits)");
         return CMP_ERR_STATE;
     }
     HIP_CHECK(hipSetDevice(m->ctx->device));
     HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
-    HIP_CHECK(hipMemcpy2D(host_out, (size_t)m->V * 4, d->logits, (size_t)m->ldz * 4, (size_t)m->V * 4, d->B, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy2D(host_out, (size_t)m->V * 4, R.logits, (size_t)m->ldz * 4, (size_t)m->V * 4, R.B, hipMemcpyDeviceToHost));
     return CMP_OK;
 }

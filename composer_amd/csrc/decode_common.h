@@ -1,6 +1,8 @@
-// decode_common.h -- device helpers shared by the batch-1 decode chain (decode.hip) and the batched one (decode_batch.hip):
-// the wave reductions, the split-key attention record layout and the sampler.  Both chains draw their ids through the same
-// sample_block, so a batched row and a batch-1 decode see the same arithmetic for the same logits.
+// decode_common.h -- what the batch-1 decode chain (decode.hip) and the batched one (decode_batch.hip) share.  Device side: the
+// wave reductions, the split-key attention record layout and the sampler -- both chains draw their ids through the same
+// sample_block, so a batched row and a batch-1 decode see the same arithmetic for the same logits.  Host side (at the end): the
+// per-row loop state, the row buffers and the transposed weights of a chain, and everything AROUND the per-token chains -- the
+// prefill of one row, the slide, the begin-time checks, the graph capture -- written once (decode.hip) for both.
 #pragma once
 #include "model.h"
 
@@ -60,7 +62,7 @@ __device__ __forceinline__ int block_argmax(float best, int arg, float* bv, int*
 }
 
 // ---- event grammar (composer_hip.h, "event-grammar decoding") ----------------------------------------------------------------
-// The per-row state of the grammar beside the sampling parameters in DecState / DecRow: the caller's id layout, the rule bits and
+// The per-row state of the grammar beside the sampling parameters in DecRow: the caller's id layout, the rule bits and
 // the fold of prompt ++ ids so far.  `layout` = 0: no layout was given (no dynamic rule, the state never moves); `active` = 0: no
 // rule and no static bit -- the kernels that draw then call today's sampler and nothing else.
 struct DecGrammar {
@@ -381,3 +383,116 @@ static inline hipError_t grammar_upload(const DecGrammarCfg& c, int V, unsigned*
     if (c.words.empty()) return hipMemsetAsync(banw, 0, bytes, s);
     return hipMemcpyAsync(banw, c.words.data(), bytes, hipMemcpyHostToDevice, s);
 }
+
+// ---- the state of a chain ----------------------------------------------------------------------------------------------------
+#define DECB_MAX_ROWS 256
+
+struct DecRow {          // device-resident per-row loop state (the captured chain does not depend on it); the batch-1 chain has one
+    int pos;             // position id of the token about to be consumed (first member: all the batch-1 attention reads)
+    int token;           // that token
+    int produced;        // ids written to this row's slot of ids[]
+    int advance;         // 1: kv mode (pos += 1 per step), 0: literal (pos stays 0)
+    unsigned rng;        // sampling counter
+    unsigned seed;       // (uint32)(seed + b).  Temperature and seed live here (not in kernel arguments) so that the captured
+    float temperature;   // per-token graph does not depend on them and survives from one begin to the next.  <= 0: greedy
+    int hold;            // sliding-window mode, batched chain: 1 while the row sits out a replay (its cache is full, pos == W):
+                         // attention neither appends nor reads, the sampler leaves the row alone; the row's slide, run after the
+                         // replay, clears it.  Always 0 on the batch-1 chain, whose kernels do not read it
+    int top_k;           // truncated sampling, per row: 0 or >= V: off
+    float top_p;         // 1: off
+    DecGrammar gr;       // event grammar: layout, rules and the fold of the row's prompt ++ ids so far
+};
+
+struct DecRowList {      // rows of one slide, by value in the kernel arguments: no host buffer has to outlive an enqueued step
+    unsigned char row[DECB_MAX_ROWS];
+};
+
+struct DecLayerW { float *attn_wT, *proj_wT, *fc_wT, *pr_wT; };     // fp32, transposed to [N][K]
+
+// The transposed weights a chain's GEMVs / projections read, and its static grammar bans: independent of the batch size, so their
+// addresses outlive every captured chain.  Each chain has its OWN instance: a chain in mid-decode keeps the weights its begin saw
+// when a parameter is set and the other chain then begins.
+struct DecWeights {
+    std::vector<DecLayerW> lw;
+    unsigned* banw = nullptr;           // static bans of the event grammar, ceil(V / 32) words shared by all rows (zero: none)
+    int64_t version = -1;               // cmp_model::param_version the transposes were made from
+    std::vector<void*> allocs;
+};
+
+// Everything indexed by row, for capB rows (the batch-1 chain: one), and how far the rows have got (the same for every row).
+struct DecRows {
+    int capB = 0;                       // rows the buffers and caches hold
+    int cap = 1 << 16;                  // ids per row
+    DecRow* st = nullptr;
+    int32_t* ids = nullptr;             // [capB][cap]
+    float *x = nullptr, *u = nullptr, *qkv = nullptr, *att = nullptr, *r = nullptr, *g = nullptr, *logits = nullptr;
+    // sliding-window mode: every row's prompt and its length stay on the device beside its ids, so that the tail a slide
+    // re-encodes is gathered without a host round trip
+    int32_t* prompts = nullptr;         // [capB][W]
+    int32_t* plen = nullptr;            // [capB]
+    std::vector<float*> kc, vc;         // per layer, [capB] x K [H][D/4][W][4], V [H][W][D]
+    std::vector<void*> allocs;          // sized by capB (replaced when a larger B is asked for)
+    int B = 0, mode = 0;
+    int keep = 0;                       // 0: plain kv / literal decode
+    int produced = 0, returned = 0;
+    bool begun = false;
+    int64_t row_slides = 0, fwd_calls = 0;
+};
+
+struct DecodeState {                    // the batch-1 chain (decode.hip)
+    DecWeights w;
+    DecRows rows;                       // one row
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    int pos = 0;                        // host mirror of the row's position (kv-mode window check; when to slide)
+    bool built = false;                 // buffers allocated, chain captured (reused by later cmp_decode_begin calls)
+    bool graph_on = false;
+};
+
+struct DecodeBatchState {               // the batched chain (decode_batch.hip)
+    DecWeights w;
+    DecRows rows;
+    std::map<int, std::pair<hipGraph_t, hipGraphExec_t>> graphs;     // captured chain per B
+    bool graph_on = true;
+    std::vector<int> pos;               // host mirror of each row's position (kv-mode window check; which rows slide at which step)
+};
+
+template <typename Tp> static int dec_alloc(std::vector<void*>& list, Tp** p, size_t bytes) {
+    void* q = nullptr;
+    HIP_CHECK(hipMalloc(&q, bytes ? bytes : 16));
+    list.push_back(q);
+    *p = (Tp*)q;
+    return CMP_OK;
+}
+
+// `enqueue` captured on the stream into a graph and instantiated; no graph is left behind when either step fails
+template <typename F> static int dec_capture(hipStream_t s, F&& enqueue, hipGraph_t* graph, hipGraphExec_t* exec) {
+    HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue();
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(s, &g);
+    if (rc != CMP_OK) { if (g) hipGraphDestroy(g); return rc; }
+    HIP_CHECK(e);
+    hipGraphExec_t ex = nullptr;
+    e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+    if (e != hipSuccess) hipGraphDestroy(g);
+    HIP_CHECK(e);
+    *graph = g;
+    *exec = ex;
+    return CMP_OK;
+}
+
+// decode.hip, for both chains.  `who`: the caller's name as its refusals print it
+bool dec_graph_enabled();                                                        // COMPOSER_NO_GRAPH=1: off
+int dec_check_prompt(const char* who, int row, const int32_t* ids, int P, int V, int W);      // row < 0: the batch-1 chain's wording
+int dec_check_keep(const char* who, int keep, int W);
+int dec_require_begun(const char* who, bool begun, const char* begin_fn);
+int dec_weights_refresh(cmp_model* m, DecWeights& w);       // allocated on first use; transposed again when a parameter has changed
+void dec_rows_free(DecRows& R);
+int dec_rows_alloc(cmp_model* m, DecRows& R, int B);
+DecRow dec_row_init(int mode, int P, unsigned seed, float temperature, int top_k, float top_p, const DecGrammarCfg& c,
+                    const int32_t* prompt);
+int dec_prefill_row(cmp_model* m, DecRows& R, const DecWeights& w, int b, const int32_t* prompt, int P);
+int dec_enqueue_slide(cmp_model* m, DecRows& R, const DecWeights& w, const DecRowList& rl, int nb);
+// decode_batch.hip: decb_sample_kernel for rows row0 .. row0 + nrows - 1 from `logits` (one row each, stride ldz)
+int decb_launch_sample(cmp_model* m, DecRows& R, const DecWeights& w, const float* logits, int nrows, int row0, int first);

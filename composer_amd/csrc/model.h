@@ -268,9 +268,6 @@ int grad_clip_finish_run(void* stream, const double* slots, int nslots, float gs
 // model.hip
 int ensure_workspace(cmp_model* m, int B, int T);
 int model_forward(cmp_model* m, const int32_t* x_dev, int B, int T, bool training, int64_t step, int past_len = 0);
-// decode.hip
+// decode.hip, decode_batch.hip (what the two chains share: decode_common.h)
 void decode_state_free(DecodeState* d);
-// decode_batch.hip
 void decode_batch_state_free(DecodeBatchState* d);
-int decode_batch_slide_stats(DecodeBatchState* d, int64_t* row_slides, int64_t* forward_calls);
-int decode_batch_grammar_state(cmp_model* m, int row, uint32_t sounding[4], int32_t* pedal, int64_t* time_steps);

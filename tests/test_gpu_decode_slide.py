@@ -18,7 +18,8 @@ left from before the slide, or the token after a slide at position keep +- 1 eac
 Cases: head sizes 16 / 32 / 64 / 128, use_layer_norm = False, the padded head (E 96 / H 4), one bf16 model; keep 1, 37, W // 2,
 W - 1 spread over them; both chains; the graph and COMPOSER_NO_GRAPH=1; a ragged batch of 37 (22 rows sliding in one step,
 a row with P = W, a row whose first tail reaches back into its prompt) bitwise against batches of one and against a workspace
-that holds one row per forward call; the benchmark's geometry (E 512 / H 8 / L 6 / W 2048, keep 1024).
+that holds one row per forward call; the benchmark's geometry (E 512 / H 8 / L 6 / W 2048, keep 1024); a batch-1 decode with a
+grammar, interrupted between two cmp_decode_steps calls by a batched decode and a forward pass, that goes on id for id.
 
 Measured err / floor (max |z_hip - z64| over max |z32 - z64|; floors 4e-7 .. 3.5e-6 at max |z| 2.3 .. 8.6), MI355X, batch-1 chain /
 batched chain (B = 5), 3 or more slides of some row in every case; the worst logit row is a slide step's in all but two cases:
@@ -407,6 +408,52 @@ def test_generate_goes_on_past_the_window_and_steps_n_equals_n_steps_of_one():
     _lib.check(m._lib.cmp_decode_begin_slide(m._h, np.ascontiguousarray(p).ctypes.data_as(C.c_void_p), len(p), keep, 1.0, 4))
     big = np.zeros(65537, np.int32)
     assert m._lib.cmp_decode_steps(m._h, 65537, big.ctypes.data_as(C.c_void_p)) != 0
+    m.close()
+
+
+@pytest.mark.gpu
+def test_the_batch1_chain_survives_a_batched_decode_between_its_steps():
+    """tests/test_gpu_decode_batch.py::test_state_isolation_and_continuation in the other direction.  Both chains prefill, slide and
+    read back through the same functions, each on its own state: a batch-1 kv-slide decode with a grammar, interrupted by a batched
+    kv-slide decode with another grammar and by a forward pass, goes on as if nothing had run in between -- ids, grammar state
+    and slide counters.  Integer equality throughout."""
+    from composer_amd import _lib, grammar as G
+    name = "d32"
+    W, keep = GEOMS[name][3], GEOMS[name][7]
+    n_ids, cut = 130, 60
+    m = make_model(name, make_params(name), max_batch=4)
+    lib, h = m._lib, m._h
+    p = np.ascontiguousarray(make_prompts(name, 1)[0][:10])
+    gram, bans = G.EventGrammar(V, 0, 128, 288, 100, 388, 389, rules=G.ALL), [3, 140, 300, 301]
+    other, other_bans = G.EventGrammar(V, 128, 0, 256, 120, rules=G.NOTE_ON_SILENT), [7, 290]
+    slides = count_slides(10, n_ids, W, keep)
+    assert slides >= 1 and count_slides(10, cut, W, keep) == 0       # the cache fills after W - 10 ids: the cut lies before it
+
+    def begin():
+        m._set_decode_grammar(0, gram, bans)
+        _lib.check(lib.cmp_decode_begin_slide(h, p.ctypes.data_as(C.c_void_p), len(p), keep, 1.0, 4), "begin_slide")
+
+    def steps(n):
+        out = np.empty(n, np.int32)
+        _lib.check(lib.cmp_decode_steps(h, n, out.ctypes.data_as(C.c_void_p)), "steps")
+        return out
+
+    begin()
+    ref = steps(n_ids)
+    begin()
+    a = steps(cut)
+    ragged = [r[:q] for r, q in zip(make_prompts(name, 3), (60, 50, 7))]
+    ob = m.generate_batch(ragged, 2 * W, temperature=1.0, mode="kv-slide", slide_keep=keep, seed=9, grammar=other,
+                          banned_ids=other_bans)                     # the batched chain in between, with its own grammar
+    assert m.decode_slide_stats(batched=True)[0] == sum(count_slides(len(q), 2 * W, W, keep) for q in ragged)
+    m(np.asarray(ragged[2], np.int32)[None])                         # and a forward pass
+    b = steps(n_ids - cut)
+    ids = np.concatenate([a, b])
+    assert ids.tolist() == ref.tolist()
+    assert not set(ids.tolist()) & set(bans)
+    assert m.decode_grammar_state(batched=False) == gram.fold(p.tolist() + ids.tolist())
+    assert m.decode_grammar_state(batched=True, row=2) == other.fold(ragged[2].tolist() + ob[2].tolist())
+    assert m.decode_slide_stats() == (slides,) * 2
     m.close()
 
 
