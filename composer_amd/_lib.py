@@ -46,6 +46,13 @@ class GemmPlanInfo(C.Structure):
                                          "sched", "empty")]
 
 
+class AttnPlanInfo(C.Structure):
+    """cmp_attn_plan_info: the attention launcher's decision for one launch record (host only; tests/test_attn_plan_host.py)."""
+    _fields_ = [("form", C.c_int32), ("drop", C.c_int32), ("nlaunch", C.c_int32), ("grid_x", C.c_int32 * 2), ("grid_y", C.c_int32 * 2),
+                ("block", C.c_int32), ("smem", C.c_int64 * 2), ("optin", C.c_int32), ("plan_u", C.c_int32), ("bias_fused", C.c_int32),
+                ("bias_pass", C.c_int32), ("cls", C.c_int32 * 2), ("work", C.c_double * 2), ("bytes", C.c_double * 2), ("empty", C.c_int32)]
+
+
 _P = C.c_void_p
 _i, _f, _i64, _u64, _u32 = C.c_int, C.c_float, C.c_int64, C.c_uint64, C.c_uint32
 
@@ -149,6 +156,8 @@ SIGNATURES = {
     "cmp_k_attn_fwd": (_i, [_P, _P, _P, _P, _i, _i, _i, _i, _i, _i, _f, _u64, _u32]),
     "cmp_attn_bwd_bias_next": (_i, [_P]),
     "cmp_k_attn_bwd": (_i, [_P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _i, _f, _u64, _u32]),
+    "cmp_attn_plan": (_i, [_i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, C.POINTER(AttnPlanInfo)]),
+    "cmp_attn_caps": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "cmp_k_softmax_xent": (_i, [_P, _P, _i, _P, _P, _P, _P, _i, _i, _f, _i]),
     "cmp_k_adam": (_i, [_P, _P, _P, _P, _P, _P, _i64, _f, _f, _f, _f, _i64, _f]),
     "cmp_k_adam_dev": (_i, [_P, _P, _P, _P, _P, _P, _i64, _f, _f, _f, _f, _i64, _P]),
@@ -160,7 +169,8 @@ SIGNATURES = {
 # timing (tools/ab_step.py) may lack them; the package's own library must export every symbol
 _ADDED_LATER = {"cmp_gemm_ln_scale_next", "cmp_attn_bwd_ln_next", "cmp_k_layernorm_bwd_prescaled", "cmp_k_wgrad_ln_fix", "cmp_k_ln_stats_merge", "cmp_dp_rccl_version", "cmp_dp_allreduce_pattern", "cmp_dp_init_exchange", "cmp_train_step_graph_probe", "cmp_train_step_launches", "cmp_k_embed_fwd_stats", "cmp_k_ln_fold_prep", "cmp_gemm_ln_next", "cmp_k_layernorm_bwd_parts", "cmp_model_path_info", "cmp_forward_ex", "cmp_hidden_get_at", "cmp_dp_stats", "cmp_prof_end2", "cmp_prof_pause", "cmp_prof_resume", "cmp_k_wgrad_group", "cmp_k_embed_bwd_v", "cmp_decode_batch_begin", "cmp_decode_batch_steps", "cmp_k_sample_rows", "cmp_decode_logits_get", "cmp_decode_batch_logits_get", "cmp_k_sample_ex", "cmp_k_sample_rows_ex", "cmp_decode_begin_ex", "cmp_decode_batch_begin_ex", "cmp_train_options",
                 "cmp_train_options_get", "cmp_train_grad_stats", "cmp_train_metrics_wait_ex", "cmp_k_adam_dev", "cmp_k_grad_clip_ws", "cmp_k_grad_clip",
-                "cmp_decode_grammar", "cmp_decode_grammar_state", "cmp_k_sample_banned", "cmp_score", "cmp_k_score_rows", "cmp_gemm_plan"}
+                "cmp_decode_grammar", "cmp_decode_grammar_state", "cmp_k_sample_banned", "cmp_score", "cmp_k_score_rows", "cmp_gemm_plan",
+                "cmp_attn_plan", "cmp_attn_caps"}
 
 _lib = None
 

@@ -1177,59 +1177,37 @@ __global__ __launch_bounds__(256, 2) void attn_dkv_ks_kernel(const T* __restrict
 }
 
 // =================================================================================================
-// host launchers
+// host launchers.  What a launch becomes is decided in attn_plan.h (attn_plan_fwd / attn_plan_bwd); the code below asks the
+// device the facts the plan needs, refuses before anything is enqueued and launches what the plan names.
 // =================================================================================================
 int colsum_run(void* stream, const void* X, int ldx, float* out, int rows, int cols, int dtype, float* det_ws, size_t det_ws_bytes);   // elementwise.hip
-// grid.x: block pairs, or single blocks when the paired grid would leave most of the 256 CUs x 2-3 workgroups without work
-static int attn_grid_x(int Tn, int BH) {
-    const int nb = cdiv(Tn, 128), pairs = (nb + 1) / 2;
-    return (nb > 1 && (int64_t)pairs * BH < 512) ? nb : pairs;
-}
-// The block plan of a forward / dQ launch (attn_job): how many (batch, head) rows per XCD run as single blocks behind the paired
-// ones.  An XCD's workgroups start in order on 32 CUs x wgs_per_cu slots; the paired rows fill whole rounds of those slots and
-// the rows of the last, partial round go unpaired (with less than one round of pairs: three quarters of the rows).  Measured
-// (tools/ubench/attn_plan_probe.py, outputs bit-identical): B*H = 256: forward 73.6 -> 68.7 us, dQ 87.8 -> 82.0; 512: 140 -> 131,
-// 171 -> 154; 1024: 286 -> 281, 321 -> 314; 128: 42 -> 38, 50 -> 46.  (A list-scheduling model of the launch predicted three times
-// these gains: workgroups of a partly filled round run faster, the slots are not independent machines.)
-// -1 = the plain 2-D grid (B*H not a multiple of 8, a single block, few rows, or the pairs already fill whole rounds).
-static int attn_plan_u(int Tn, int BH, int wgs_per_cu) {
-    const int nb = cdiv(Tn, 128), pairs = (nb + 1) / 2;
-    if (nb < 2 || (BH & 7) || (int64_t)pairs * BH < 512 || wgs_per_cu < 1) return -1;
-    const int rows_x = BH / 8, slots = 32 * wgs_per_cu;
-    const int rounds = rows_x * pairs / slots;
-    const int paired_rows = rounds > 0 ? rounds * slots / pairs : rows_x / 4;
-    const int u = rows_x - paired_rows;
-    return u > 0 ? u : -1;
-}
-static dim3 attn_plan_grid(int Tn, int BH, int u) {
-    if (u < 0) return dim3(attn_grid_x(Tn, BH), BH);
-    const int nb = cdiv(Tn, 128), pairs = (nb + 1) / 2, rows_x = BH / 8;
-    return dim3(8 * ((rows_x - u) * pairs + u * nb), 1);
-}
-// Small grids (the reference's default configuration at batch 1: 16 (batch, head) rows of 1024 tokens = 128 workgroups of the
-// 128-row kind, every one a serial walk over up to 16 key tiles at ~1 us each): the key-split forms of the three kernels (KS).
-// COMPOSER_ATTN_KS=0 turns them off, =1 forces them wherever they exist (tests).
-static bool attn_key_split(int Tn, int BH, int D, bool bf16) {
-    if (!bf16 || D > 32 || Tn < 64) return false;       // (at D = 64 the 256-row staging registers spill: not built)
-    static const int mode = [] { const char* e = getenv("COMPOSER_ATTN_KS"); return e ? atoi(e) : -1; }();
-    if (mode == 0) return false;
-    if (mode == 1) return true;
-    // one round of 512 key-split workgroups (two per CU); with twice the rows the split already loses (default model at batch 2:
-    // 2.17 vs 2.01 ms/step, tools/ks_threshold_probe.py)
-    return (int64_t)cdiv(Tn, 128) * BH <= 128;
+
+#define ATTN_GEO_IS(D) (attn_lds_stride(true, D) == Geo<bf16_t, D>::S && attn_lds_stride(false, D) == Geo<float, D>::S)
+static_assert(ATTN_GEO_IS(16) && ATTN_GEO_IS(32) && ATTN_GEO_IS(64) && ATTN_GEO_IS(128), "attn_plan.h restates Geo<T, D>::S");
+
+// COMPOSER_ATTN_KS=0 turns the key-split kernels off, =1 forces them wherever they exist (tests); COMPOSER_ATTN_BIAS_PASS=<MiB>
+// moves the bound of the bias column-sum pass, 0 = never.  Both read once per process.
+static AttnEnv attn_env() {
+    static const AttnEnv env = [] {
+        AttnEnv e;
+        if (const char* v = getenv("COMPOSER_ATTN_KS")) e.ks_mode = atoi(v);
+        if (const char* v = getenv("COMPOSER_ATTN_BIAS_PASS")) e.bias_pass_mib = atoi(v);
+        return e;
+    }();
+    return env;
 }
 template <typename K> static int attn_wgs_per_cu(K kernel, size_t smem) {
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, smem) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return n;
 }
+#define ATTN_OPTIN(kernel, bytes) HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)))
 // LDS opt-in of the key-split kernels (4 * 256 staged rows), decided once per (type, head size) for all of them together: a device
 // or driver that refuses it keeps the 128-row kernels, forward and backward alike (the GEMM ring falls back to its two-stage loop
 // in the same situation) instead of failing every small-grid attention call.
-template <typename T, int D> static size_t attn_ks_smem() { return 4 * 256 * Geo<T, D>::S * sizeof(T); }
 template <typename T, int D> static bool attn_ks_available() {
     static const bool ok = [] {
-        const int ks = (int)attn_ks_smem<T, D>(), kv = ks / 2 + 3 * 256 * (int)sizeof(float);
+        const int ks = (int)attn_ks_smem(true, D), kv = (int)attn_ks_kv_smem(true, D);
         const void* big[] = {(const void*)attn_fwd_kernel<T, D, true, false, true>, (const void*)attn_fwd_kernel<T, D, false, false, true>,
                              (const void*)attn_bwd_ks_kernel<T, D, true>, (const void*)attn_bwd_ks_kernel<T, D, false>,
                              (const void*)attn_dq_ks_kernel<T, D, true>, (const void*)attn_dq_ks_kernel<T, D, false>};
@@ -1242,175 +1220,169 @@ template <typename T, int D> static bool attn_ks_available() {
     }();
     return ok;
 }
-template <typename T, int D>
-static int launch_fwd(hipStream_t s, const void* qkv, void* o, float* lse, int B, int Tn, int H, float scale, DropCfg d,
-                      const float* amask) {
-    if constexpr (std::is_same<T, bf16_t>::value && D <= 32) {
-        const size_t smem_ks = attn_ks_smem<T, D>();
-        if (!amask && attn_ks_available<T, D>() && attn_key_split(Tn, B * H, D, true)) {
-            const dim3 grid(cdiv(Tn, 32), B * H);
-            PROF_START(3, s);
-            if (d.thr) attn_fwd_kernel<T, D, true, false, true><<<grid, 256, smem_ks, s>>>((const T*)qkv, (T*)o, lse, Tn, H, scale, d, -1, nullptr);
-            else attn_fwd_kernel<T, D, false, false, true><<<grid, 256, smem_ks, s>>>((const T*)qkv, (T*)o, lse, Tn, H, scale, d, -1, nullptr);
-            PROF_STOP(3, s, 2.0 * B * H * (double)Tn * Tn * D, (double)B * Tn * H * (4.0 * D * sizeof(T) + 4.0));
-            KERNEL_CHECK();
-            return CMP_OK;
+// The device facts of the 128-row kernels (KERNEL: CMP_ATTN_K_*): resident workgroups per CU of the kernel the block plan is for,
+// asked once per (kernel, type, head size).  An image above 64 KiB needs its opt-in before the occupancy can be asked, so the opt-in
+// of that kernel set stays here, ahead of the query, on every launch.
+template <typename T, int D, int KERNEL> static int attn_rows_caps(AttnCaps* c) {
+    constexpr size_t smem = attn_rows_smem(std::is_same<T, bf16_t>::value, D);
+    if constexpr (KERNEL == CMP_ATTN_K_FWD) {
+        if (attn_fwd_optin(smem)) {
+            ATTN_OPTIN((attn_fwd_kernel<T, D, true>), smem);
+            ATTN_OPTIN((attn_fwd_kernel<T, D, false>), smem);
         }
-    }
-    size_t smem = 4 * 64 * Geo<T, D>::S * sizeof(T);
-    if (smem > 65536) {
-        HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<T, D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<T, D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    }
-    static const int wgs_per_cu = attn_wgs_per_cu(attn_fwd_kernel<T, D, true>, smem);
-    const int plan_u = attn_plan_u(Tn, B * H, wgs_per_cu);
-    const dim3 grid = attn_plan_grid(Tn, B * H, plan_u);
-    const double flops = 2.0 * B * H * (double)Tn * Tn * D;      // QK^T + PV on the unmasked half
-    if (amask) {      // Transformer.call(attention_mask=...): the instances that add the per-key mask term
-        if (smem > 65536) {
-            HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<T, D, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<T, D, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        static const int wgs_per_cu = attn_wgs_per_cu(attn_fwd_kernel<T, D, true>, smem);
+        c->wgs_per_cu = wgs_per_cu;
+    } else if constexpr (KERNEL == CMP_ATTN_K_DQ_LN) {
+        if (attn_bwd_optin(smem)) {
+            ATTN_OPTIN((attn_dq_ln_kernel<T, D, true>), smem);
+            ATTN_OPTIN((attn_dq_ln_kernel<T, D, false>), smem);
+            ATTN_OPTIN((attn_dkv_ln_kernel<T, D, true>), smem + ATTN_DKV_EXTRA);
+            ATTN_OPTIN((attn_dkv_ln_kernel<T, D, false>), smem + ATTN_DKV_EXTRA);
         }
-        if (d.thr) attn_fwd_kernel<T, D, true, true><<<grid, 256, smem, s>>>((const T*)qkv, (T*)o, lse, Tn, H, scale, d, plan_u, amask);
-        else attn_fwd_kernel<T, D, false, true><<<grid, 256, smem, s>>>((const T*)qkv, (T*)o, lse, Tn, H, scale, d, plan_u, amask);
-        KERNEL_CHECK();
-        return CMP_OK;
+        static const int wgs_per_cu_ln = attn_wgs_per_cu(attn_dq_ln_kernel<T, D, true>, smem);
+        c->wgs_per_cu = wgs_per_cu_ln;
+    } else {
+        if (attn_bwd_optin(smem)) {
+            ATTN_OPTIN((attn_dq_kernel<T, D, true>), smem);
+            ATTN_OPTIN((attn_dq_kernel<T, D, false>), smem);
+            ATTN_OPTIN((attn_dkv_kernel<T, D, true>), smem + ATTN_DKV_EXTRA);
+            ATTN_OPTIN((attn_dkv_kernel<T, D, false>), smem + ATTN_DKV_EXTRA);
+        }
+        static const int wgs_per_cu = attn_wgs_per_cu(attn_dq_kernel<T, D, true>, smem);
+        c->wgs_per_cu = wgs_per_cu;
     }
-    PROF_START(3, s);
-    if (d.thr) attn_fwd_kernel<T, D, true><<<grid, 256, smem, s>>>((const T*)qkv, (T*)o, lse, Tn, H, scale, d, plan_u, nullptr);
-    else attn_fwd_kernel<T, D, false><<<grid, 256, smem, s>>>((const T*)qkv, (T*)o, lse, Tn, H, scale, d, plan_u, nullptr);
-    PROF_STOP(3, s, flops, (double)B * Tn * H * (4.0 * D * sizeof(T) + 4.0));      // q, k, v in; o, lse out
-    KERNEL_CHECK();
     return CMP_OK;
 }
-template <typename T, int D>
-static int launch_bwd(hipStream_t s, const void* qkv, const void* o, const void* d_o, const float* lse, float* delta,
-                      void* dqkv, int B, int Tn, int H, float scale, DropCfg d, float* bias_grad, AttnLnRows lr) {
-    if constexpr (std::is_same<T, bf16_t>::value) {
-        if (lr.rstd) {
-            // the backward pass of the fused block path (bf16, chip-filling launches): the 128-row kernels with rstd-scaled stores (AttnLnRows)
-            size_t smem = 4 * 64 * Geo<T, D>::S * sizeof(T);
-            if (smem + 1536 > 65536) {
-                HIP_CHECK(hipFuncSetAttribute((const void*)attn_dq_ln_kernel<T, D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                HIP_CHECK(hipFuncSetAttribute((const void*)attn_dq_ln_kernel<T, D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                HIP_CHECK(hipFuncSetAttribute((const void*)attn_dkv_ln_kernel<T, D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem + 1536));
-                HIP_CHECK(hipFuncSetAttribute((const void*)attn_dkv_ln_kernel<T, D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem + 1536));
-            }
-            const double fl = (double)B * H * (double)Tn * Tn * D;
-            static const int wgs_per_cu_ln = attn_wgs_per_cu(attn_dq_ln_kernel<T, D, true>, smem);
-            const int plan_u = attn_plan_u(Tn, B * H, wgs_per_cu_ln);
-            const dim3 qgrid = attn_plan_grid(Tn, B * H, plan_u);
-            const dim3 kgrid(attn_grid_x(Tn, B * H), B * H);
-            PROF_START(4, s);
-            if (d.thr) attn_dq_ln_kernel<T, D, true><<<qgrid, 256, smem, s>>>((const T*)qkv, (const T*)o, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d, plan_u, lr);
-            else attn_dq_ln_kernel<T, D, false><<<qgrid, 256, smem, s>>>((const T*)qkv, (const T*)o, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d, plan_u, lr);
-            PROF_STOP(4, s, 3.0 * fl, (double)B * Tn * H * (6.0 * D * sizeof(T) + 8.0));
-            KERNEL_CHECK();
-            PROF_START(5, s);
-            if (d.thr) attn_dkv_ln_kernel<T, D, true><<<kgrid, 256, smem + 384 * sizeof(float), s>>>((const T*)qkv, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d, lr);
-            else attn_dkv_ln_kernel<T, D, false><<<kgrid, 256, smem + 384 * sizeof(float), s>>>((const T*)qkv, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d, lr);
-            PROF_STOP(5, s, 4.0 * fl, (double)B * Tn * H * (6.0 * D * sizeof(T) + 8.0));
-            KERNEL_CHECK();
+// ... and of one launch: the key-split set first where it is built and the launch may use it; nothing of the 128-row kernels when
+// the launch then takes the key split.
+template <typename T, int D, bool BACKWARD> static int attn_caps(const AttnDesc& d, const AttnEnv& env, AttnCaps* c) {
+    constexpr bool bf = std::is_same<T, bf16_t>::value;
+    if constexpr (BACKWARD && bf) {
+        if (d.ln.rstd) return attn_rows_caps<T, D, CMP_ATTN_K_DQ_LN>(c);
+    }
+    if constexpr (attn_ks_built(bf, D)) {
+        if (BACKWARD || !d.amask) {
+            c->ks_ok = attn_ks_available<T, D>();
+            if (attn_key_split(d.T, d.B * d.H, D, bf, env, c->ks_ok)) return CMP_OK;
+        }
+    }
+    return attn_rows_caps<T, D, BACKWARD ? CMP_ATTN_K_DQ : CMP_ATTN_K_FWD>(c);
+}
+
+// `DROP` inside the statement is the compile-time form of `drop`
+#define DISPATCH_DROP(drop, ...)                                  \
+    if (drop) { constexpr bool DROP = true; __VA_ARGS__; }        \
+    else { constexpr bool DROP = false; __VA_ARGS__; }
+// launch i of plan p on stream s between the timing marks of its class: `grid` and `lds` inside the statement are the plan's
+#define ATTN_LAUNCH(i, ...)                                                    \
+    do {                                                                       \
+        const AttnLaunch& l_ = p.l[i];                                         \
+        const dim3 grid(l_.grid_x, l_.grid_y);                                 \
+        const size_t lds = l_.smem;                                            \
+        if (l_.cls >= 0) PROF_START(l_.cls, s);                                \
+        DISPATCH_DROP(p.drop, __VA_ARGS__)                                     \
+        if (l_.cls >= 0) PROF_STOP(l_.cls, s, l_.work, l_.bytes);              \
+        KERNEL_CHECK();                                                        \
+    } while (0)
+
+template <typename T, int D> static int launch_fwd(hipStream_t s, const AttnDesc& d) {
+    constexpr bool bf = std::is_same<T, bf16_t>::value;
+    const AttnEnv env = attn_env();
+    AttnCaps caps;
+    if (const int rc = attn_caps<T, D, false>(d, env, &caps)) return rc;
+    const AttnPlan p = attn_plan_fwd(d, env, caps);
+    const DropCfg drop = make_drop(d.p_drop, d.seed, d.rng_stream);
+    const T* qkv = (const T*)d.qkv;
+    T* o = (T*)d.o;
+    switch (p.form) {
+        case CMP_ATTN_FWD_KS:
+            if constexpr (attn_ks_built(bf, D))
+                ATTN_LAUNCH(0, attn_fwd_kernel<T, D, DROP, false, true><<<grid, 256, lds, s>>>(qkv, o, d.lse, d.T, d.H, d.scale, drop, -1, nullptr));
             return CMP_OK;
-        }
-    } else {
-        CMP_REQUIRE(!lr.rstd, "attention backward: LayerNorm row scaling exists in bf16 only");
-    }
-    if constexpr (std::is_same<T, bf16_t>::value && D <= 32) {
-        // one launch, both roles: LDS = the larger of the two (dQ double-buffers its 256-key tiles)
-        const size_t smem_ks = attn_ks_smem<T, D>(), smem_kv = smem_ks / 2 + 3 * 256 * sizeof(float);
-        if (attn_ks_available<T, D>() && attn_key_split(Tn, B * H, D, true)) {
-            const double flk = (double)B * H * (double)Tn * Tn * D;
-            // The c_attn bias gradient (column sums of [dQ | dK | dV]) is NOT fused here: a fused sum ends a workgroup on a transpose-reduce
-            // and a device-scope float atomic whose round trip the launch has to wait out -- 16.5 of the 29.4 us of the dK/dV launch (two
-            // sums) and ~8 of dQ's 19 at the default configuration (measurement builds, profiles/r5_06); only a launch of several rounds
-            // hides that tail behind other workgroups.  A column-sum pass over the [tokens, 3E] gradient costs ~5 us at these sizes (63 us
-            // at the benchmark's, where the fused sums stay).
-            float* const bias_out = bias_grad;
-            bias_grad = nullptr;
-            auto bias_pass = [&]() -> int {
-                return bias_out ? colsum_run(s, dqkv, 3 * H * D, bias_out, B * Tn, 3 * H * D, CMP_BF16, nullptr, 0) : CMP_OK;
-            };
-            if ((int64_t)2 * cdiv(Tn, 32) * B * H > 512) {         // not resident at once: two launches
-                const dim3 g1(cdiv(Tn, 32), B * H);
-                PROF_START(4, s);
-                if (d.thr) attn_dq_ks_kernel<T, D, true><<<g1, 256, smem_ks, s>>>((const T*)qkv, (const T*)o, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d);
-                else attn_dq_ks_kernel<T, D, false><<<g1, 256, smem_ks, s>>>((const T*)qkv, (const T*)o, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d);
-                PROF_STOP(4, s, 3.0 * flk, (double)B * Tn * H * (6.0 * D * sizeof(T) + 8.0));
-                KERNEL_CHECK();
-                PROF_START(5, s);
-                if (d.thr) attn_dkv_ks_kernel<T, D, true><<<g1, 256, smem_kv, s>>>((const T*)qkv, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d);
-                else attn_dkv_ks_kernel<T, D, false><<<g1, 256, smem_kv, s>>>((const T*)qkv, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d);
-                PROF_STOP(5, s, 4.0 * flk, (double)B * Tn * H * (6.0 * D * sizeof(T) + 8.0));
-                KERNEL_CHECK();
-                return bias_pass();
+        case CMP_ATTN_FWD_ROWS:
+            ATTN_LAUNCH(0, attn_fwd_kernel<T, D, DROP><<<grid, 256, lds, s>>>(qkv, o, d.lse, d.T, d.H, d.scale, drop, p.plan_u, nullptr));
+            return CMP_OK;
+        default:         // CMP_ATTN_FWD_MASK: the instances with the mask term take their opt-in here (the plain ones: attn_rows_caps)
+            if (p.optin) {
+                ATTN_OPTIN((attn_fwd_kernel<T, D, true, true>), p.l[0].smem);
+                ATTN_OPTIN((attn_fwd_kernel<T, D, false, true>), p.l[0].smem);
             }
-            const dim3 kgrid(2 * cdiv(Tn, 32), B * H);
-            PROF_START(5, s);                  // (counted with the dK/dV class: one launch carries the seven products)
-            if (d.thr) attn_bwd_ks_kernel<T, D, true><<<kgrid, 256, smem_ks, s>>>((const T*)qkv, (const T*)o, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d);
-            else attn_bwd_ks_kernel<T, D, false><<<kgrid, 256, smem_ks, s>>>((const T*)qkv, (const T*)o, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d);
-            PROF_STOP(5, s, 7.0 * flk, (double)B * Tn * H * (9.0 * D * sizeof(T) + 8.0));
-            KERNEL_CHECK();
-            return bias_pass();
-        }
+            ATTN_LAUNCH(0, attn_fwd_kernel<T, D, DROP, true><<<grid, 256, lds, s>>>(qkv, o, d.lse, d.T, d.H, d.scale, drop, p.plan_u, d.amask));
+            return CMP_OK;
     }
-    dim3 grid(attn_grid_x(Tn, B * H), B * H);
-    // Short launches take the c_attn bias sums out of the kernels too (see the key-split branch): the fused float atomics leave a ~16 us
-    // tail that only a launch of several rounds hides.  Same box, [tokens, 3E] gradient of 1.6 ... 12.6 MB (the default model at batch
-    // 1 ... 8): 2.99 -> 2.67 ms/step at batch 8, 1.95 -> 1.76 at batch 2; 25 MB (6L/8H/d512 at batch 8): 3.03 vs 3.04; 100 MB (batch 32):
-    // 7.39 vs 7.43 -- the pass re-reads the gradient, so it stops at 16 MiB (COMPOSER_ATTN_BIAS_PASS=<MiB> overrides, 0 = never).
-    static const int bias_pass_mib = [] { const char* e = getenv("COMPOSER_ATTN_BIAS_PASS"); return e ? atoi(e) : 16; }();
-    float* bias_out = nullptr;
-    if (bias_grad && std::is_same<T, bf16_t>::value && (int64_t)B * Tn * 3 * H * D * 2 <= (int64_t)bias_pass_mib << 20) { bias_out = bias_grad; bias_grad = nullptr; }
-    size_t smem = 4 * 64 * Geo<T, D>::S * sizeof(T);
-    if (smem + 1536 > 65536) {
-        HIP_CHECK(hipFuncSetAttribute((const void*)attn_dq_kernel<T, D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        HIP_CHECK(hipFuncSetAttribute((const void*)attn_dq_kernel<T, D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        HIP_CHECK(hipFuncSetAttribute((const void*)attn_dkv_kernel<T, D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem + 1536));
-        HIP_CHECK(hipFuncSetAttribute((const void*)attn_dkv_kernel<T, D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem + 1536));
+}
+template <typename T, int D> static int launch_bwd(hipStream_t s, const AttnDesc& d) {
+    constexpr bool bf = std::is_same<T, bf16_t>::value;
+    const AttnEnv env = attn_env();
+    AttnCaps caps;
+    if (const int rc = attn_caps<T, D, true>(d, env, &caps)) return rc;
+    const AttnPlan p = attn_plan_bwd(d, env, caps);
+    const DropCfg drop = make_drop(d.p_drop, d.seed, d.rng_stream);
+    const T *qkv = (const T*)d.qkv, *o = (const T*)d.o, *d_o = (const T*)d.d_o;
+    T* dqkv = (T*)d.dqkv;
+    float* const bias = p.bias_fused ? d.bias_grad : nullptr;
+    switch (p.form) {
+        case CMP_ATTN_BWD_LN:
+            if constexpr (bf) {
+                ATTN_LAUNCH(0, attn_dq_ln_kernel<T, D, DROP><<<grid, 256, lds, s>>>(qkv, o, d_o, d.lse, d.delta, dqkv, bias, d.T, d.H, d.scale, drop, p.plan_u, d.ln));
+                ATTN_LAUNCH(1, attn_dkv_ln_kernel<T, D, DROP><<<grid, 256, lds, s>>>(qkv, d_o, d.lse, d.delta, dqkv, bias, d.T, d.H, d.scale, drop, d.ln));
+            }
+            break;
+        case CMP_ATTN_BWD_KS2:         // dK/dV reads the delta the dQ launch stored
+            if constexpr (attn_ks_built(bf, D)) {
+                ATTN_LAUNCH(0, attn_dq_ks_kernel<T, D, DROP><<<grid, 256, lds, s>>>(qkv, o, d_o, d.lse, d.delta, dqkv, bias, d.T, d.H, d.scale, drop));
+                ATTN_LAUNCH(1, attn_dkv_ks_kernel<T, D, DROP><<<grid, 256, lds, s>>>(qkv, d_o, d.lse, d.delta, dqkv, bias, d.T, d.H, d.scale, drop));
+            }
+            break;
+        case CMP_ATTN_BWD_KS1:
+            if constexpr (attn_ks_built(bf, D))
+                ATTN_LAUNCH(0, attn_bwd_ks_kernel<T, D, DROP><<<grid, 256, lds, s>>>(qkv, o, d_o, d.lse, d.delta, dqkv, bias, d.T, d.H, d.scale, drop));
+            break;
+        default:
+            ATTN_LAUNCH(0, attn_dq_kernel<T, D, DROP><<<grid, 256, lds, s>>>(qkv, o, d_o, d.lse, d.delta, dqkv, bias, d.T, d.H, d.scale, drop, p.plan_u));
+            ATTN_LAUNCH(1, attn_dkv_kernel<T, D, DROP><<<grid, 256, lds, s>>>(qkv, d_o, d.lse, d.delta, dqkv, bias, d.T, d.H, d.scale, drop));
+            break;
     }
-    const double fl = (double)B * H * (double)Tn * Tn * D;        // one product over the unmasked half
-    PROF_START(4, s);
-    static const int wgs_per_cu = attn_wgs_per_cu(attn_dq_kernel<T, D, true>, smem);
-    const int plan_u = attn_plan_u(Tn, B * H, wgs_per_cu);
-    const dim3 qgrid = attn_plan_grid(Tn, B * H, plan_u);
-    if (d.thr) attn_dq_kernel<T, D, true><<<qgrid, 256, smem, s>>>((const T*)qkv, (const T*)o, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d, plan_u);
-    else attn_dq_kernel<T, D, false><<<qgrid, 256, smem, s>>>((const T*)qkv, (const T*)o, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d, plan_u);
-    PROF_STOP(4, s, 3.0 * fl, (double)B * Tn * H * (6.0 * D * sizeof(T) + 8.0));       // q, k, v, o, dO, lse in; dQ, delta out
-    KERNEL_CHECK();
-    PROF_START(5, s);
-    if (d.thr) attn_dkv_kernel<T, D, true><<<grid, 256, smem + 384 * sizeof(float), s>>>((const T*)qkv, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d);
-    else attn_dkv_kernel<T, D, false><<<grid, 256, smem + 384 * sizeof(float), s>>>((const T*)qkv, (const T*)d_o, lse, delta, (T*)dqkv, bias_grad, Tn, H, scale, d);
-    PROF_STOP(5, s, 4.0 * fl, (double)B * Tn * H * (6.0 * D * sizeof(T) + 8.0));       // q, k, v, dO, lse, delta in; dK, dV out
-    KERNEL_CHECK();
-    if (bias_out) return colsum_run(s, dqkv, 3 * H * D, bias_out, B * Tn, 3 * H * D, CMP_BF16, nullptr, 0);
+    if (p.bias_pass) return colsum_run(s, d.dqkv, 3 * d.H * d.D, d.bias_grad, d.B * d.T, 3 * d.H * d.D, CMP_BF16, nullptr, 0);
     return CMP_OK;
 }
 
 #define DISPATCH_D(T, fn, ...)                                                         \
-    switch (D) {                                                                       \
+    switch (d.D) {                                                                     \
         case 16: return fn<T, 16>(__VA_ARGS__);                                        \
         case 32: return fn<T, 32>(__VA_ARGS__);                                        \
         case 64: return fn<T, 64>(__VA_ARGS__);                                        \
         case 128: return fn<T, 128>(__VA_ARGS__);                                      \
-        default: cmp_set_error("attention: head size %d unsupported (16/32/64/128)", D); \
-                 return CMP_ERR_INVALID;                                               \
     }
+// refusals and the empty launch (attn_plan_check) come before the first question to the device; then the kernels of (dtype, D)
+#define ATTN_RUN(backward, fn, ...)                                                    \
+    do {                                                                               \
+        const AttnPlan chk = attn_plan_check(d, backward);                             \
+        if (chk.status != CMP_OK) {                                                    \
+            cmp_set_error("%s", chk.msg);                                              \
+            return chk.status;                                                         \
+        }                                                                              \
+        if (chk.empty) return CMP_OK;                                                  \
+        if (d.dtype == CMP_BF16) { DISPATCH_D(bf16_t, fn, __VA_ARGS__) }               \
+        else { DISPATCH_D(float, fn, __VA_ARGS__) }                                    \
+        return CMP_ERR_INVALID;       /* (not reached: every other head size was refused) */ \
+    } while (0)
 
+int attn_fwd_run(void* stream, const AttnDesc& d) { ATTN_RUN(false, launch_fwd, (hipStream_t)stream, d); }
+
+// the C ABI's positional arguments as a launch record
+static AttnDesc attn_abi_desc(int dtype, int B, int T, int H, int D, int scale, float p_drop, uint64_t seed, uint32_t rng_stream, const void* qkv,
+                              const void* o, const float* lse) {
+    AttnDesc d;
+    d.dtype = dtype; d.B = B; d.T = T; d.H = H; d.D = D;
+    d.scale = scale ? 1.0f / sqrtf((float)D) : 1.0f;
+    d.p_drop = p_drop; d.seed = seed; d.rng_stream = rng_stream;
+    d.qkv = qkv; d.o = const_cast<void*>(o); d.lse = const_cast<float*>(lse);
+    return d;
+}
 extern "C" int cmp_k_attn_fwd(void* stream, const void* qkv, void* o, float* lse, int B, int T, int H, int D, int scale,
                               int dtype, float p_drop, uint64_t seed, uint32_t rng_stream) {
-    return attn_fwd_run(stream, qkv, o, lse, B, T, H, D, scale ? 1.0f / sqrtf((float)D) : 1.0f, dtype, p_drop, seed, rng_stream, nullptr);
-}
-
-// sc: the factor on q.k (the model driver passes 1/sqrt(E/H) of the reference's head size, which may be smaller than D: zero-padded heads)
-// amask: device float [B, T] added to the scaled scores of every query of a batch row (null: none)
-int attn_fwd_run(void* stream, const void* qkv, void* o, float* lse, int B, int T, int H, int D, float sc, int dtype, float p_drop,
-                 uint64_t seed, uint32_t rng_stream, const float* amask) {
-    if (B * T == 0) return CMP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    DropCfg d = make_drop(p_drop, seed, rng_stream);
-    if (dtype == CMP_BF16) { DISPATCH_D(bf16_t, launch_fwd, s, qkv, o, lse, B, T, H, sc, d, amask) }
-    else { DISPATCH_D(float, launch_fwd, s, qkv, o, lse, B, T, H, sc, d, amask) }
+    return attn_fwd_run(stream, attn_abi_desc(dtype, B, T, H, D, scale, p_drop, seed, rng_stream, qkv, o, lse));
 }
 
 // The attention probabilities themselves (Transformer(..., output_attention_weights=True), transformer.py:360-369, 808-809):
@@ -1441,28 +1413,28 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const T* __restrict__ q
     }
 }
 
-int attn_probs_run(void* stream, const void* qkv, const float* lse, const float* amask, float* out, int B, int q0, int T, int H, int D,
-                   float sc, int dtype, float p_drop, uint64_t seed, uint32_t rng_stream) {
-    if (B * (T - q0) <= 0) return CMP_OK;
+int attn_probs_run(void* stream, const AttnDesc& d, int q0, float* out) {
+    if (d.B * (d.T - q0) <= 0) return CMP_OK;
     hipStream_t s = (hipStream_t)stream;
-    const DropCfg d = make_drop(p_drop, seed, rng_stream);
-    const dim3 grid(T - q0, B * H);
-    if (dtype == CMP_BF16) attn_probs_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)qkv, lse, amask, out, q0, T, H, D, sc, d);
-    else attn_probs_kernel<float><<<grid, 256, 0, s>>>((const float*)qkv, lse, amask, out, q0, T, H, D, sc, d);
+    const DropCfg drop = make_drop(d.p_drop, d.seed, d.rng_stream);
+    const dim3 grid(d.T - q0, d.B * d.H);
+    if (d.dtype == CMP_BF16) attn_probs_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)d.qkv, d.lse, d.amask, out, q0, d.T, d.H, d.D, d.scale, drop);
+    else attn_probs_kernel<float><<<grid, 256, 0, s>>>((const float*)d.qkv, d.lse, d.amask, out, q0, d.T, d.H, d.D, d.scale, drop);
     KERNEL_CHECK();
     return CMP_OK;
 }
 
+int attn_bwd_run(void* stream, const AttnDesc& d) { ATTN_RUN(true, launch_bwd, (hipStream_t)stream, d); }
+
 // One-shot for the kernel-level tests that call cmp_k_attn_bwd directly (per calling thread): the next cmp_k_attn_bwd also
-// adds the column sums of [dQ | dK | dV] to out[0..3E) (the c_attn bias gradient).  The model driver passes the pointer to
-// attn_bwd_run itself.
+// adds the column sums of [dQ | dK | dV] to out[0..3E) (the c_attn bias gradient).  The model driver sets AttnDesc::bias_grad itself.
 static thread_local float* t_attn_bias_next = nullptr;
 extern "C" int cmp_attn_bwd_bias_next(float* out) {
     t_attn_bias_next = out;
     return CMP_OK;
 }
 
-// ... and (round 6) stores its gradient rows scaled by rstd[token] (AttnLnRows, common.h)
+// ... and (round 6) stores its gradient rows scaled by rstd[token] (AttnLnRows, attn_plan.h)
 static thread_local AttnLnRows t_attn_ln_next;
 extern "C" int cmp_attn_bwd_ln_next(const float* rstd) {
     t_attn_ln_next = AttnLnRows{rstd};
@@ -1472,20 +1444,67 @@ extern "C" int cmp_attn_bwd_ln_next(const float* rstd) {
 extern "C" int cmp_k_attn_bwd(void* stream, const void* qkv, const void* o, const void* d_o, const float* lse,
                               float* delta_ws, void* dqkv, int B, int T, int H, int D, int scale, int dtype,
                               float p_drop, uint64_t seed, uint32_t rng_stream) {
-    float* bias_grad = t_attn_bias_next;
+    AttnDesc d = attn_abi_desc(dtype, B, T, H, D, scale, p_drop, seed, rng_stream, qkv, o, lse);
+    d.d_o = d_o; d.delta = delta_ws; d.dqkv = dqkv;
+    d.bias_grad = t_attn_bias_next;
     t_attn_bias_next = nullptr;
-    const AttnLnRows lr = t_attn_ln_next;
+    d.ln = t_attn_ln_next;
     t_attn_ln_next = AttnLnRows();
-    return attn_bwd_run(stream, qkv, o, d_o, lse, delta_ws, dqkv, B, T, H, D, scale ? 1.0f / sqrtf((float)D) : 1.0f, dtype, p_drop, seed,
-                        rng_stream, bias_grad, lr);
+    return attn_bwd_run(stream, d);
 }
 
-int attn_bwd_run(void* stream, const void* qkv, const void* o, const void* d_o, const float* lse, float* delta_ws, void* dqkv,
-                 int B, int T, int H, int D, float sc, int dtype, float p_drop, uint64_t seed, uint32_t rng_stream,
-                 float* bias_grad, AttnLnRows lr) {
-    if (B * T == 0) return CMP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    DropCfg d = make_drop(p_drop, seed, rng_stream);
-    if (dtype == CMP_BF16) { DISPATCH_D(bf16_t, launch_bwd, s, qkv, o, d_o, lse, delta_ws, dqkv, B, T, H, sc, d, bias_grad, lr) }
-    else { DISPATCH_D(float, launch_bwd, s, qkv, o, d_o, lse, delta_ws, dqkv, B, T, H, sc, d, bias_grad, lr) }
+// the plan of the launch cmp_k_attn_fwd / cmp_k_attn_bwd would make of such a record on a device with these caps: no HIP call
+extern "C" int cmp_attn_plan(int dtype, int B, int T, int H, int D, float p_drop, int has_amask, int want_bias, int has_ln_rows,
+                             int backward, int wgs_per_cu, int ks_ok, cmp_attn_plan_info* out) {
+    CMP_REQUIRE(out != nullptr, "attn_plan: out is null");
+    static const float some = 0.f;            // any non-null address: the plan looks at null-ness only
+    AttnDesc d;
+    d.dtype = dtype; d.B = B; d.T = T; d.H = H; d.D = D; d.p_drop = p_drop;
+    if (has_amask) d.amask = &some;
+    if (want_bias) d.bias_grad = const_cast<float*>(&some);
+    if (has_ln_rows) d.ln.rstd = &some;
+    AttnCaps caps;
+    caps.ks_ok = ks_ok != 0;
+    caps.wgs_per_cu = wgs_per_cu;
+    const AttnPlan p = backward ? attn_plan_bwd(d, attn_env(), caps) : attn_plan_fwd(d, attn_env(), caps);
+    if (p.status != CMP_OK) {
+        cmp_set_error("%s", p.msg);
+        return p.status;
+    }
+    *out = cmp_attn_plan_info{p.form, p.drop, p.nlaunch, {(int)p.l[0].grid_x, (int)p.l[1].grid_x}, {(int)p.l[0].grid_y, (int)p.l[1].grid_y}, (int)p.block,
+                              {(int64_t)p.l[0].smem, (int64_t)p.l[1].smem}, p.optin, p.plan_u, p.bias_fused, p.bias_pass, {p.l[0].cls, p.l[1].cls},
+                              {p.l[0].work, p.l[1].work}, {p.l[0].bytes, p.l[1].bytes}, p.empty};
+    return CMP_OK;
 }
+// what the launcher asks the current device about the kernels of (dtype, D): the key-split opt-in and the occupancy of `kernel`
+template <typename T, int D> static int attn_caps_of(int kernel, AttnCaps* c) {
+    constexpr bool bf = std::is_same<T, bf16_t>::value;
+    if constexpr (attn_ks_built(bf, D)) c->ks_ok = attn_ks_available<T, D>();
+    if (kernel == CMP_ATTN_K_FWD) return attn_rows_caps<T, D, CMP_ATTN_K_FWD>(c);
+    if (kernel == CMP_ATTN_K_DQ) return attn_rows_caps<T, D, CMP_ATTN_K_DQ>(c);
+    if constexpr (bf) {
+        if (kernel == CMP_ATTN_K_DQ_LN) return attn_rows_caps<T, D, CMP_ATTN_K_DQ_LN>(c);
+    }
+    cmp_set_error("attn_caps: no kernel %d for dtype %d", kernel, bf ? CMP_BF16 : CMP_FP32);
+    return CMP_ERR_INVALID;
+}
+extern "C" int cmp_attn_caps(int dtype, int D, int kernel, int* wgs_per_cu, int* ks_ok) {
+    CMP_REQUIRE(wgs_per_cu && ks_ok, "attn_caps: null output");
+    AttnDesc d;
+    d.B = d.T = 1; d.D = D;
+    const AttnPlan chk = attn_plan_check(d, false);
+    if (chk.status != CMP_OK) {
+        cmp_set_error("%s", chk.msg);
+        return chk.status;
+    }
+    AttnCaps c;
+    const int rc = [&]() -> int {
+        if (dtype == CMP_BF16) { DISPATCH_D(bf16_t, attn_caps_of, kernel, &c) }
+        else { DISPATCH_D(float, attn_caps_of, kernel, &c) }
+        return CMP_ERR_INVALID;
+    }();
+    *wgs_per_cu = c.wgs_per_cu;
+    *ks_ok = c.ks_ok;
+    return rc;
+}
+

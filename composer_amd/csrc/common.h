@@ -104,19 +104,11 @@ struct WgradGroup {              // owned by the caller, one per call site whose
 int wgrad_group_run(void* stream, WgradGroup* g, const WgradProblem* probs, int nprob, int K, const GemmExtra& ex, bool* handled);
 void wgrad_group_free(WgradGroup* g);
 int gemm_run(void* stream, const GemmDesc& d, const GemmExtra& ex);
-// Round 6 (backward pass of the fused block path): the attention backward kernels store rstd o [dQ | dK | dV], rstd being that of the
-// token's row in the LayerNorm whose output fed c_attn (ln_stats_merge_kernel) -- the c_attn weight gradient then
-// runs on the raw rows (elementwise.hip: wgrad_ln_fix_kernel).  The bias gradient stays the column sums of the unscaled gradient.
-struct AttnLnRows {
-    const float* rstd = nullptr;      // [tokens]; null: nothing of this
-};
-int attn_bwd_run(void* stream, const void* qkv, const void* o, const void* d_o, const float* lse, float* delta_ws, void* dqkv,
-                 int B, int T, int H, int D, float sc, int dtype, float p_drop, uint64_t seed, uint32_t rng_stream,
-                 float* bias_grad, AttnLnRows lr = AttnLnRows());
-int attn_fwd_run(void* stream, const void* qkv, void* o, float* lse, int B, int T, int H, int D, float sc, int dtype, float p_drop,
-                 uint64_t seed, uint32_t rng_stream, const float* amask = nullptr);
-int attn_probs_run(void* stream, const void* qkv, const float* lse, const float* amask, float* out, int B, int q0, int T, int H, int D,
-                   float sc, int dtype, float p_drop, uint64_t seed, uint32_t rng_stream);
+#include "attn_plan.h"      // AttnDesc, AttnLnRows and the attention launch plan: host-only, no HIP
+int attn_fwd_run(void* stream, const AttnDesc& d);
+int attn_bwd_run(void* stream, const AttnDesc& d);
+// the probabilities of the queries [q0, T) of the same launch record (d.lse from its forward pass) into out [B, H, T - q0, T]
+int attn_probs_run(void* stream, const AttnDesc& d, int q0, float* out);
 
 __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -823,6 +823,17 @@ static int rows_copy(cmp_model* m, const void* src, void* dst, int B, int Tn, in
 // rows of the square one) and the T new output rows are taken out again.
 // transformer.py:340-343: w / sqrt(head size) -- the reference's head size E / H, whatever size the kernels run on
 static float attn_scale(const cmp_model* m) { return m->cfg.scale_attention ? 1.0f / sqrtf((float)m->Dl) : 1.0f; }
+// The attention launches of a layer as one launch record (attn_plan.h: AttnDesc): its forward, probabilities and backward calls
+// share everything but the mask, the gradient operands, the bias pointer and the rstd rows.
+static AttnDesc attn_desc(const cmp_model* m, int layer, int B, int Tt, int64_t step, float p) {
+    const LayerAct& a = m->act[layer];
+    AttnDesc d;
+    d.dtype = m->dtype; d.B = B; d.T = Tt; d.H = m->H; d.D = m->D;
+    d.scale = attn_scale(m);
+    d.p_drop = p; d.seed = m->drop_seed(); d.rng_stream = drop_stream(step, layer, 1);
+    d.qkv = a.qkv; d.o = a.att; d.lse = a.lse;
+    return d;
+}
 
 int model_forward(cmp_model* m, const int32_t* x_dev, int B, int T, bool training, int64_t step, int past_len) {
     Range range_("composer.forward");
@@ -867,8 +878,7 @@ int model_forward(cmp_model* m, const int32_t* x_dev, int B, int T, bool trainin
         LnEpi l;
         l.in_part = a.ln1_part; l.np = E / 256; l.eps = m->cfg.ln_eps; l.cs = fold;
         CHECK_RC(gemm(m, xw(1, M, 3 * E, E, m->xs[i], W(o.attn_w), a.qkv, fold + 3 * E), nullptr, &l, RV[0]));   // qkv = ln_1(x).Wattn + b   :583-584, 417
-        CHECK_RC(attn_fwd_run(s, a.qkv, a.att, a.lse, B, Tt, m->H, m->D, attn_scale(m), dt, pa, m->drop_seed(), drop_stream(step, i, 1),
-                              nullptr));
+        CHECK_RC(attn_fwd_run(s, attn_desc(m, i, B, Tt, step, pa)));
         l = LnEpi();
         l.in_part = a.ln1_part; l.np = E / 256; l.eps = m->cfg.ln_eps; l.gamma = m->P + o.ln1_g; l.beta = m->P + o.ln1_b;
         l.out_part = a.ln2_part;
@@ -893,11 +903,11 @@ int model_forward(cmp_model* m, const int32_t* x_dev, int B, int T, bool trainin
                                          m->cfg.ln_eps, dt));
         CHECK_RC(gemm(m, xw(wt, M, 3 * Ea, E, a.u, W(o.attn_w), Tp ? m->dqkv : a.qkv, m->P + o.attn_b)));
         if (Tp) CHECK_RC(rows_copy(m, m->dqkv, a.qkv, B, T, 3 * Ea, T, 0, 3 * Ea, Tt, Tp, 3 * Ea));  // concat([past, new]) :423-426
-        CHECK_RC(attn_fwd_run(s, a.qkv, a.att, a.lse, B, Tt, m->H, m->D, attn_scale(m), dt, pa, m->drop_seed(),
-                              drop_stream(step, i, 1), m->fwd_amask));
+        AttnDesc ad = attn_desc(m, i, B, Tt, step, pa);
+        ad.amask = m->fwd_amask;
+        CHECK_RC(attn_fwd_run(s, ad));
         if (m->fwd_probs_out) {      // output_attention_weights: this layer's [B, H, T, Tt] probabilities, copied out before the next layer
-            CHECK_RC(attn_probs_run(s, a.qkv, a.lse, m->fwd_amask, m->fwd_probs_dev, B, Tp, Tt, m->H, m->D, attn_scale(m), dt, pa,
-                                    m->drop_seed(), drop_stream(step, i, 1)));
+            CHECK_RC(attn_probs_run(s, ad, Tp, m->fwd_probs_dev));
             HIP_CHECK(hipMemcpyAsync(m->fwd_probs_out[i], m->fwd_probs_dev, (size_t)B * m->H * T * Tt * 4, hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
         }
@@ -1093,10 +1103,11 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
         if (!ln) CHECK_RC(colsum_any(m, dao, E, m->G + o.proj_b, M, E));
         CHECK_RC(gemm(m, xw(1, M, Ea, E, dao, m->w(o.proj_w), m->tmpE)));          // datt
         const bool det = m->slab != nullptr;     // the fused bias sums are float atomics: a separate fixed-order pass instead
-        AttnLnRows alr;
-        if (raw) alr.rstd = a.ln1_rstd;
-        CHECK_RC(attn_bwd_run(s, a.qkv, a.att, m->tmpE, a.lse, m->delta, m->dqkv, B, T, m->H, m->D, attn_scale(m),
-                              dt, pa, m->drop_seed(), drop_stream(step, i, 1), det ? nullptr : m->G + o.attn_b, alr));   // b_attn grad = column sums of dqkv
+        AttnDesc ad = attn_desc(m, i, B, T, step, pa);
+        ad.d_o = m->tmpE; ad.delta = m->delta; ad.dqkv = m->dqkv;
+        ad.bias_grad = det ? nullptr : m->G + o.attn_b;                            // b_attn grad = column sums of dqkv
+        if (raw) ad.ln.rstd = a.ln1_rstd;
+        CHECK_RC(attn_bwd_run(s, ad));
         if (det) CHECK_RC(colsum_det(m, m->dqkv, 3 * Ea, m->G + o.attn_b, M, 3 * Ea));
         auto group_launch = [&]() -> int {
             const WgradProblem wp[4] = {

@@ -581,6 +581,39 @@ int cmp_attn_bwd_bias_next(float* out);
 int cmp_k_attn_bwd(void* stream, const void* qkv, const void* o, const void* d_o, const float* lse,
                    float* delta_ws, void* dqkv, int B, int T, int H, int D, int scale, int dtype,
                    float p_drop, uint64_t seed, uint32_t rng_stream);
+/* Host-only window on the attention launcher's decision (CPU tests): the plan of the launch that cmp_k_attn_fwd (backward = 0) or
+ * cmp_k_attn_bwd (backward = 1) would make of such arguments -- has_amask: a per-key mask term (the model's forward only);
+ * want_bias: cmp_attn_bwd_bias_next armed; has_ln_rows: cmp_attn_bwd_ln_next armed -- on a device that answers wgs_per_cu and
+ * ks_ok (cmp_attn_caps).  Reads COMPOSER_ATTN_KS / COMPOSER_ATTN_BIAS_PASS as the launcher does, calls no HIP function and
+ * works without a device.  A launch that would be refused returns the same status and sets the same cmp_last_error() text. */
+enum {
+    CMP_ATTN_FWD_KS = 0,         /* key-split forward (bf16, head size <= 32, small grids) */
+    CMP_ATTN_FWD_MASK = 1,       /* 128-row forward with the mask term */
+    CMP_ATTN_FWD_ROWS = 2,       /* 128-row forward */
+    CMP_ATTN_BWD_LN = 3,         /* 128-row dQ, dK/dV with rstd-scaled stores */
+    CMP_ATTN_BWD_KS1 = 4,        /* key-split backward in one launch */
+    CMP_ATTN_BWD_KS2 = 5,        /* key-split dQ, then key-split dK/dV */
+    CMP_ATTN_BWD_ROWS = 6        /* 128-row dQ, dK/dV */
+};
+enum { CMP_ATTN_K_FWD = 0, CMP_ATTN_K_DQ = 1, CMP_ATTN_K_DQ_LN = 2 };   /* the kernel a block plan is for (cmp_attn_caps) */
+typedef struct cmp_attn_plan_info {
+    int32_t form;                /* CMP_ATTN_* */
+    int32_t drop;                /* the dropout instantiations */
+    int32_t nlaunch;             /* 1, or 2: [0] dQ, [1] dK/dV */
+    int32_t grid_x[2], grid_y[2], block;
+    int64_t smem[2];             /* dynamic LDS bytes per launch */
+    int32_t optin;               /* an image above 64 KiB: the kernels need the dynamic-LDS opt-in with smem[i] */
+    int32_t plan_u;              /* forward / dQ block plan: (batch, head) rows per XCD that run as single blocks; -1: the 2-D grid */
+    int32_t bias_fused, bias_pass;   /* wanted bias sums: in the kernels (float atomics), or a cmp_k_colsum pass after them */
+    int32_t cls[2];              /* cmp_prof_* timing class per launch, -1: not timed */
+    double work[2], bytes[2];    /* ... its flops and algorithmic HBM bytes */
+    int32_t empty;               /* B * T == 0: nothing is launched */
+} cmp_attn_plan_info;
+int cmp_attn_plan(int dtype, int B, int T, int H, int D, float p_drop, int has_amask, int want_bias, int has_ln_rows,
+                  int backward, int wgs_per_cu, int ks_ok, cmp_attn_plan_info* out);
+/* What the attention launcher asks the current device about the kernels of (dtype, D): resident workgroups per CU of `kernel`
+ * (CMP_ATTN_K_*; the block plan's slots) and whether the key-split set got its LDS opt-in (0 where none is built).  Needs a GPU. */
+int cmp_attn_caps(int dtype, int D, int kernel, int* wgs_per_cu, int* ks_ok);
 /* fused softmax cross-entropy forward+backward: logits fp32 [rows, ldz]; dlogits (dtype) [rows, ldz] with
  * zeroed padding; row_loss fp32 [rows]; row_correct int32 [rows]; inv_n = 1/(B*T) */
 int cmp_k_softmax_xent(void* stream, const float* logits, int ldz, const int32_t* y, void* dlogits,

@@ -447,9 +447,14 @@ def test_wgrad_group_guarded(lib, K, padded):
 
 
 # ------------------------------------------------------------------------------------------ attention
-@pytest.mark.parametrize("p", [0.0, 0.2])
-@pytest.mark.parametrize("dtype,B,T,H,D", [(dt, *s) for s in ((2, 33, 4, 16), (1, 130, 1, 128), (1, 333, 2, 64)) for dt in (FP32, BF16)]
-                         + [(BF16, 1, 96, 2, 16)])          # the last one runs the key-split kernels
+# (module-level: tests/test_attn_plan_host.py holds the rows to the launcher's plan on the CPU)
+ATTN_GUARDED_P = [0.0, 0.2]
+ATTN_GUARDED_CASES = ([(dt, *s) for s in ((2, 33, 4, 16), (1, 130, 1, 128), (1, 333, 2, 64)) for dt in (FP32, BF16)]
+                      + [(BF16, 1, 96, 2, 16)])          # the last one runs the key-split kernels
+
+
+@pytest.mark.parametrize("p", ATTN_GUARDED_P)
+@pytest.mark.parametrize("dtype,B,T,H,D", ATTN_GUARDED_CASES)
 def test_attention_guarded(lib, dtype, B, T, H, D, p):
     """cmp_k_attn_fwd / cmp_k_attn_bwd (bias gradient armed) with qkv and dO as arena inputs and o, lse, delta, dqkv as arena
     outputs at ragged T; the values against float64 with the tolerances of test_gpu_kernels.test_attention_fwd_bwd."""

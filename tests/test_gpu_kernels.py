@@ -401,9 +401,15 @@ def attn_ref(qkv, B, T, H, D, keep=None, p=0.0):
     return x, o, lse
 
 
+# The attention case tables are module-level so that tests/test_attn_plan_host.py can hold every row to the launcher's plan on the CPU:
+# the kernel form a row's comment names IS the form it reaches.
+ATTN_FWD_BWD_SHAPES = [(2, 33, 4, 16), (1, 64, 2, 32), (2, 200, 2, 64), (1, 130, 1, 128), (1, 256, 3, 64), (1, 333, 2, 64), (1, 520, 1, 32)]
+ATTN_FWD_BWD_P = [0.0, 0.2]
+
+
 @pytest.mark.parametrize("dtype", [FP32, BF16])
-@pytest.mark.parametrize("B,T,H,D", [(2, 33, 4, 16), (1, 64, 2, 32), (2, 200, 2, 64), (1, 130, 1, 128), (1, 256, 3, 64), (1, 333, 2, 64), (1, 520, 1, 32)])
-@pytest.mark.parametrize("p", [0.0, 0.2])
+@pytest.mark.parametrize("B,T,H,D", ATTN_FWD_BWD_SHAPES)
+@pytest.mark.parametrize("p", ATTN_FWD_BWD_P)
 def test_attention_fwd_bwd(lib, dtype, B, T, H, D, p):
     E = H * D
     g = torch.Generator().manual_seed(B * 1000 + T + D)
@@ -483,21 +489,28 @@ def check_attention_groups(lib, B, H, D, T, dtype, p, groups):
             assert rel_err(gh[b, :, j, h, :], x.grad[:, j]) < tol * 2, (b, h, name)
 
 
-@pytest.mark.parametrize("dtype,T,p", [(BF16, 1024, 0.0), (BF16, 1024, 0.1), (BF16, 2048, 0.0), (BF16, 2048, 0.1), (FP32, 1024, 0.1)])
+ATTN_FULL_LENGTH_CASES = [(BF16, 1024, 0.0), (BF16, 1024, 0.1), (BF16, 2048, 0.0), (BF16, 2048, 0.1), (FP32, 1024, 0.1)]
+ATTN_FULL_LENGTH_BHD = (8, 8, 64)
+
+
+@pytest.mark.parametrize("dtype,T,p", ATTN_FULL_LENGTH_CASES)
 def test_attention_full_length_many_groups(lib, dtype, T, p):
     """BASELINE shapes (seq 1024 / 2048, D = 64) with B*H = 64 (batch, head) groups: the balanced q-block pairing, the XCD
     re-deal of workgroups and the 64-key fused softmax step run with >= 8 query blocks per group; five groups (first, last and
     three in between) against float64."""
-    check_attention_groups(lib, 8, 8, 64, T, dtype, p, ((0, 0), (1, 5), (3, 2), (6, 7), (7, 7)))
+    check_attention_groups(lib, *ATTN_FULL_LENGTH_BHD, T, dtype, p, ((0, 0), (1, 5), (3, 2), (6, 7), (7, 7)))
 
 
-@pytest.mark.parametrize("dtype,B,H,D,T,p", [
+ATTN_BLOCK_PLAN_CASES = [
     (BF16, 32, 8, 64, 1024, 0.1),      # 32 rows per XCD, 128 pairs over 96 slots: 24 rows paired, 8 as single blocks
     (BF16, 16, 8, 64, 1000, 0.1),      # less than one round of pairs: 12 of 16 rows as single blocks; ragged last block
     (BF16, 40, 8, 64, 640, 0.0),       # five blocks per row (the middle one runs alone in a paired row), 8 rows unpaired
-    (BF16, 8, 16, 32, 2048, 0.1),      # 16 blocks per row, head size 32
+    (BF16, 8, 16, 32, 2048, 0.1),      # 16 blocks per row, head size 32: dQ runs 4 of 16 rows single; the forward (4 per CU) pairs all 16
     (FP32, 40, 8, 64, 512, 0.1),       # parity mode: two workgroups per CU, 64 slots per XCD
-])
+]
+
+
+@pytest.mark.parametrize("dtype,B,H,D,T,p", ATTN_BLOCK_PLAN_CASES)
 def test_attention_block_plans(lib, dtype, B, H, D, T, p):
     """Forward and dQ launches whose paired workgroups do not fill whole rounds of the resident slots run the rows of the last
     round as single blocks, heaviest first (attention.hip attn_job / attn_plan_u): every block of every row must still be
@@ -508,12 +521,15 @@ def test_attention_block_plans(lib, dtype, B, H, D, T, p):
     check_attention_groups(lib, B, H, D, T, dtype, p, groups)
 
 
-@pytest.mark.parametrize("B,H,D,T,p", [
+ATTN_KEY_SPLIT_CASES = [
     (1, 16, 16, 1024, 0.1),      # the reference's default configuration (default_config.yml:32-48) at batch 1
     (1, 16, 16, 1000, 0.0),      # ragged: the last 256-row staging tile and the last 32-row block are partial
     (2, 4, 32, 600, 0.1),        # head size 32; three staging tiles, the last one ragged
     (1, 2, 16, 96, 0.1),         # a single staging tile: three of the four waves own no key at all for the first block
-])
+]
+
+
+@pytest.mark.parametrize("B,H,D,T,p", ATTN_KEY_SPLIT_CASES)
 def test_attention_key_split_kernels(lib, B, H, D, T, p):
     """Small grids (B*H*ceil(T/128) <= 128 workgroups of the 128-row kind, bf16, head size <= 32) run the key-split forms of the
     three attention kernels (attention.hip KS): 32-row blocks, the four waves of a workgroup split every staged 256-row tile and
@@ -522,17 +538,44 @@ def test_attention_key_split_kernels(lib, B, H, D, T, p):
     check_attention_groups(lib, B, H, D, T, BF16, p, [(b, h) for b in range(B) for h in range(H)][:6] + [(B - 1, H - 1)])
 
 
-@pytest.mark.parametrize("B,H,D,T,p,fused", [
+ATTN_BIAS_PATH_CASES = [
     (8, 8, 64, 1024, 0.1, True),       # [tokens, 3E] gradient of 25 MB: the sums stay fused in dQ / dK-dV (float atomics)
     (5, 12, 64, 2048, 0.0, True),      # C4's head layout, 47 MB
     (1, 16, 16, 1024, 0.1, False),     # 1.6 MB: key-split kernels, the sums come from a column-sum pass over the stored gradient
     (8, 16, 16, 1024, 0.1, False),     # 12.6 MB: the 128-row kernels, column-sum pass
-])
+]
+
+
+def test_attention_caps_are_what_the_host_tables_assume(lib):
+    """cmp_attn_caps: what the launcher asks this device about the kernels of every (dtype, head size) -- resident workgroups per CU of the
+    forward, dQ and rstd-scaled dQ kernels, the key-split opt-in -- is what tests/test_attn_plan_host.py plans the case tables with."""
+    import test_attn_plan_host as HP
+    for (dtype, D), per_kernel in HP.DEVICE_CAPS.items():
+        for kernel, want in enumerate(per_kernel):
+            wgs, ks_ok = C.c_int(-1), C.c_int(-1)
+            rc = lib.cmp_attn_caps(dtype, D, kernel, C.byref(wgs), C.byref(ks_ok))
+            if want is None:
+                assert rc != 0 and "no kernel" in lib.cmp_last_error().decode(), (dtype, D, kernel)       # rstd rows exist in bf16 only
+                continue
+            ck(lib, rc)
+            assert (wgs.value, ks_ok.value) == (want, HP.device_ks_ok(dtype, D)), (dtype, D, kernel)
+
+
+def device_attn_plan(lib, dtype, B, T, H, D, p, backward, want_bias=0, has_ln_rows=0):
+    """What the launcher decides for such a cmp_k_attn_fwd / cmp_k_attn_bwd call on this device (cmp_attn_caps, cmp_attn_plan)."""
+    from composer_amd import _lib
+    wgs, ks_ok, info = C.c_int(0), C.c_int(0), _lib.AttnPlanInfo()
+    ck(lib, lib.cmp_attn_caps(dtype, D, (2 if has_ln_rows else 1) if backward else 0, C.byref(wgs), C.byref(ks_ok)))
+    ck(lib, lib.cmp_attn_plan(dtype, B, T, H, D, p, 0, want_bias, has_ln_rows, backward, wgs.value, ks_ok.value, C.byref(info)))
+    return info
+
+
+@pytest.mark.parametrize("B,H,D,T,p,fused", ATTN_BIAS_PATH_CASES)
 def test_attention_bias_gradient_paths(lib, B, H, D, T, p, fused):
     """The c_attn bias gradient = column sums of [dQ | dK | dV] (Conv1D bias under tf.GradientTape, transformer.py:205-209): fused
     into the backward kernels from their f32 accumulators where the launch is long enough to hide the atomics, a pass over the stored
-    bf16 gradient otherwise (attention.hip launch_bwd: 16 MiB).  Either way it must equal the column sums of the gradient the same
-    call stored -- exactly those of the stored values for the pass, within bf16 rounding of the summands for the fused form -- and
+    bf16 gradient otherwise (attn_plan.h: behind the key-split kernels, or at most 16 MiB; which one is read from the launcher's
+    plan).  Either way it must equal the column sums of the gradient the same call stored -- exactly those of the stored values for the pass, within bf16 rounding of the summands for the fused form -- and
     accumulate on top of the vector's contents."""
     E = H * D
     g = torch.Generator().manual_seed(B + T + D)
@@ -547,9 +590,10 @@ def test_attention_bias_gradient_paths(lib, B, H, D, T, p, fused):
     ck(lib, lib.cmp_attn_bwd_bias_next(P(bias)))
     ck(lib, lib.cmp_k_attn_bwd(stream(), P(qkv), P(o), P(do), P(lse), P(delta), P(dqkv), B, T, H, D, 1, BF16, p, 5, 3))
     torch.cuda.synchronize()
-    mib = int(os.environ.get("COMPOSER_ATTN_BIAS_PASS", "16"))          # (the measurement override moves the bound; the forms stay right)
-    assert (B * T * 3 * E * 2 > 16 << 20) == fused
-    fused = B * T * 3 * E * 2 > mib << 20
+    planned = bool(device_attn_plan(lib, BF16, B, T, H, D, p, backward=1, want_bias=1).bias_fused)
+    if int(os.environ.get("COMPOSER_ATTN_BIAS_PASS", "16")) == 16:      # (the measurement override moves the bound; the forms stay right)
+        assert planned == fused
+    fused = planned
     want = dqkv.double().sum(0).cpu() + 7.0
     scale = dqkv.double().abs().sum(0).cpu().clamp_min(1e-30)           # rounding of the summands is relative to their magnitudes
     err = ((bias.double().cpu() - want).abs() / scale).max().item()

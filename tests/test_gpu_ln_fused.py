@@ -331,12 +331,18 @@ def test_layernorm_backward_takes_a_prescaled_gradient(lib, E, p):
     assert rel(dmask.double().cpu().numpy(), np.where(keep, dx.double().cpu().numpy() / (1 - p), 0.0)) < 5e-3
 
 
-@pytest.mark.parametrize("D,H", [(64, 8), (32, 16), (128, 4)])
-@pytest.mark.parametrize("p", [0.0, 0.1])
+# (module-level: tests/test_attn_plan_host.py holds the cases to the launcher's plan on the CPU)
+ATTN_LN_ROWS_HEADS = [(64, 8), (32, 16), (128, 4)]
+ATTN_LN_ROWS_P = [0.0, 0.1]
+ATTN_LN_ROWS_BT = (3, 384)
+
+
+@pytest.mark.parametrize("D,H", ATTN_LN_ROWS_HEADS)
+@pytest.mark.parametrize("p", ATTN_LN_ROWS_P)
 def test_attention_backward_scales_its_rows_by_the_layernorm_rstd(lib, D, H, p):
     """AttnLnRows: [dQ | dK | dV] rows stored times the rstd of their token's LayerNorm statistics, the c_attn bias gradient (column sums
     of the UNSCALED gradient) untouched -- against the plain launch on the same inputs."""
-    B, T = 3, 384
+    B, T = ATTN_LN_ROWS_BT
     E = H * D
     rng = np.random.default_rng(D + int(10 * p))
     qkv = bf(rng.normal(0, 1.0, (B * T, 3 * E)))
