@@ -12,6 +12,7 @@ per-event likelihood of MIDI / `.data` files under a restored model; `generate -
 import datetime
 import json
 import logging
+import math
 import os
 import shutil
 import sys
@@ -333,14 +334,27 @@ def evaluate(model_type, dataset_path, restoredir, use_generator, max_files):
               help='Score the --num-samples N sequences under the model (mean log-probability of the generated events, '
                    'temperature 1, no filter) and write only the K best as OUTPUT-0 ... OUTPUT-{K-1}, best first; 1 <= K <= N. '
                    'Defaults to off: every sample is written.')
+@click.option('--duration', default=None, type=float, metavar='SECONDS',
+              help='Generate SECONDS of music behind the prompt (rounded to the config\'s time step, at least one): the time '
+                   'shifts land on it exactly, then every sounding note and the pedal are released, and the sequence ends '
+                   'there. --length stays the cap on events (a sample that reaches it first is written unfinished); long '
+                   'durations want --decode-mode kv-slide, which is not bound to window_size. Defaults to off.')
+@click.option('--max-polyphony', default=None, type=int, metavar='N',
+              help='Never more than N notes sounding at once (N >= 1): no NOTE_ON is sampled while N pitches sound. '
+                   'Defaults to off.')
 def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt_data, prompt_length, generate_length,
-             temperature, decode_mode, slide_keep, top_k, top_p, constrain, pitch_range, num_samples, keep_best):
+             temperature, decode_mode, slide_keep, top_k, top_p, constrain, pitch_range, num_samples, keep_best, duration,
+             max_polyphony):
     """Generate a MIDI file (cli.py:617-680): MIDI prompt -> event ids -> model -> event ids -> MIDI.  An output path
     ending in `.data` gets the event ids in the dataset's binary format instead of a MIDI file.  With --num-samples N > 1
     the N sequences are decoded as one batch and written to OUTPUT-0 ... OUTPUT-{N-1} (same suffix); --top-k / --top-p apply
-    to every sample, and so do --constrain / --pitch-range."""
+    to every sample, and so do --constrain / --pitch-range, --duration and --max-polyphony."""
     from composer_amd import notes as nt
     from composer_amd import grammar as gm
+    if duration is not None and not (duration > 0 and math.isfinite(duration)):      # refused from the arguments (a NaN fails too)
+        raise click.UsageError('--duration {}: SECONDS must be a number > 0.'.format(duration))
+    if max_polyphony is not None and max_polyphony < 1:
+        raise click.UsageError('--max-polyphony {}: must be >= 1.'.format(max_polyphony))
     if pitch_range is not None:                                  # refused from the arguments, before any device use
         try:
             lo, hi = (int(t) for t in pitch_range.split(':'))
@@ -411,8 +425,27 @@ def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt
         if pitch_range is not None:
             slide.update(banned_ids=g.pitch_range_bans(lo, hi))
         click.echo('grammar: constrain {} pitch-range {}'.format('on' if constrain else 'off', pitch_range or 'off'), err=True)
+    timed = None
+    if duration is not None or max_polyphony is not None:
+        # the budget reads the layout (which ids shift time, which are notes): supplied with no rule when nothing above gave it
+        g = slide.get('grammar') or gm.EventGrammar.from_dataset_params(d.time_step_increment, d.max_time_steps, d.velocity_bins,
+                                                                        rules=0)
+        steps = max(1, int(round(duration * 1000.0 / d.time_step_increment))) if duration is not None else None
+        slide.update(grammar=g, duration_steps=steps, max_polyphony=max_polyphony or 0)
+        timed = gm.TimedRules(g, steps or 0, max_polyphony or 0)
+        click.echo('budget: duration {} max-polyphony {}'.format(
+            '{} steps of {} ms'.format(steps, d.time_step_increment) if steps else 'off', max_polyphony or 'off'), err=True)
+
+    def report(i, ids):                                          # one line per sample: what was written, and whether it ended
+        if timed is None or not timed.time_steps:
+            return
+        st = timed.fold(x, ids)
+        click.echo('sample {}: {} events, {:.3f} s, finished {}'.format(
+            i, len(ids), (st.g.time_steps - (st.t_end - timed.time_steps)) * d.time_step_increment / 1000.0,
+            'yes' if st.done_at >= 0 else 'no'), err=True)
     if num_samples == 1 and keep_best is None:
         ids = model.generate(x, generate_length, temperature=temperature, mode=decode_mode, **slide)
+        report(0, ids)
         _write_generated(list(x) + ids.tolist(), out, d)         # prompt + generated (cli.py:676)
         click.echo(','.join(str(int(i)) for i in ids))
         return
@@ -428,6 +461,7 @@ def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt
         click.echo('keep-best: kept {}'.format(','.join(str(i) for i in order)), err=True)
         batch = [batch[i] for i in order]
     for i, ids in enumerate(batch):
+        report(i, ids)
         _write_generated(list(x) + ids.tolist(), out.with_name('{}-{}{}'.format(out.stem, i, out.suffix)), d)
         click.echo(','.join(str(int(t)) for t in ids))
 

@@ -433,14 +433,14 @@ __global__ __launch_bounds__(256) void dec_sample2_kernel(const float* __restric
     float pe[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) { const int e = tid + 256 * i; pe[i] = e < E ? wpe[(int64_t)posc * E + e] : 0.f; }
-    const int id = sample_block_grammar(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, trunc_lds, g0, banw);
+    const int id = sample_block_grammar(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, trunc_lds, g0, &st->bd, banw);
     if (tid == 0) {
         if (nprod < capI) ids[nprod] = id;
         st->produced = nprod + 1;
         st->rng = ctr + 1;
         st->token = id;
         st->pos = pos;
-        grammar_advance(&st->gr, g0, id);
+        grammar_advance(&st->gr, &st->bd, g0, id, nprod + 1);
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) { const int e = tid + 256 * i; if (e < E) x[e] = wte[(int64_t)id * E + e] + pe[i]; }
@@ -562,6 +562,34 @@ extern "C" int cmp_decode_grammar_state(cmp_model* m, int batched, int row, uint
     return CMP_OK;
 }
 
+// ---- timed generation: configuration and state read-back of both chains (composer_hip.h) ----
+extern "C" int cmp_decode_budget(cmp_model* m, int batched, int64_t time_steps, int32_t max_polyphony) {
+    CMP_REQUIRE(m, "decode_budget: null model");
+    CMP_REQUIRE(time_steps >= 0, "decode_budget: time_steps=%lld must be >= 0 (0: no time budget)", (long long)time_steps);
+    CMP_REQUIRE(max_polyphony >= 0, "decode_budget: max_polyphony=%d must be >= 0 (0: no cap)", max_polyphony);
+    DecBudgetCfg& bc = m->budget[batched ? 1 : 0];      // read by the chain's next begin
+    bc.time_steps = time_steps;
+    bc.max_polyphony = max_polyphony;
+    return CMP_OK;
+}
+
+extern "C" int cmp_decode_budget_state(cmp_model* m, int batched, int row, int64_t* steps_left, int32_t* phase, int32_t* done_at) {
+    CMP_REQUIRE(m && steps_left && phase && done_at, "decode_budget_state: null argument");
+    const DecRows* R = dec_rows_of(m, batched);
+    CHECK_RC(dec_require_begun("decode_budget_state", R && R->begun, dec_begin_name(batched)));
+    if (batched) CMP_REQUIRE(row >= 0 && row < R->B, "decode_budget_state: row %d outside the batch of %d rows", row, R->B);
+    else CMP_REQUIRE(row == 0, "decode_budget_state: row %d of the batch-1 chain (row 0 only)", row);
+    HIP_CHECK(hipSetDevice(m->ctx->device));
+    HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+    DecRow h;
+    HIP_CHECK(hipMemcpy(&h, R->st + row, sizeof(h), hipMemcpyDeviceToHost));
+    const bool any = (h.gr.sounding[0] | h.gr.sounding[1] | h.gr.sounding[2] | h.gr.sounding[3]) != 0u || h.gr.pedal != 0;
+    *steps_left = h.bd.t_end ? h.bd.t_end - h.gr.time_steps : 0;
+    *phase = budget_phase(h.bd.t_end, h.gr.time_steps, any);
+    *done_at = h.bd.done_at;
+    return CMP_OK;
+}
+
 extern "C" int cmp_decode_slide_stats(cmp_model* m, int batched, int64_t* row_slides, int64_t* forward_calls) {
     CMP_REQUIRE(m && row_slides && forward_calls, "decode_slide_stats: null argument");
     const DecRows* R = dec_rows_of(m, batched);
@@ -602,7 +630,7 @@ __global__ __launch_bounds__(256) void dec_slide_sample_kernel(const float* __re
     const unsigned ctr = rs->rng;
     const int nprod = rs->produced;
     const GramRegs g0 = grammar_read(&rs->gr);
-    const int id = sample_block_grammar(z, V, rs->temperature, rs->top_k, rs->top_p, rs->seed, ctr, bv, bi, trunc_lds, g0, banw);
+    const int id = sample_block_grammar(z, V, rs->temperature, rs->top_k, rs->top_p, rs->seed, ctr, bv, bi, trunc_lds, g0, &rs->bd, banw);
     __syncthreads();                       // every thread has read the state before thread 0 moves it on
     if (tid == 0) {
         if (nprod < cap) ids[(int64_t)b * cap + nprod] = id;
@@ -611,7 +639,7 @@ __global__ __launch_bounds__(256) void dec_slide_sample_kernel(const float* __re
         rs->token = id;
         rs->pos = keep;
         rs->hold = 0;
-        grammar_advance(&rs->gr, g0, id);
+        grammar_advance(&rs->gr, &rs->bd, g0, id, nprod + 1);
     }
     float* xr = x + (int64_t)b * E;
     for (int e = tid; e < E; e += 256) xr[e] = wte[(int64_t)id * E + e] + wpe[(int64_t)keep * E + e];
@@ -788,8 +816,22 @@ int dec_rows_alloc(cmp_model* m, DecRows& R, int B) {
     return CMP_OK;
 }
 
+// what a begin call refuses of the chain's budget (composer_hip.h, "timed generation"), before any device work
+int dec_check_budget(const char* who, const DecGrammarCfg& c, const DecBudgetCfg& bc) {
+    if (bc.time_steps == 0 && bc.max_polyphony == 0) return CMP_OK;
+    CMP_REQUIRE(c.has_layout, "%s: a budget (time_steps %lld, max_polyphony %d) is set but the chain has no grammar layout: "
+                "cmp_decode_grammar names the TIME_SHIFT, NOTE_ON, NOTE_OFF and pedal ids (rules = 0 is enough)", who,
+                (long long)bc.time_steps, bc.max_polyphony);
+    if (bc.time_steps > 0 && !c.words.empty()) {
+        const int id = c.g.time_shift0;
+        CMP_REQUIRE(!((c.words[id >> 5] >> (id & 31)) & 1u), "%s: the static vector bans time_shift0 = %d, the one-step TIME_SHIFT: "
+                    "under a time budget it must stay drawable", who, id);
+    }
+    return CMP_OK;
+}
+
 DecRow dec_row_init(int mode, int P, unsigned seed, float temperature, int top_k, float top_p, const DecGrammarCfg& c,
-                    const int32_t* prompt) {
+                    const DecBudgetCfg& bc, const int32_t* prompt) {
     DecRow h = {};
     h.pos = (mode == CMP_DECODE_KV) ? P : 0;     // position of the first generated token when it is fed back
     h.advance = (mode == CMP_DECODE_KV) ? 1 : 0;
@@ -798,6 +840,11 @@ DecRow dec_row_init(int mode, int P, unsigned seed, float temperature, int top_k
     h.top_k = top_k;
     h.top_p = top_p;
     h.gr = grammar_begin(c, prompt, P);
+    // the budget covers the generated part: the prompt's own duration is not charged to it
+    h.bd.t_end = bc.time_steps > 0 ? h.gr.time_steps + bc.time_steps : 0;
+    h.bd.max_polyphony = bc.max_polyphony;
+    h.bd.done_at = -1;
+    if (bc.time_steps > 0 || bc.max_polyphony > 0) h.gr.active = 1;
     return h;
 }
 
@@ -868,6 +915,7 @@ static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mod
     CMP_REQUIRE(mode == CMP_DECODE_LITERAL || mode == CMP_DECODE_KV, "decode_begin: bad mode %d", mode);
     CHECK_RC(sampling_check("decode_begin", m->V, temperature, top_k, top_p));
     CHECK_RC(dec_check_prompt("decode_begin", -1, prompt, P, m->V, m->W));
+    CHECK_RC(dec_check_budget("decode_begin", m->gram[0], m->budget[0]));
     HIP_CHECK(hipSetDevice(m->ctx->device));
     hipStream_t s = m->ctx->stream;
     // the workspace never grows after its first sizing: a slide re-encodes `keep` tokens through it, so it is sized (or found too
@@ -895,7 +943,7 @@ static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mod
     R.mode = mode;
     R.keep = keep;
     R.row_slides = R.fwd_calls = 0;
-    const DecRow h = dec_row_init(mode, P, (unsigned)seed, temperature, top_k, top_p, m->gram[0], prompt);
+    const DecRow h = dec_row_init(mode, P, (unsigned)seed, temperature, top_k, top_p, m->gram[0], m->budget[0], prompt);
     HIP_CHECK(grammar_upload(m->gram[0], m->V, d->w.banw, s));
     HIP_CHECK(hipMemcpyAsync(R.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
     if (keep > 0) HIP_CHECK(hipMemcpyAsync(R.plen, &P, 4, hipMemcpyHostToDevice, s));

@@ -282,14 +282,14 @@ __global__ __launch_bounds__(256) void decb_sample_kernel(const float* __restric
     const int pos = first ? pos0 : (adv ? pos0 + 1 : 0);
     const int posc = min(pos, W - 1);      // host refuses to step past the table; never index outside it
     float* xr = x + (int64_t)b * E;
-    const int id = sample_block_grammar(z, V, temperature, rs->top_k, rs->top_p, seed, ctr, bv, bi, trunc_lds, g0, banw);
+    const int id = sample_block_grammar(z, V, temperature, rs->top_k, rs->top_p, seed, ctr, bv, bi, trunc_lds, g0, &rs->bd, banw);
     if (tid == 0) {
         if (nprod < cap) ids[(int64_t)b * cap + nprod] = id;
         rs->produced = nprod + 1;
         rs->rng = ctr + 1;
         rs->token = id;
         rs->pos = pos;
-        grammar_advance(&rs->gr, g0, id);
+        grammar_advance(&rs->gr, &rs->bd, g0, id, nprod + 1);
     }
     for (int e = tid; e < E; e += 256) xr[e] = wte[(int64_t)id * E + e] + wpe[(int64_t)posc * E + e];
 }
@@ -430,6 +430,7 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
         CMP_REQUIRE(lens[b] <= ld, "decode_batch_begin: row %d: length %d exceeds the leading dimension %d", b, lens[b], ld);
         CHECK_RC(dec_check_prompt("decode_batch_begin", b, prompts + (int64_t)b * ld, lens[b], m->V, m->W));
     }
+    CHECK_RC(dec_check_budget("decode_batch_begin", m->gram[1], m->budget[1]));
     HIP_CHECK(hipSetDevice(m->ctx->device));
     hipStream_t s = m->ctx->stream;
     if (keep > 0) {
@@ -463,7 +464,7 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
     d->pos.assign(B, 0);
     for (int b = 0; b < B; b++) {
         h[b] = dec_row_init(mode, lens[b], (unsigned)(seed + (uint64_t)b), temperature ? temperature[b] : temperature0,
-                            top_k ? top_k[b] : 0, top_p ? top_p[b] : 1.0f, m->gram[1], prompts + (int64_t)b * ld);
+                            top_k ? top_k[b] : 0, top_p ? top_p[b] : 1.0f, m->gram[1], m->budget[1], prompts + (int64_t)b * ld);
         d->pos[b] = h[b].pos;
     }
     HIP_CHECK(grammar_upload(m->gram[1], m->V, d->w.banw, s));

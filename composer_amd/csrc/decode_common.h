@@ -64,7 +64,7 @@ __device__ __forceinline__ int block_argmax(float best, int arg, float* bv, int*
 // ---- event grammar (composer_hip.h, "event-grammar decoding") ----------------------------------------------------------------
 // The per-row state of the grammar beside the sampling parameters in DecRow: the caller's id layout, the rule bits and
 // the fold of prompt ++ ids so far.  `layout` = 0: no layout was given (no dynamic rule, the state never moves); `active` = 0: no
-// rule and no static bit -- the kernels that draw then call today's sampler and nothing else.
+// rule, no static bit and no budget -- the kernels that draw then call today's sampler and nothing else.
 struct DecGrammar {
     int note_on0, note_off0, time_shift0, time_shift_n, sustain_on, sustain_off;
     unsigned rules;          // CMP_GRAMMAR_* bits (0 without a layout)
@@ -74,6 +74,17 @@ struct DecGrammar {
     unsigned sounding[4];    // bit p: pitch p sounds
     long long time_steps;    // sum over the TIME_SHIFT events of the sequence, id time_shift0 + j counting j + 1
 };
+// ---- timed generation (composer_hip.h, "timed generation"): the budget of a row beside its grammar state in DecRow --------------
+struct DecBudget {
+    long long t_end;         // time_steps(prompt) + the chain's time budget; 0: no time budget (the row stays in PLAY)
+    int max_polyphony;       // 0: no cap
+    int done_at;             // -1 until the state first becomes DONE, then the ids the row had produced at that moment
+};
+// the phase of a row: a pure function of its state (any: a pitch sounds or the pedal is down)
+__host__ __device__ __forceinline__ int budget_phase(long long t_end, long long time_steps, bool any) {
+    if (t_end == 0 || time_steps < t_end) return CMP_BUDGET_PLAY;
+    return any ? CMP_BUDGET_ENDING : CMP_BUDGET_DONE;
+}
 
 // the transition NoteSequence.from_events implements, for one id: the prompt's fold in the begin functions (host)
 static inline void grammar_step(DecGrammar& g, int id) {
@@ -104,11 +115,44 @@ __device__ __forceinline__ GramRegs grammar_read(const DecGrammar* __restrict__ 
     r.time_steps = g->time_steps;
     return r;
 }
+// The transition under a time budget (t_end != 0): in DONE the id is a filler and the state stays where it is; after a real id,
+// done_at records the ids produced so far (`produced`, this one included) when the new state is DONE.  The new state's three
+// terms -- pitches sounding, pedal, time -- are followed in registers from g0 (bit p of the sounding set in arithmetic, as
+// ban_sounds reads it).
+__device__ __forceinline__ void grammar_advance_timed(DecGrammar* __restrict__ gm, DecBudget* __restrict__ bd, const GramRegs& g0,
+                                                      int id, int produced, long long t_end) {
+    int cnt = __popc(g0.s0) + __popc(g0.s1) + __popc(g0.s2) + __popc(g0.s3), ped = g0.pedal;
+    long long t = g0.time_steps;
+    if (budget_phase(t_end, t, (cnt | ped) != 0) == CMP_BUDGET_DONE) return;
+    const unsigned on = (unsigned)(id - g0.note_on0), off = (unsigned)(id - g0.note_off0), ts = (unsigned)(id - g0.time_shift0);
+    if (on < 128u) {
+        gm->sounding[on >> 5] |= 1u << (on & 31);
+        cnt += 1;                                     // (one more or the same: not empty either way)
+    } else if (off < 128u) {
+        gm->sounding[off >> 5] &= ~(1u << (off & 31));
+        const unsigned r = off & 31, i = off >> 5;
+        cnt -= (int)((((g0.s0 >> r) & (unsigned)(i == 0u)) | ((g0.s1 >> r) & (unsigned)(i == 1u)) |
+                      ((g0.s2 >> r) & (unsigned)(i == 2u)) | ((g0.s3 >> r) & (unsigned)(i == 3u))) & 1u);
+    } else if (ts < (unsigned)g0.time_shift_n) {
+        t += (long long)ts + 1;
+        gm->time_steps = t;
+    } else if (id == g0.sustain_on) {
+        gm->pedal = ped = 1;
+    } else if (id == g0.sustain_off) {
+        gm->pedal = ped = 0;
+    }
+    if (budget_phase(t_end, t, (cnt | ped) != 0) == CMP_BUDGET_DONE) bd->done_at = produced;
+}
 // ... and the transition for the drawn id on the device, by ONE lane after every thread has read the state: g0 is the state the
 // draw saw, gm the state in memory; only the word that changes is written (a note event updates its word of the sounding set in
-// memory: which word is known only now, and a run-time choice between registers is what the compiler turns into scratch)
-__device__ __forceinline__ void grammar_advance(DecGrammar* __restrict__ gm, const GramRegs& g0, int id) {
+// memory: which word is known only now, and a run-time choice between registers is what the compiler turns into scratch).
+// The budget is not part of what the draw's threads load: t_end, constant since begin, is read here by the one lane, and only on
+// a chain with a layout; without a time budget the transition is the code it was.
+__device__ __forceinline__ void grammar_advance(DecGrammar* __restrict__ gm, DecBudget* __restrict__ bd, const GramRegs& g0, int id,
+                                                int produced) {
     if (!g0.layout) return;
+    const long long t_end = bd->t_end;
+    if (t_end != 0) { grammar_advance_timed(gm, bd, g0, id, produced, t_end); return; }
     const unsigned on = (unsigned)(id - g0.note_on0), off = (unsigned)(id - g0.note_off0), ts = (unsigned)(id - g0.time_shift0);
     if (on < 128u) {
         gm->sounding[on >> 5] |= 1u << (on & 31);
@@ -131,10 +175,17 @@ struct BanCtx {
     unsigned rules;
     int pedal;
     unsigned s0, s1, s2, s3;
+    // timed generation: the phase of the row, the TIME_SHIFT ids [ts_lo, ts_hi) that would pass t_end (PLAY; empty without a time
+    // budget), whether the polyphony cap is reached (PLAY: no NOTE_ON), and the filler id of DONE
+    int phase, ts_lo, ts_hi, no_on, time_shift0;
 };
 __device__ __forceinline__ int uni_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ BanCtx ban_load(const GramRegs& g, const unsigned* __restrict__ words) {
+// bd: the row's budget, loaded HERE -- on the banning path only, so a chain without grammar and budget (`active` = 0) reads none
+// of it; t_end and max_polyphony are constant since begin, so there is no writer to race with
+__device__ __forceinline__ BanCtx ban_load(const GramRegs& g, const DecBudget* __restrict__ bd, const unsigned* __restrict__ words) {
     BanCtx b;
+    const long long t_end = bd->t_end;
+    const int max_polyphony = bd->max_polyphony;
     b.words = words;
     b.note_on0 = uni_i(g.note_on0); b.note_off0 = uni_i(g.note_off0);
     b.sustain_on = uni_i(g.sustain_on); b.sustain_off = uni_i(g.sustain_off);
@@ -142,11 +193,22 @@ __device__ __forceinline__ BanCtx ban_load(const GramRegs& g, const unsigned* __
     b.pedal = uni_i(g.pedal);
     b.s0 = (unsigned)uni_i((int)g.s0); b.s1 = (unsigned)uni_i((int)g.s1);
     b.s2 = (unsigned)uni_i((int)g.s2); b.s3 = (unsigned)uni_i((int)g.s3);
+    // the budget's terms, once per workgroup from the uniform words above: the popcount of the sounding set, the phase, and the
+    // number of TIME_SHIFT ids that stay allowed, min(time_shift_n, t_end - time_steps) (all of them without a time budget)
+    const int cnt = __popc(b.s0) + __popc(b.s1) + __popc(b.s2) + __popc(b.s3);
+    const long long left = t_end - g.time_steps;
+    const int tsn = g.layout ? g.time_shift_n : 0;
+    const int allow = (t_end != 0 && left < (long long)tsn) ? (int)(left > 0 ? left : 0) : tsn;
+    b.phase = uni_i(budget_phase(t_end, g.time_steps, (cnt | b.pedal) != 0));
+    b.time_shift0 = uni_i(g.time_shift0);
+    b.ts_lo = uni_i(g.time_shift0 + allow);
+    b.ts_hi = uni_i(g.time_shift0 + tsn);
+    b.no_on = uni_i((max_polyphony > 0 && cnt >= max_polyphony) ? 1 : 0);
     return b;
 }
 // static bans only (cmp_k_sample_banned)
 __device__ __forceinline__ BanCtx ban_static(const unsigned* __restrict__ words) {
-    BanCtx b = {words, 0, 0, -1, -1, 0u, 0, 0u, 0u, 0u, 0u};
+    BanCtx b = {words, 0, 0, -1, -1, 0u, 0, 0u, 0u, 0u, 0u, CMP_BUDGET_PLAY, 0, 0, 0, -1};
     return b;
 }
 // bit p of the sounding set, in arithmetic alone (a select between the four words ends up as an indexed load from scratch)
@@ -158,7 +220,15 @@ __device__ __forceinline__ bool ban_sounds(const BanCtx& b, unsigned p) {
 }
 // column c (0 <= c < V) cannot be drawn in this state
 __device__ __forceinline__ bool banned(const BanCtx& b, int c) {
+    if (b.phase != CMP_BUDGET_PLAY) {                 // (uniform) the static vector and the rule bits are not read here
+        if (b.phase == CMP_BUDGET_DONE) return c != b.time_shift0;                    // the filler alone
+        const unsigned p = (unsigned)(c - b.note_off0);                              // ENDING: only what releases
+        if (p < 128u) return !ban_sounds(b, p);
+        return !(c == b.sustain_off && b.pedal);
+    }
     bool r = (b.words[c >> 5] >> (c & 31)) & 1u;
+    r = r || (c >= b.ts_lo && c < b.ts_hi);           // a TIME_SHIFT that would pass t_end
+    if (b.no_on) r = r || (unsigned)(c - b.note_on0) < 128u;                         // the polyphony cap is reached
     if (b.rules & CMP_GRAMMAR_NOTE_OFF_SOUNDING) {
         const unsigned p = (unsigned)(c - b.note_off0);
         if (p < 128u) r = r || !ban_sounds(b, p);
@@ -354,8 +424,9 @@ __device__ __forceinline__ int sample_block_banned(const float* __restrict__ z, 
 }
 __device__ __forceinline__ int sample_block_grammar(const float* __restrict__ z, int V, float temperature, int top_k, float top_p,
                                                     unsigned seed, unsigned ctr, float* bv, int* bi, unsigned char* lds,
-                                                    const GramRegs& g, const unsigned* __restrict__ words) {
-    if (uni_i(g.active)) return sample_block_banned(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, lds, ban_load(g, words));
+                                                    const GramRegs& g, const DecBudget* __restrict__ bd,
+                                                    const unsigned* __restrict__ words) {
+    if (uni_i(g.active)) return sample_block_banned(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, lds, ban_load(g, bd, words));
     return sample_block_any(z, V, temperature, top_k, top_p, seed, ctr, bv, bi, lds);
 }
 
@@ -401,6 +472,7 @@ struct DecRow {          // device-resident per-row loop state (the captured cha
     int top_k;           // truncated sampling, per row: 0 or >= V: off
     float top_p;         // 1: off
     DecGrammar gr;       // event grammar: layout, rules and the fold of the row's prompt ++ ids so far
+    DecBudget bd;        // timed generation: where the row's time ends, its polyphony cap, when it was done
 };
 
 struct DecRowList {      // rows of one slide, by value in the kernel arguments: no host buffer has to outlive an enqueued step
@@ -490,8 +562,9 @@ int dec_require_begun(const char* who, bool begun, const char* begin_fn);
 int dec_weights_refresh(cmp_model* m, DecWeights& w);       // allocated on first use; transposed again when a parameter has changed
 void dec_rows_free(DecRows& R);
 int dec_rows_alloc(cmp_model* m, DecRows& R, int B);
+int dec_check_budget(const char* who, const DecGrammarCfg& c, const DecBudgetCfg& bc);      // the begin-time refusals of a budget
 DecRow dec_row_init(int mode, int P, unsigned seed, float temperature, int top_k, float top_p, const DecGrammarCfg& c,
-                    const int32_t* prompt);
+                    const DecBudgetCfg& bc, const int32_t* prompt);
 int dec_prefill_row(cmp_model* m, DecRows& R, const DecWeights& w, int b, const int32_t* prompt, int P);
 int dec_enqueue_slide(cmp_model* m, DecRows& R, const DecWeights& w, const DecRowList& rl, int nb);
 // decode_batch.hip: decb_sample_kernel for rows row0 .. row0 + nrows - 1 from `logits` (one row each, stride ldz)

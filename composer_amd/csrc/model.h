@@ -16,6 +16,12 @@ struct DecGrammarCfg {
     std::vector<uint32_t> words;       // static bans, ceil(V / 32) words; empty: none
 };
 
+// ... and cmp_decode_budget (both 0: off)
+struct DecBudgetCfg {
+    int64_t time_steps = 0;
+    int32_t max_polyphony = 0;
+};
+
 struct GradClipStats { double norm; float scale; float factor; };     // elementwise.hip: grad_clip_finish_kernel
 
 struct Metrics {
@@ -213,6 +219,7 @@ struct cmp_model {
     DecodeState* dec = nullptr;
     DecodeBatchState* decb = nullptr;  // batched decode (decode_batch.hip): its own buffers, KV caches and captured chains
     DecGrammarCfg gram[2];             // event grammar of the batch-1 chain [0] and of the batched chain [1] (cmp_decode_grammar)
+    DecBudgetCfg budget[2];            // time budget and polyphony cap of the two chains, likewise (cmp_decode_budget)
     int gemm_role = -1;                // profiler class of the GEMMs being enqueued (0 while the forward pass is)
 
     // dropout seed of this replica: the model seed with the data-parallel rank folded in (rank 0: the seed itself)

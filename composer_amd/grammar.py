@@ -5,6 +5,10 @@ is down and a SUSTAIN_OFF while it is up.  An `EventGrammar` names the id layout
 state those four cases depend on (which pitches sound, where the pedal is, plus the summed time shifts) and says which ids are
 banned in a state.  The decode chains keep the same state per row on the device and draw from the allowed ids only
 (`Transformer.generate(..., grammar=...)`); this module is what the tests compare them with.  Pure numpy / Python.
+
+`TimedRules` restates the second contract of that header ("timed generation") over an `EventGrammar`: a time budget the draws land
+on exactly, an ending phase that only releases what sounds, and a polyphony cap (`Transformer.generate(..., duration_steps=,
+max_polyphony=)`).
 """
 import numpy as np
 
@@ -203,3 +207,99 @@ class EventGrammar:
         mask[self.note_on0:self.note_on0 + lo] = True
         mask[self.note_on0 + hi + 1:self.note_on0 + PITCHES] = True
         return ban_words(self.vocab_size, mask)
+
+
+# ---------------------------------------------------------------------- timed generation (composer_hip.h, "timed generation")
+PLAY, ENDING, DONE = 0, 1, 2
+
+
+class TimedState:
+    """The state of a row under a budget: the grammar's state `g`, the step count `t_end` at which the generated part ends (0: no
+    time budget), the ids produced so far and `done_at` (-1 until the state first becomes DONE, then the ids produced by then)."""
+    __slots__ = ('g', 't_end', 'produced', 'done_at')
+
+    def __init__(self, g=None, t_end=0, produced=0, done_at=-1):
+        self.g = GrammarState() if g is None else g
+        self.t_end, self.produced, self.done_at = int(t_end), int(produced), int(done_at)
+
+    def copy(self):
+        return TimedState(self.g.copy(), self.t_end, self.produced, self.done_at)
+
+    @property
+    def steps_left(self):
+        return self.t_end - self.g.time_steps if self.t_end else 0
+
+    def __repr__(self):
+        return 'TimedState(%r, t_end=%d, produced=%d, done_at=%d)' % (self.g, self.t_end, self.produced, self.done_at)
+
+
+class TimedRules:
+    """The budget of cmp_decode_budget over an `EventGrammar`: `time_steps` >= 0 steps of generated time (0: none) that the draw
+    lands on exactly, an ending phase that only releases what sounds, and at most `max_polyphony` >= 0 sounding pitches (0: no
+    cap).  Phases, ban sets and the frozen DONE state as the decode chains keep them per row on the device."""
+
+    def __init__(self, grammar, time_steps=0, max_polyphony=0):
+        self.grammar = grammar
+        self.time_steps, self.max_polyphony = int(time_steps), int(max_polyphony)
+        if self.time_steps < 0:
+            raise ValueError('time_steps=%d must be >= 0 (0: no time budget)' % self.time_steps)
+        if self.max_polyphony < 0:
+            raise ValueError('max_polyphony=%d must be >= 0 (0: no cap)' % self.max_polyphony)
+
+    def check_static_bans(self, static):
+        """The rule the begin calls enforce: a time budget needs the one-step shift drawable, or a row one step short of t_end
+        could never land on it."""
+        if self.time_steps and static is not None and words_to_mask(self.grammar.vocab_size, static)[self.grammar.time_shift0]:
+            raise ValueError('the static ban vector bans the one-step TIME_SHIFT id %d: a time budget needs it drawable'
+                             % self.grammar.time_shift0)
+        return static
+
+    def t_end(self, prompt):
+        """time_steps(prompt) + the budget: the prompt's own duration is not charged to it.  0 without a time budget."""
+        return self.grammar.fold(prompt).time_steps + self.time_steps if self.time_steps else 0
+
+    def begin(self, prompt):
+        """The state of a row whose sequence so far is its prompt."""
+        return TimedState(self.grammar.fold(prompt), self.t_end(prompt))
+
+    def phase(self, state):
+        if state.t_end == 0 or state.g.time_steps < state.t_end:
+            return PLAY
+        return ENDING if state.g.sounding.any() or state.g.pedal else DONE
+
+    def banned(self, state, static=None):
+        """bool [V]: the ban set of the next draw in `state`."""
+        g, ph = self.grammar, self.phase(state)
+        if ph == PLAY:
+            b = g.banned(state.g, static)
+            if state.t_end:
+                b[g.time_shift0 + min(g.time_shift_n, state.t_end - state.g.time_steps):g.time_shift0 + g.time_shift_n] = True
+            if self.max_polyphony and int(state.g.sounding.sum()) >= self.max_polyphony:
+                b[g.note_on0:g.note_on0 + PITCHES] = True
+            return b
+        b = np.ones(g.vocab_size, bool)
+        if ph == ENDING:                 # the static vector and the rule bits are ignored: the ending must be able to finish
+            b[g.note_off0:g.note_off0 + PITCHES] = ~state.g.sounding
+            if state.g.pedal:
+                b[g.sustain_off] = False
+        else:
+            b[g.time_shift0] = False     # the filler
+        return b
+
+    def step(self, state, event_id):
+        """Applies one drawn id to `state` in place.  In DONE the id is a filler: only `produced` moves.  Returns `done_at`."""
+        if self.phase(state) != DONE:
+            self.grammar.step(state.g, event_id)
+            state.produced += 1
+            if self.phase(state) == DONE:
+                state.done_at = state.produced
+        else:
+            state.produced += 1
+        return state.done_at
+
+    def fold(self, prompt, ids):
+        """The state after `ids` drawn behind `prompt`."""
+        st = self.begin(prompt)
+        for i in np.asarray(ids).reshape(-1):
+            self.step(st, i)
+        return st

@@ -749,8 +749,83 @@ class Transformer:
         bits = np.unpackbits(np.array(list(w), '<u4').view(np.uint8), bitorder='little').astype(bool)
         return gm.GrammarState(bits, bool(ped.value), ts.value)
 
+    # Timed generation asks for its ids in chunks and reads the budget state after each.  32 is a choice, not a measurement: one
+    # synchronisation per 32 tokens at about 119 us per token, and at most 31 filler steps behind the end of a row.
+    BUDGET_CHUNK = 32
+
+    def _check_decode_budget(self, grammar, banned_ids, duration_steps, max_polyphony):
+        """(time steps, cap) of a generate call, refused from the arguments as cmp_decode_budget and the begin call would refuse
+        them (before the chain's configuration is touched)."""
+        from composer_amd import grammar as gm
+        steps = 0 if duration_steps is None else int(duration_steps)
+        cap = int(max_polyphony)
+        if duration_steps is not None and steps < 1:
+            raise ValueError('duration_steps=%d must be >= 1' % steps)
+        if cap < 0:
+            raise ValueError('max_polyphony=%d must be >= 0 (0: no cap)' % cap)
+        if steps or cap:
+            if grammar is None:
+                raise ValueError('duration_steps / max_polyphony need a grammar: the layout says which ids shift time and which '
+                                 'are notes (rules=0 is enough)')
+            if banned_ids is not None:
+                gm.TimedRules(grammar, steps, cap).check_static_bans(gm.ban_words(self.vocab_size, banned_ids))
+        return steps, cap
+
+    def _set_decode_budget(self, batched, steps, cap):
+        """cmp_decode_budget for the chain the next begin call belongs to; without a budget the chain is switched off again only
+        if an earlier call of this object switched it on (as _set_decode_grammar)."""
+        on = getattr(self, '_budget_on', None)
+        if on is None:
+            on = self._budget_on = [False, False]
+        if steps == 0 and cap == 0:
+            if on[batched]:
+                _lib.check(self._lib.cmp_decode_budget(self._h, batched, 0, 0), 'cmp_decode_budget')
+                on[batched] = False
+            return
+        _lib.check(self._lib.cmp_decode_budget(self._h, batched, steps, cap), 'cmp_decode_budget')
+        on[batched] = True
+
+    def decode_budget_state(self, batched=False, row=0):
+        """(steps_left, phase, done_at) of a row after its latest id (cmp_decode_budget_state): the steps of its time budget
+        still to go, `composer_amd.grammar.PLAY` / `ENDING` / `DONE`, and the number of ids it had produced when it became DONE
+        (-1 before; ids from there on are filler).  (0, PLAY, -1) while the chain has no budget."""
+        left, ph, da = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.cmp_decode_budget_state(self._h, 1 if batched else 0, int(row), C.byref(left), C.byref(ph), C.byref(da)),
+                   'cmp_decode_budget_state')
+        return left.value, ph.value, da.value
+
+    def _timed_steps(self, length):
+        """`length` ids of the batch-1 chain at most, BUDGET_CHUNK per call, until the row is done: the ids up to done_at."""
+        out = np.empty(length, np.int32)
+        n = 0
+        while n < length:
+            c = min(self.BUDGET_CHUNK, length - n)
+            part = np.empty(c, np.int32)
+            _lib.check(self._lib.cmp_decode_steps(self._h, c, part.ctypes.data_as(C.c_void_p)), 'cmp_decode_steps')
+            out[n:n + c] = part
+            n += c
+            done_at = self.decode_budget_state()[2]
+            if done_at >= 0:
+                return out[:done_at].copy()
+        return out
+
+    def _timed_batch_steps(self, B, length):
+        """The same for the batched chain, until every row is done: a list of B arrays, row b cut at its done_at."""
+        out = np.empty((B, length), np.int32)
+        n = 0
+        while n < length:
+            c = min(self.BUDGET_CHUNK, length - n)
+            part = np.empty((B, c), np.int32)
+            _lib.check(self._lib.cmp_decode_batch_steps(self._h, c, part.ctypes.data_as(C.c_void_p)), 'cmp_decode_batch_steps')
+            out[:, n:n + c] = part
+            n += c
+            if all(self.decode_budget_state(True, b)[2] >= 0 for b in range(B)):      # (stops reading at the first unfinished row)
+                break
+        done = [self.decode_budget_state(True, b)[2] for b in range(B)]
+        return [out[b, :(d if d >= 0 else n)].copy() for b, d in enumerate(done)]
+
     def generate(self, prompt_ids, length, temperature=1.0, mode='kv', seed=None, slide_keep=None, top_k=0, top_p=1.0,
-                 grammar=None, banned_ids=None):
+                 grammar=None, banned_ids=None, duration_steps=None, max_polyphony=0):
         """Returns `length` generated ids.  mode 'literal' restates cli.py:663-676 as written (no `past`),
         mode 'kv' is model(x, past=presents).  temperature <= 0 -> greedy argmax.  mode 'kv-slide' is 'kv' that goes on past
         window_size: when the cache is full the last `slide_keep` tokens (default window_size // 2) are re-encoded from position 0
@@ -759,10 +834,17 @@ class Transformer:
         `sampling_keep_set(logits, temperature, top_k, top_p)` names, renormalised.
         grammar (a `composer_amd.grammar.EventGrammar`) / banned_ids (ids, a bool mask or ban words): event-grammar decoding -- ids
         the grammar bans in the state of prompt ++ ids so far, and the banned ids, are never drawn (they read -inf, before top_k /
-        top_p rank the row and for the greedy argmax too).  Default: off, the sampler as it was."""
+        top_p rank the row and for the greedy argmax too).  Default: off, the sampler as it was.
+        duration_steps / max_polyphony: timed generation (cmp_decode_budget; both need `grammar`, rules 0 is enough).  With
+        duration_steps the generated part lasts exactly that many time steps and ends with every note released and the pedal
+        up: `length` is then the cap on events, the ids come back as soon as the row is done (fewer than `length` of them), or
+        all `length` ids when the cap came first (`decode_budget_state()[2]` is then -1).  max_polyphony: never more than that
+        many pitches sounding at once (0: no cap)."""
         p = np.ascontiguousarray(np.asarray(prompt_ids, dtype=np.int32).reshape(-1))
         top_k, top_p = check_sampling(top_k, top_p)
+        steps, cap = self._check_decode_budget(grammar, banned_ids, duration_steps, max_polyphony)
         self._set_decode_grammar(0, grammar, banned_ids)
+        self._set_decode_budget(0, steps, cap)
         filters = top_k != 0 or top_p != 1.0
         if mode == 'kv-slide':
             keep = self._slide_keep(slide_keep)
@@ -773,6 +855,8 @@ class Transformer:
             else:
                 _lib.check(self._lib.cmp_decode_begin_slide(self._h, p.ctypes.data_as(C.c_void_p), len(p), keep, float(temperature),
                                                             int(self.seed if seed is None else seed)), 'cmp_decode_begin_slide')
+            if steps:
+                return self._timed_steps(int(length))
             out = np.empty(length, np.int32)
             _lib.check(self._lib.cmp_decode_steps(self._h, int(length), out.ctypes.data_as(C.c_void_p)), 'cmp_decode_steps')
             return out
@@ -789,19 +873,27 @@ class Transformer:
         else:
             _lib.check(self._lib.cmp_decode_begin(self._h, p.ctypes.data_as(C.c_void_p), len(p), m, float(temperature),
                                                   int(self.seed if seed is None else seed)), 'cmp_decode_begin')
+        if steps:
+            return self._timed_steps(int(length))
         out = np.empty(length, np.int32)
         _lib.check(self._lib.cmp_decode_steps(self._h, int(length), out.ctypes.data_as(C.c_void_p)), 'cmp_decode_steps')
         return out
 
     def generate_batch(self, prompts, length, temperature=1.0, mode='kv', seed=None, slide_keep=None, top_k=0, top_p=1.0,
-                       grammar=None, banned_ids=None):
+                       grammar=None, banned_ids=None, duration_steps=None, max_polyphony=0):
         """B independent sequences decoded together: returns int32 [B, length].  `prompts` is a list of id sequences (ragged
         rows allowed); row b samples with seed + b, so it equals `generate(prompts[b], length, seed=seed + b)` in its first id
         and depends on nothing but its own prompt and seed.  Modes, temperature and slide_keep as in `generate`; in 'kv-slide'
         every row slides on its own length.  temperature, top_k and top_p are each a scalar (every row) or a sequence of B values
         (row b's own): a row's ids depend on its own three only.  grammar / banned_ids as in `generate`: one grammar and one ban
-        vector for all rows, the state each row's own."""
+        vector for all rows, the state each row's own.
+        duration_steps / max_polyphony as in `generate`: one budget for all rows, each row charged from its own prompt's time.
+        With duration_steps the result is a list of B arrays of unequal length (row b cut where it was done, or all `length`
+        ids when the cap came first); decoding stops when every row is done, so a finished row costs at most the filler steps
+        until the slowest row ends (plus the rest of that chunk of BUDGET_CHUNK steps)."""
+        steps, cap = self._check_decode_budget(grammar, banned_ids, duration_steps, max_polyphony)
         self._set_decode_grammar(1, grammar, banned_ids)
+        self._set_decode_budget(1, steps, cap)
         rows = [np.asarray(p, dtype=np.int64).reshape(-1) for p in prompts]
         slide = mode == 'kv-slide'
         if slide:
@@ -856,6 +948,8 @@ class Transformer:
                                                         ld, m, float(temperature), int(self.seed if seed is None else seed)),
                        'cmp_decode_batch_begin')
         self._decode_batch_rows = B
+        if steps:
+            return self._timed_batch_steps(B, int(length))
         out = np.empty((B, length), np.int32)
         _lib.check(self._lib.cmp_decode_batch_steps(self._h, int(length), out.ctypes.data_as(C.c_void_p)), 'cmp_decode_batch_steps')
         return out

@@ -379,6 +379,45 @@ int cmp_decode_grammar_state(cmp_model* m, int batched, int row, uint32_t soundi
 int cmp_k_sample_banned(void* stream, const float* logits, int V, float temperature, int top_k, float top_p,
                         const uint32_t* banned_dev, uint64_t seed, uint32_t counter0, int n, int32_t* ids_out);
 
+/* ---- timed generation: a time budget and a polyphony cap in the sampler ------------------------------------------------------
+ * The vocabulary has no end-of-piece event, so a decode that stops after a number of ids stops wherever that id falls: the length
+ * in seconds is an accident of the draws, and NoteSequence.from_events drops every note (and the pedal period) still open at the
+ * end.  With a budget configured, both decode chains draw a generated part that lasts exactly `time_steps` steps, then release
+ * what sounds, and never stack more than `max_polyphony` pitches.  Enforced per draw on the device, like the grammar; the
+ * contract (composer_amd.grammar.TimedRules restates it on the host):
+ *   Configuration: per chain, read by that chain's next begin call (any of them), as cmp_decode_grammar is.  time_steps >= 0 in
+ *     the units of cmp_decode_grammar_state's time_steps (id time_shift0 + j counts j + 1), 0: no time budget; max_polyphony >= 0,
+ *     0: no cap; both 0: off.  At begin every row gets t_end = time_steps(its prompt) + time_steps (0 without a time budget): the
+ *     budget covers the generated part, the prompt's own duration is not charged to it.
+ *   Phases, a pure function of the row's state: PLAY: t_end == 0 or time_steps < t_end.  ENDING: time_steps == t_end and a pitch
+ *     sounds or the pedal is down.  DONE: time_steps == t_end, nothing sounds, the pedal is up.
+ *   Ban set of a draw.  PLAY: the grammar's (rules and static vector), plus TIME_SHIFT j while time_steps + j + 1 > t_end -- time
+ *     never passes t_end and can always reach it -- plus, with a cap, every NOTE_ON while popcount(sounding) >= max_polyphony.
+ *     ENDING: everything but NOTE_OFF p of a sounding p, and SUSTAIN_OFF while the pedal is down; the static vector and the rule
+ *     bits are ignored here (the ending must always be able to finish), the model still chooses the order of the releases.
+ *     DONE: everything but time_shift0.  That id is a filler: it does not move the grammar state (time_steps stays at t_end);
+ *     the produced count, the draw counter and the position go on as for any id, so the chain is otherwise unchanged.
+ *   The draw is the grammar's: the id equals, bit for bit, cmp_k_sample_ex on a copy of the logits row with the ban set's columns
+ *     at -inf (same temperature, top_k, top_p, seed and draw counter), before the ranking and for greedy too.
+ *   done_at, per row on the device: -1 until the state first becomes DONE, then the number of ids the row had produced at that
+ *     moment.  Ids from done_at on are filler and not part of the result.
+ *   The state is a function of the whole sequence: a kv-slide re-encode does not reset it, the literal mode carries it too, and a
+ *     held row of the batched chain stays untouched by the replay.  A row's ids depend on its own prompt, seed, parameters and the
+ *     chain's budget only.
+ *   Off (both 0) is the code path without this section: every id of every entry point is what it was, bit for bit.
+ *   Refusals (CMP_ERR_INVALID before any device work, the reason in cmp_last_error): a negative value, at the call; at a begin
+ *     call, a budget on a chain without a grammar layout (which ids are TIME_SHIFT, NOTE_ON, NOTE_OFF and pedal events is the
+ *     layout's to say; rules = 0 is enough) and a time budget whose static vector bans time_shift0 (a row one step short of t_end
+ *     could never land on it).  A refused call leaves the configuration and a decode in progress as they were. */
+#define CMP_BUDGET_PLAY 0
+#define CMP_BUDGET_ENDING 1
+#define CMP_BUDGET_DONE 2
+int cmp_decode_budget(cmp_model* m, int batched, int64_t time_steps, int32_t max_polyphony);
+/* Row `row` of the chain (batch-1: row 0) after its latest id; synchronises, like cmp_decode_grammar_state.  steps_left:
+ * t_end - time_steps; phase: CMP_BUDGET_*.  Without a budget: steps_left 0, phase PLAY, done_at -1.  CMP_ERR_STATE before begin,
+ * CMP_ERR_INVALID for a bad row. */
+int cmp_decode_budget_state(cmp_model* m, int batched, int row, int64_t* steps_left, int32_t* phase, int32_t* done_at);
+
 /* ---- batched decode: B independent sequences per step (1 <= B <= 256), state apart from cmp_decode_begin's ----------------
  * prompts: host int32 [B][ld], row b holds lens[b] ids (1 <= lens[b] <= window_size).  Row b samples with seed (uint32)(seed + b);
  * its i-th generated id uses draw counter i, as cmp_decode_begin does, so its first id equals cmp_decode_begin's on that prompt
