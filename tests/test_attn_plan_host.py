@@ -158,6 +158,44 @@ def test_ln_rows_cases_get_the_rstd_form_with_fused_sums(lib):
         assert (plain["form"], plain["bias_pass"]) == (BWD_ROWS, 1), plain
 
 
+def test_attention_bound_tables_reach_the_forms_their_comments_name(lib):
+    """tests/test_gpu_attention_bounds.py: every row of its tables, at both dropout rates, with the bias gradient armed."""
+    import test_gpu_attention_bounds as AB
+    def forms(row, **kw):
+        dtype, B, T, H, D, _ = row
+        return [tuple(q["form"] for q in both(lib, dtype, B, T, H, D, p, bias=1, **kw)) for p in AB.P_DROP]
+    # tile-edge lengths: bf16 at head size 16 is on the key-split set from T = 64 on, in ONE launch (at most 2 * 9 * 2 = 36 workgroups);
+    # every other row, head size 64 and all of fp32, on the 128-row kernels
+    seen = set()
+    for row in AB.TILE_EDGE_CASES:
+        dtype, B, T, H, D, _ = row
+        want = (FWD_KS, BWD_KS1) if (dtype == BF16 and D == 16 and T >= 64) else (FWD_ROWS, BWD_ROWS)
+        assert forms(row) == [want] * 2, row
+        seen.add((dtype, D, want))
+    assert seen == {(FP32, 16, (FWD_ROWS, BWD_ROWS)), (FP32, 64, (FWD_ROWS, BWD_ROWS)), (BF16, 64, (FWD_ROWS, BWD_ROWS)),
+                    (BF16, 16, (FWD_ROWS, BWD_ROWS)), (BF16, 16, (FWD_KS, BWD_KS1))}
+    assert {r[2] for r in AB.TILE_EDGE_CASES} == {1, 2} | {e + d for e in (32, 64, 128, 256) for d in (-1, 0, 1)}
+    # T = 333 on the 128-row kernels: three query blocks; the narrow bf16 heads only because 3 * 48 blocks are past the key split
+    for row in AB.ROWS_333_CASES:
+        dtype, B, T, H, D, _ = row
+        assert forms(row) == [(FWD_ROWS, BWD_ROWS)] * 2 and T == 333 and -(-T // 128) == 3, row
+        if dtype == BF16 and D <= 32:
+            assert 3 * B * H > 128, row
+    assert {(r[0], r[4]) for r in AB.ROWS_333_CASES} == {(FP32, 64), (BF16, 64), (FP32, 128), (BF16, 128), (BF16, 16), (BF16, 32)}
+    assert {r[0] for r in AB.ROWS_333_CASES if r[5] == 0} == {FP32, BF16}                     # one row per dtype with scale = 0
+    # key split: the backward in one launch while 2 * 11 * B H <= 512, in two from there on
+    for row in AB.KEY_SPLIT_ONE_CASES:
+        assert forms(row) == [(FWD_KS, BWD_KS1)] * 2 and 2 * 11 * row[1] * row[3] <= 512, row
+    for row in AB.KEY_SPLIT_TWO_CASES:
+        assert forms(row) == [(FWD_KS, BWD_KS2)] * 2 and 3 * row[1] * row[3] <= 128 and 2 * 11 * row[1] * row[3] > 512, row
+    assert {r[4] for r in AB.KEY_SPLIT_ONE_CASES} == {r[4] for r in AB.KEY_SPLIT_TWO_CASES} == {16, 32}
+    # the rstd-scaled backward: a row of the rstd test's own table
+    for row in AB.LN_ROWS_CASES:
+        dtype, B, T, H, D, _ = row
+        assert (B, T) == L.ATTN_LN_ROWS_BT and (D, H) in L.ATTN_LN_ROWS_HEADS and dtype == BF16
+        assert [plan(lib, dtype, B, T, H, D, p, bias=1, ln=1, backward=1)["form"] for p in AB.P_DROP] == [BWD_LN] * 2, row
+
+
 # ------------------------------------------------------------------------------------------ (b) the model's own launches
 def test_model_launches(lib):
     # C2 (E = 512, 8 heads of 64, T = 1024) at B = 128: 1024 (batch, head) rows, 128 per XCD; 4 pairs each over 96 slots: 5 whole rounds

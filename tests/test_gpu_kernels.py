@@ -445,13 +445,19 @@ def test_attention_fwd_bwd(lib, dtype, B, T, H, D, p):
         assert err / max(ref[:, sl].abs().max().item(), 0.1 * whole, 1e-30) < tol * 2, name
 
 
-def check_attention_groups(lib, B, H, D, T, dtype, p, groups):
+def check_attention_groups(lib, B, H, D, T, dtype, p, groups, inputs="randn"):
     """The whole grid runs on the GPU; the float64 reference is computed for the listed (batch, head) groups, each of them
-    checked in full: o, lse, dq, dk, dv."""
+    checked in full: o, lse, dq, dk, dv -- first with the global-maximum tolerances this file has always used, then per element under
+    the limits of tests/attention_bounds.py (attn_check).  inputs: "randn", or "planted" (attention_bounds.attn_inputs: every query
+    weights a partner key, so that a key or a tile that some row does not see moves that row by many limits)."""
+    import attention_bounds as AB
     E = H * D
     g = torch.Generator().manual_seed(T + int(p * 100) + dtype + B)
-    qkv = dev(torch.randn(B * T, 3 * E, generator=g), dtype)
-    do = dev(torch.randn(B * T, E, generator=g), dtype)
+    if inputs == "planted":
+        qkv, do = (dev(t, dtype) for t in AB.attn_inputs(B, T, H, D, 1.0 / math.sqrt(D), seed=T + int(p * 100) + dtype + B, device="cuda"))
+    else:
+        qkv = dev(torch.randn(B * T, 3 * E, generator=g), dtype)
+        do = dev(torch.randn(B * T, E, generator=g), dtype)
     o = torch.zeros(B * T, E, device="cuda", dtype=tdt(dtype))
     lse = torch.zeros(B * H * T, device="cuda")
     ck(lib, lib.cmp_k_attn_fwd(stream(), P(qkv), P(o), P(lse), B, T, H, D, 1, dtype, p, 77, 9))
@@ -487,6 +493,12 @@ def check_attention_groups(lib, B, H, D, T, dtype, p, groups):
         assert rel_err(lh[b, h], torch.logsumexp(w, -1).detach()) < (1e-5 if dtype == FP32 else 2e-2), (b, h)
         for j, name in enumerate(("dq", "dk", "dv")):
             assert rel_err(gh[b, :, j, h, :], x.grad[:, j]) < tol * 2, (b, h, name)
+    what = "attention %s B%d T%d H%d D%d p%.1f %s" % ("bf16" if dtype == BF16 else "fp32", B, T, H, D, p, inputs)
+    # planted: the groups that cover every partner offset the grid holds (the callers' lists are chosen for the schedule, not for that)
+    bound_groups = AB.covering_groups(B, H) if inputs == "planted" else groups
+    worst = AB.attn_check(qkv, do, o, lse, delta, dqkv, B, T, H, D, dtype, p, 1.0 / math.sqrt(D), 77, 9, bound_groups, what=what, raise_on_fail=False)
+    print(AB.figures(what, worst, dtype))
+    AB.raise_first(worst)
 
 
 ATTN_FULL_LENGTH_CASES = [(BF16, 1024, 0.0), (BF16, 1024, 0.1), (BF16, 2048, 0.0), (BF16, 2048, 0.1), (FP32, 1024, 0.1)]
@@ -498,7 +510,8 @@ def test_attention_full_length_many_groups(lib, dtype, T, p):
     """BASELINE shapes (seq 1024 / 2048, D = 64) with B*H = 64 (batch, head) groups: the balanced q-block pairing, the XCD
     re-deal of workgroups and the 64-key fused softmax step run with >= 8 query blocks per group; five groups (first, last and
     three in between) against float64."""
-    check_attention_groups(lib, *ATTN_FULL_LENGTH_BHD, T, dtype, p, ((0, 0), (1, 5), (3, 2), (6, 7), (7, 7)))
+    for inputs in ("randn", "planted"):
+        check_attention_groups(lib, *ATTN_FULL_LENGTH_BHD, T, dtype, p, ((0, 0), (1, 5), (3, 2), (6, 7), (7, 7)), inputs=inputs)
 
 
 ATTN_BLOCK_PLAN_CASES = [
@@ -518,7 +531,8 @@ def test_attention_block_plans(lib, dtype, B, H, D, T, p):
     count) against float64, and the whole output must be free of untouched (zero-initialised) rows."""
     rows = B * H
     groups = sorted({(0, 0), (0, H - 1), ((rows // 2) // H, (rows // 2) % H), ((rows - 9) // H, (rows - 9) % H), (B - 1, H - 1)})
-    check_attention_groups(lib, B, H, D, T, dtype, p, groups)
+    for inputs in ("randn", "planted"):
+        check_attention_groups(lib, B, H, D, T, dtype, p, groups, inputs=inputs)
 
 
 ATTN_KEY_SPLIT_CASES = [
@@ -535,7 +549,8 @@ def test_attention_key_split_kernels(lib, B, H, D, T, p):
     three attention kernels (attention.hip KS): 32-row blocks, the four waves of a workgroup split every staged 256-row tile and
     merge their partial softmax states / gradient tiles through LDS.  Every (batch, head) group against float64, with the
     dropout masks the other kernels draw."""
-    check_attention_groups(lib, B, H, D, T, BF16, p, [(b, h) for b in range(B) for h in range(H)][:6] + [(B - 1, H - 1)])
+    for inputs in ("randn", "planted"):
+        check_attention_groups(lib, B, H, D, T, BF16, p, [(b, h) for b in range(B) for h in range(H)][:6] + [(B - 1, H - 1)], inputs=inputs)
 
 
 ATTN_BIAS_PATH_CASES = [
