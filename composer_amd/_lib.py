@@ -38,6 +38,11 @@ class EventGrammar(C.Structure):
     ]
 
 
+class BatchRow(C.Structure):
+    """cmp_batch_row: one row of a device dataset's batch plan (composer_amd.dataset.DeviceDataset builds it)."""
+    _fields_ = [("offset", C.c_int64), ("transpose", C.c_int32), ("stretch_q10", C.c_int32)]
+
+
 class GemmPlanInfo(C.Structure):
     """cmp_gemm_plan_info: the launcher's decision for one cmp_k_gemm argument list (host only; tests/test_gemm_plan_host.py)."""
     _fields_ = [(n, C.c_int32) for n in ("family", "a_km", "b_km", "swap", "kind", "lnm", "np", "diag", "grid_x", "grid_y", "grid_z", "block")] + \
@@ -99,6 +104,11 @@ SIGNATURES = {
     "cmp_eval_step": (_i, [_P, _P, _P, _i, _i, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(_i64)]),
     "cmp_score": (_i, [_P, _P, _P, _i, _i, _P, _P, _P]),
     "cmp_k_score_rows": (_i, [_P, _P, _i, _P, _P, _P, _P, _i, _i]),
+    "cmp_dataset_create": (_i, [_P, _P, _i64, C.POINTER(EventGrammar), C.POINTER(_P)]),
+    "cmp_dataset_destroy": (_i, [_P]),
+    "cmp_k_batch_rows": (_i, [_P, _P, _i64, C.POINTER(EventGrammar), _P, _i, _i, _P, _P, _P]),
+    "cmp_dataset_batch": (_i, [_P, _P, _i, _i, _P, _P, _P]),
+    "cmp_train_step_dataset": (_i, [_P, _P, _P, _i, _i, _f, C.POINTER(_i64)]),
     "cmp_present_get": (_i, [_P, _i, _i, _i, _P]),
     "cmp_forward_generation": (_i, [_P, C.POINTER(_i64)]),
     "cmp_present_get_at": (_i, [_P, _i, _i, _i, _i64, _P]),
@@ -172,7 +182,8 @@ SIGNATURES = {
 _ADDED_LATER = {"cmp_gemm_ln_scale_next", "cmp_attn_bwd_ln_next", "cmp_k_layernorm_bwd_prescaled", "cmp_k_wgrad_ln_fix", "cmp_k_ln_stats_merge", "cmp_dp_rccl_version", "cmp_dp_allreduce_pattern", "cmp_dp_init_exchange", "cmp_train_step_graph_probe", "cmp_train_step_launches", "cmp_k_embed_fwd_stats", "cmp_k_ln_fold_prep", "cmp_gemm_ln_next", "cmp_k_layernorm_bwd_parts", "cmp_model_path_info", "cmp_forward_ex", "cmp_hidden_get_at", "cmp_dp_stats", "cmp_prof_end2", "cmp_prof_pause", "cmp_prof_resume", "cmp_k_wgrad_group", "cmp_k_embed_bwd_v", "cmp_decode_batch_begin", "cmp_decode_batch_steps", "cmp_k_sample_rows", "cmp_decode_logits_get", "cmp_decode_batch_logits_get", "cmp_k_sample_ex", "cmp_k_sample_rows_ex", "cmp_decode_begin_ex", "cmp_decode_batch_begin_ex", "cmp_train_options",
                 "cmp_train_options_get", "cmp_train_grad_stats", "cmp_train_metrics_wait_ex", "cmp_k_adam_dev", "cmp_k_grad_clip_ws", "cmp_k_grad_clip",
                 "cmp_decode_grammar", "cmp_decode_grammar_state", "cmp_k_sample_banned", "cmp_score", "cmp_k_score_rows", "cmp_gemm_plan",
-                "cmp_attn_plan", "cmp_attn_caps", "cmp_decode_budget", "cmp_decode_budget_state"}
+                "cmp_attn_plan", "cmp_attn_caps", "cmp_decode_budget", "cmp_decode_budget_state", "cmp_dataset_create", "cmp_dataset_destroy",
+                "cmp_k_batch_rows", "cmp_dataset_batch", "cmp_train_step_dataset"}
 
 _lib = None
 

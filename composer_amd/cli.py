@@ -25,6 +25,7 @@ import numpy as np
 from . import config as cfgmod
 from . import dataset as ds
 from . import tfrecord
+from .augment import check_augment_options
 from .transformer import ModelSaveFrequencyMode, Transformer, check_train_options
 
 
@@ -139,6 +140,42 @@ def train_options_from(config, clip_norm=None, accumulate_steps=None, warmup_ste
                           pick(warmup_steps, 'warmup_steps', 0))
 
 
+def _augment_options(augment_transpose=0, augment_stretch=0.0, random_crop=False, source='transformer.train'):
+    try:
+        return check_augment_options(augment_transpose, augment_stretch, random_crop)
+    except (ValueError, TypeError) as e:
+        raise click.UsageError('{}: {}'.format(source, e))
+
+
+def augment_options_from(config, augment_transpose=None, augment_stretch=None, random_crop=None):
+    """(augment_transpose, augment_stretch, random_crop): the optional keys of `transformer.train` (absent in the reference's files:
+    off), overridden by the flags that were given; a bad value is a click.UsageError."""
+    t = config.transformer.train
+    pick = lambda flag, key, default: t.get(key, default) if flag is None else flag
+    return _augment_options(pick(augment_transpose, 'augment_transpose', 0), pick(augment_stretch, 'augment_stretch', 0.0),
+                            pick(random_crop, 'random_crop', False))
+
+
+def get_device_dataset(dataset_path, config, augment, max_files=None, rank=0, world_size=1, seed=0):
+    """The train split of a directory dataset as a DeviceDataset: the files and their order are get_dataset's, the batches are built
+    on the device (augment = (transpose, stretch, random_crop))."""
+    from composer_amd import grammar as gm
+    p = Path(dataset_path) / 'train'
+    if not p.exists():
+        logging.error('Could not get train dataset since \'{}\' has no train folder.'.format(dataset_path))
+        sys.exit(1)
+    files = ds.get_processed_files(p)
+    np.random.default_rng(seed).shuffle(files)
+    if max_files is not None:
+        files = files[:max_files]
+    d = config.dataset
+    settings = (d.time_step_increment, d.max_time_steps, d.velocity_bins)
+    transpose, stretch, random_crop = augment
+    return ds.DeviceDataset(ds.read_id_stream(files, expect_settings=settings), config.transformer.train.batch_size,
+                            config.transformer.model.window_size, gm.EventGrammar.from_dataset_params(*settings, rules=0), shuffle=True,
+                            seed=seed, rank=rank, world_size=world_size, random_crop=random_crop, transpose=transpose, stretch=stretch)
+
+
 def get_config_from_restoredir(restoredir):
     """cli.py:500-514"""
     path = Path(restoredir) / 'config.yml'
@@ -216,14 +253,26 @@ def summary(model_type, config_filepath):
                    'Overrides transformer.train.accumulate_steps.')
 @click.option('--warmup-steps', default=None, type=int,
               help='Linear learning-rate warm-up over this many optimiser steps (0 off). Overrides transformer.train.warmup_steps.')
+@click.option('--augment-transpose', default=None, type=int, metavar='N',
+              help='Transpose every training row by a random number of semitones in [-N, N] (0-12; 0 off), on the device. '
+                   'Overrides transformer.train.augment_transpose.')
+@click.option('--augment-stretch', default=None, type=float, metavar='FRAC',
+              help='Stretch the time axis of every training row by a random factor in [1 - FRAC, 1 + FRAC] (0-0.5; 0 off), on the '
+                   'device. Overrides transformer.train.augment_stretch.')
+@click.option('--random-crop/--no-random-crop', default=None,
+              help='Cut training rows at random offsets of the id stream instead of a fixed grid of windows. Overrides '
+                   'transformer.train.random_crop.')
 def train(model_type, dataset_path, logdir, restoredir, config_filepath, epochs, use_generator, max_files,
           save_frequency_mode, save_frequency, max_checkpoints, show_progress_bar, max_steps, checkpoint_format,
-          clip_norm, accumulate_steps, warmup_steps):
+          clip_norm, accumulate_steps, warmup_steps, augment_transpose, augment_stretch, random_crop):
     """Trains the specified model (cli.py:516-589)."""
     _require_transformer(model_type)
     for flag, value in (('--clip-norm', clip_norm), ('--accumulate-steps', accumulate_steps), ('--warmup-steps', warmup_steps)):
         if value is not None:                                    # refused from the arguments, before any device use
             _train_options(**{flag[2:].replace('-', '_'): value}, source=flag)
+    for flag, value in (('--augment-transpose', augment_transpose), ('--augment-stretch', augment_stretch)):
+        if value is not None:
+            _augment_options(**{flag[2:].replace('-', '_'): value}, source=flag)
     rank = int(os.environ.get('RANK', '0'))
     if restoredir is not None:
         config = get_config_from_restoredir(restoredir)
@@ -247,10 +296,17 @@ def train(model_type, dataset_path, logdir, restoredir, config_filepath, epochs,
             with open(config.filepath) as src, open(model_logdir / 'config.yml', 'w+') as dst:
                 dst.write(banner + '\n' + src.read())
     clip_norm, accumulate_steps, warmup_steps = train_options_from(config, clip_norm, accumulate_steps, warmup_steps)
+    augment = augment_options_from(config, augment_transpose, augment_stretch, random_crop)
+    if any(augment) and not Path(dataset_path).is_dir():         # refused before any device use
+        raise click.UsageError('--augment-transpose / --augment-stretch / --random-crop need a directory dataset: \'{}\' holds '
+                               'pre-cut batches (or does not exist)'.format(dataset_path))
     model, _ = create_model(model_type, config)
     rank, world = _init_distributed(model)
     _, seed = _runtime(config)
-    dataset = get_dataset(model_type, dataset_path, config, 'train', max_files=max_files, rank=rank, world_size=world, seed=seed)
+    if any(augment):
+        dataset = get_device_dataset(dataset_path, config, augment, max_files=max_files, rank=rank, world_size=world, seed=seed)
+    else:                                                        # everything off: the host-cut windows, exactly as before
+        dataset = get_dataset(model_type, dataset_path, config, 'train', max_files=max_files, rank=rank, world_size=world, seed=seed)
     input_shape = (config.transformer.train.batch_size, config.transformer.model.window_size)
     model.train(dataset, input_shape, model_logdir, restoredir=restoredir, epochs=epochs,
                 learning_rate=config.transformer.train.learning_rate, save_frequency_mode=save_frequency_mode,

@@ -185,6 +185,10 @@ struct cmp_model {
     int64_t stage_ticket[STAGES] = {-1, -1, -1};
     int64_t next_ticket = 0;
     int64_t stage_cap = 0;             // tokens per staging buffer
+    // cmp_train_step_dataset: the slot's plan on the device (uploaded from stage_host) and the status the kernel writes beside x / y
+    cmp_batch_row* stage_plan[STAGES] = {nullptr, nullptr, nullptr};
+    int32_t* stage_status[STAGES] = {nullptr, nullptr, nullptr};
+    int stage_plan_cap = 0;            // rows
     int lastB = 0, lastT = 0, last_past = 0;   // shape of the forward pass whose activations are held (cmp_present_get)
     int64_t fwd_gen = 0;               // bumped by every forward pass (train steps and decode prefill included): a Presents
                                        // object remembers the pass it came from and cmp_present_get_at refuses any other
@@ -235,6 +239,20 @@ template <typename Tp> static int dev_alloc(cmp_model* m, Tp** p, size_t bytes) 
     *p = (Tp*)q;
     return CMP_OK;
 }
+
+// the id stream of a training set in HBM (batch.hip; composer_hip.h, "device dataset")
+struct cmp_dataset {
+    cmp_ctx* ctx = nullptr;
+    uint16_t* ids_dev = nullptr;
+    int64_t n = 0;
+    int max_id = 0;
+    bool has_layout = false;
+    cmp_event_grammar layout = {};
+};
+// batch.hip: every refusal of the contract for a HOST plan (V = 0: no model to check the ids and the layout against), and the launch
+int batch_plan_check(const char* who, const cmp_dataset* ds, const cmp_batch_row* plan, int B, int W, int V);
+int batch_rows_run(hipStream_t s, const cmp_dataset* ds, const cmp_batch_row* plan_dev, int B, int W, int32_t* x, int32_t* y,
+                   int32_t* status);
 
 // elementwise.hip
 int embed_fwd_run(void* stream, const int32_t* ids, const float* wte, const float* wpe, void* out, int B, int T, int E, int pos0,

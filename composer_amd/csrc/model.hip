@@ -1602,6 +1602,24 @@ static int ensure_stages(cmp_model* m, int64_t tokens) {
     return CMP_OK;
 }
 
+// what follows once the ids of step `tk` are on their way into stage_dev[slot] (x then y) and the compute stream waits for them
+static int staged_step_run(cmp_model* m, int slot, int64_t tk, int B, int T, float lr, int64_t* ticket) {
+    cmp_ctx* c = m->ctx;
+    const int64_t n = (int64_t)B * T;
+    HIP_CHECK(hipMemsetAsync(&m->metrics->bad_ids, 0, sizeof(int), c->stream));
+    CHECK_RC(train_step_enqueue(m, m->stage_dev[slot], m->stage_dev[slot] + n, B, T, lr));
+    HIP_CHECK(hipMemcpyAsync(&m->stage_metrics[slot], m->metrics, sizeof(Metrics), hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(m->metrics_host, m->metrics, sizeof(Metrics), hipMemcpyDeviceToHost, c->stream));
+    CHECK_RC(fetch_clip(m, 0));
+    CHECK_RC(fetch_clip(m, 1 + slot));
+    m->stage_has_norm[slot] = m->last_has_norm;
+    HIP_CHECK(hipEventRecord(m->stage_done[slot], c->stream));
+    m->stage_ticket[slot] = tk;
+    m->next_ticket = tk + 1;
+    *ticket = tk;
+    return CMP_OK;
+}
+
 extern "C" int cmp_train_step_async(cmp_model* m, const int32_t* x, const int32_t* y, int B, int T, float lr, int64_t* ticket) {
     CMP_REQUIRE(m && x && y && ticket, "train_step_async: null argument");
     CHECK_RC(accum_shape_check(m, B, T));
@@ -1620,18 +1638,39 @@ extern "C" int cmp_train_step_async(cmp_model* m, const int32_t* x, const int32_
     HIP_CHECK(hipMemcpyAsync(m->stage_dev[slot], m->stage_host[slot], (size_t)n * 8, hipMemcpyHostToDevice, c->copy_stream));
     HIP_CHECK(hipEventRecord(m->stage_uploaded[slot], c->copy_stream));
     HIP_CHECK(hipStreamWaitEvent(c->stream, m->stage_uploaded[slot], 0));
-    HIP_CHECK(hipMemsetAsync(&m->metrics->bad_ids, 0, sizeof(int), c->stream));
-    CHECK_RC(train_step_enqueue(m, m->stage_dev[slot], m->stage_dev[slot] + n, B, T, lr));
-    HIP_CHECK(hipMemcpyAsync(&m->stage_metrics[slot], m->metrics, sizeof(Metrics), hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipMemcpyAsync(m->metrics_host, m->metrics, sizeof(Metrics), hipMemcpyDeviceToHost, c->stream));
-    CHECK_RC(fetch_clip(m, 0));
-    CHECK_RC(fetch_clip(m, 1 + slot));
-    m->stage_has_norm[slot] = m->last_has_norm;
-    HIP_CHECK(hipEventRecord(m->stage_done[slot], c->stream));
-    m->stage_ticket[slot] = tk;
-    m->next_ticket = tk + 1;
-    *ticket = tk;
-    return CMP_OK;
+    return staged_step_run(m, slot, tk, B, T, lr, ticket);
+}
+
+// cmp_train_step_async fed by a plan (composer_hip.h, "device dataset"): the slot's pinned stage carries B plan rows instead of 2 B T
+// ids, batch_rows_kernel writes x and y into the slot's device stage on the compute stream, and the step is the one above.
+extern "C" int cmp_train_step_dataset(cmp_model* m, cmp_dataset* ds, const cmp_batch_row* plan, int B, int T, float lr, int64_t* ticket) {
+    CMP_REQUIRE(m && ds && plan && ticket, "train_step_dataset: null argument");
+    CMP_REQUIRE(ds->ctx == m->ctx, "train_step_dataset: the dataset and the model belong to different contexts");
+    CHECK_RC(accum_shape_check(m, B, T));
+    CHECK_RC(batch_plan_check("train_step_dataset", ds, plan, B, T, m->V));
+    HIP_CHECK(hipSetDevice(m->ctx->device));
+    CHECK_RC(ensure_workspace(m, B, T));
+    const int64_t n = (int64_t)B * T;
+    CHECK_RC(ensure_stages(m, std::max<int64_t>(n, 2 * (int64_t)B)));          // (a plan row is as long as two ids and their targets)
+    if (m->stage_plan_cap < B) {
+        const int cap = std::max(B, m->capB);
+        for (int i = 0; i < cmp_model::STAGES; i++) {
+            CHECK_RC(dev_alloc(m, &m->stage_plan[i], (size_t)cap * sizeof(cmp_batch_row)));
+            CHECK_RC(dev_alloc(m, &m->stage_status[i], (size_t)cap * 8));
+        }
+        m->stage_plan_cap = cap;
+    }
+    const int64_t tk = m->next_ticket;
+    const int slot = (int)(tk % cmp_model::STAGES);
+    if (m->stage_ticket[slot] >= 0) HIP_CHECK(hipEventSynchronize(m->stage_done[slot]));    // slot still owned by step tk - STAGES
+    memcpy(m->stage_host[slot], plan, (size_t)B * sizeof(cmp_batch_row));
+    cmp_ctx* c = m->ctx;
+    HIP_CHECK(hipMemcpyAsync(m->stage_plan[slot], m->stage_host[slot], (size_t)B * sizeof(cmp_batch_row), hipMemcpyHostToDevice,
+                             c->copy_stream));
+    HIP_CHECK(hipEventRecord(m->stage_uploaded[slot], c->copy_stream));
+    HIP_CHECK(hipStreamWaitEvent(c->stream, m->stage_uploaded[slot], 0));
+    CHECK_RC(batch_rows_run(c->stream, ds, m->stage_plan[slot], B, T, m->stage_dev[slot], m->stage_dev[slot] + n, m->stage_status[slot]));
+    return staged_step_run(m, slot, tk, B, T, lr, ticket);
 }
 
 extern "C" int cmp_train_metrics_wait_ex(cmp_model* m, int64_t ticket, float* loss_out, float* acc_out, float* norm, float* scale) {

@@ -15,6 +15,8 @@ from pathlib import Path
 
 import numpy as np
 
+from . import augment
+
 MAGIC_INTEGER = 9223372036854775805          # IntegerEncodedEventSequence.get_encoding_type(), sequence.py:1866
 HEADER = struct.Struct('=Qhhh')              # 14 bytes
 assert HEADER.size == 14
@@ -118,6 +120,31 @@ def get_processed_files(dataset_path):
     return sorted(p.glob('**/*.data'))
 
 
+def window_order(n, batch_size, shuffle, seed, epoch):
+    """The order in which the n windows of a stream are visited in pass `epoch` (0-based): a pure function."""
+    if not shuffle:
+        return np.arange(n)
+    # tf.data shuffle(buffer) semantics (models/__init__.py:306-309): keep a buffer of `cap` elements, emit a
+    # uniformly random one, refill from the stream
+    rng = np.random.default_rng([seed, epoch])
+    cap = 500 * batch_size
+    if cap >= n:
+        return rng.permutation(n)
+    buf = list(range(cap))
+    out = np.empty(n, np.int64)
+    nxt = cap
+    for i in range(n):
+        j = int(rng.integers(0, len(buf)))
+        out[i] = buf[j]
+        if nxt < n:
+            buf[j] = nxt
+            nxt += 1
+        else:
+            buf[j] = buf[-1]
+            buf.pop()
+    return out
+
+
 class WindowDataset:
     """Re-iterable dataset of (x, y) int32 batches [B, W]; one pass = one epoch (reshuffled each iteration).
 
@@ -137,28 +164,7 @@ class WindowDataset:
         return len(self.windows) // (self.B * self.world)
 
     def _order(self):
-        n = len(self.windows)
-        if not self.shuffle:
-            return np.arange(n)
-        # tf.data shuffle(buffer) semantics (models/__init__.py:306-309): keep a buffer of `cap` elements, emit a
-        # uniformly random one, refill from the stream
-        rng = np.random.default_rng([self.seed, self._epoch])
-        cap = 500 * self.B
-        if cap >= n:
-            return rng.permutation(n)
-        buf = list(range(cap))
-        out = np.empty(n, np.int64)
-        nxt = cap
-        for i in range(n):
-            j = int(rng.integers(0, len(buf)))
-            out[i] = buf[j]
-            if nxt < n:
-                buf[j] = nxt
-                nxt += 1
-            else:
-                buf[j] = buf[-1]
-                buf.pop()
-        return out
+        return window_order(len(self.windows), self.B, self.shuffle, self.seed, self._epoch)
 
     def __iter__(self):
         order = self._order()
@@ -170,15 +176,99 @@ class WindowDataset:
             yield w[:, :-1].copy(), w[:, 1:].copy()
 
 
-def load_dataset(filepaths, batch_size, window_size, shuffle=True, seed=0, rank=0, world_size=1, expect_settings=None):
-    """models/__init__.py:238-313 without tf.data."""
+class DeviceBatch:
+    """One batch of a DeviceDataset: the plan (augment.PLAN_DTYPE [B]: offset, transpose, stretch per row) the device builds x and y
+    from.  Transformer.train hands it to train_step_dataset; `dataset.host_batch(batch.plan)` is the same batch on the host."""
+
+    def __init__(self, dataset, plan):
+        self.dataset, self.plan = dataset, plan
+
+    def __len__(self):
+        return len(self.plan)
+
+
+class DeviceDataset:
+    """Re-iterable dataset whose batches are built on the device from the id stream in HBM (include/composer_hip.h, "device
+    dataset"): one pass = one epoch of len(windows) // (B * world) batches, like WindowDataset, but a batch is a DeviceBatch.
+
+    Everything off (the default) visits WindowDataset's windows in WindowDataset's order for the same seed and epoch.  random_crop:
+    row offsets uniform in [0, n - (W + 1)] instead of the grid i * (W + 1).  transpose = N: k uniform in [-N, N] semitones per row.
+    stretch = s: f uniform over the integers [round(1024 (1 - s)), round(1024 (1 + s))] per row.  The draws come from a generator of
+    their own keyed by (seed, epoch, batch) -- the window order does not depend on them -- for the whole global batch, of which
+    rank r takes rows [r * B, (r + 1) * B).  layout: composer_amd.grammar.EventGrammar (or anything with its four layout fields);
+    needed as soon as a row is transposed or stretched."""
+
+    def __init__(self, ids, batch_size, window_size, layout=None, shuffle=True, seed=0, rank=0, world_size=1, random_crop=False,
+                 transpose=0, stretch=0.0):
+        self.transpose, self.stretch, self.random_crop = augment.check_augment_options(transpose, stretch, random_crop)
+        ids = np.asarray(ids)
+        if ids.size and (ids.min() < 0 or ids.max() > 65535):
+            raise ValueError('event ids must fit uint16')
+        self.ids = np.ascontiguousarray(ids, dtype=np.uint16)
+        self.B, self.W = int(batch_size), int(window_size)
+        self.layout = layout
+        if layout is None and (self.transpose or self.stretch):
+            raise ValueError('transpose / stretch augmentation needs the event layout')
+        self.shuffle, self.seed = shuffle, int(seed)
+        self.rank, self.world = int(rank), int(world_size)
+        self.n_windows = len(self.ids) // (self.W + 1)                  # drop_remainder, models/__init__.py:304
+        self._epoch = 0
+        self._order_of = (None, None)                                   # (epoch, its window order)
+
+    def __len__(self):
+        return self.n_windows // (self.B * self.world)
+
+    def _order(self, epoch):
+        if self._order_of[0] != epoch:
+            self._order_of = (epoch, window_order(self.n_windows, self.B, self.shuffle, self.seed, epoch))
+        return self._order_of[1]
+
+    def plan(self, epoch, batch):
+        """The plan of this rank's rows of batch `batch` of pass `epoch` (both 0-based): a pure function of the constructor's
+        arguments, so a restored run replays the plans of the run it continues."""
+        if not 0 <= batch < len(self):
+            raise IndexError('batch %d outside [0, %d)' % (batch, len(self)))
+        G = self.B * self.world
+        mine = slice(self.rank * self.B, (self.rank + 1) * self.B)
+        rng = np.random.default_rng([self.seed, int(epoch), int(batch), 0x617567])      # the augmentation's own stream
+        lo, hi = augment.stretch_bounds(self.stretch)
+        crop = rng.integers(0, len(self.ids) - (self.W + 1) + 1, size=G)
+        k = rng.integers(-self.transpose, self.transpose + 1, size=G)
+        f = rng.integers(lo, hi + 1, size=G)
+        out = np.zeros(self.B, augment.PLAN_DTYPE)
+        if self.random_crop:
+            out['offset'] = crop[mine]
+        else:
+            out['offset'] = self._order(int(epoch))[batch * G:(batch + 1) * G][mine] * (self.W + 1)
+        out['transpose'], out['stretch_q10'] = k[mine], f[mine]
+        return out
+
+    def host_batch(self, plan):
+        """(x, y) int32 [B, W] of a plan, by the host restatement (composer_amd.augment.build_batch)."""
+        x, y, _ = augment.build_batch(self.ids, self.layout, plan, self.W)
+        return x, y
+
+    def __iter__(self):
+        epoch = self._epoch
+        self._epoch += 1
+        for b in range(len(self)):                                      # batch(B, drop_remainder=True)
+            yield DeviceBatch(self, self.plan(epoch, b))
+
+
+def read_id_stream(filepaths, expect_settings=None):
+    """The ids of all files concatenated in file order (models/__init__.py:238-300), uint16."""
     parts = []
     for p in filepaths:
         ids, settings = read_data_file(p)
         if expect_settings is not None and tuple(settings) != tuple(expect_settings):
             raise ValueError('%s was preprocessed with %s but the config says %s' % (p, settings, tuple(expect_settings)))
         parts.append(ids)
-    ids = np.concatenate(parts) if parts else np.zeros(0, np.uint16)
+    return np.concatenate(parts) if parts else np.zeros(0, np.uint16)
+
+
+def load_dataset(filepaths, batch_size, window_size, shuffle=True, seed=0, rank=0, world_size=1, expect_settings=None):
+    """models/__init__.py:238-313 without tf.data."""
+    ids = read_id_stream(filepaths, expect_settings)
     return WindowDataset(ids, batch_size, window_size, shuffle, seed, rank, world_size)
 
 

@@ -17,7 +17,9 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
+from . import augment
 from . import checkpoint as ckpt
+from .dataset import DeviceBatch
 
 
 def slide_context_length(n, window, keep):
@@ -317,10 +319,14 @@ class Transformer:
         self._specs = self._param_specs()
         self._learning_rate = 1e-3
         self._dp = None          # (rank, nranks) once init_data_parallel() ran
+        self._datasets = {}      # id(DeviceDataset) -> (the dataset, its cmp_dataset in this model's context)
         self.initialize_parameters(self.seed)
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
+        for _, h in getattr(self, '_datasets', {}).values():      # device datasets live in this model's context: they go first
+            self._lib.cmp_dataset_destroy(h)
+        self._datasets = {}
         if getattr(self, '_h', None):
             self._lib.cmp_model_destroy(self._h)
             self._h = None
@@ -611,6 +617,43 @@ class Transformer:
         _lib.check(self._lib.cmp_train_step_async(self._h, x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), B, T, lr,
                                                   C.byref(ticket)), 'cmp_train_step_async')
         return int(ticket.value)
+
+    def _dataset_handle(self, dataset):
+        """The cmp_dataset of a composer_amd.dataset.DeviceDataset in this model's context: its id stream is uploaded on first use
+        and stays in HBM until the model is closed."""
+        got = self._datasets.get(id(dataset))
+        if got is None:
+            ids = np.ascontiguousarray(dataset.ids, dtype=np.uint16)
+            layout = dataset.layout
+            if layout is not None and not isinstance(layout, _lib.EventGrammar):
+                layout = layout.to_c()
+            h = C.c_void_p()
+            _lib.check(self._lib.cmp_dataset_create(self._ctx, ids.ctypes.data_as(C.c_void_p), len(ids),
+                                                    C.byref(layout) if layout is not None else None, C.byref(h)), 'cmp_dataset_create')
+            got = self._datasets[id(dataset)] = (dataset, h)
+        return got[1]
+
+    def train_step_dataset(self, dataset, plan, learning_rate=None):
+        """train_step_async with the batch built on the device: `plan` (augment.PLAN_DTYPE [B], or (offset, transpose, stretch)
+        triples) names the rows of `dataset` (a DeviceDataset); x and y never exist on the host.  Returns a ticket for
+        step_metrics() / step_metrics_ex()."""
+        plan = augment.as_plan(plan)
+        lr = self._learning_rate if learning_rate is None else float(learning_rate)
+        ticket = C.c_int64()
+        _lib.check(self._lib.cmp_train_step_dataset(self._h, self._dataset_handle(dataset), plan.ctypes.data_as(C.c_void_p), len(plan),
+                                                    int(dataset.W), lr, C.byref(ticket)), 'cmp_train_step_dataset')
+        return int(ticket.value)
+
+    def dataset_batch(self, dataset, plan):
+        """(x, y, status) of a plan as the device builds them (cmp_dataset_batch): int32 [B, W] twice and [B, 2]; for tests and
+        debugging -- composer_amd.augment.build_batch is the same on the host."""
+        plan = augment.as_plan(plan)
+        B, W = len(plan), int(dataset.W)
+        x, y, st = np.empty((B, W), np.int32), np.empty((B, W), np.int32), np.empty((B, 2), np.int32)
+        _lib.check(self._lib.cmp_dataset_batch(self._dataset_handle(dataset), plan.ctypes.data_as(C.c_void_p), B, W,
+                                               x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p)),
+                   'cmp_dataset_batch')
+        return x, y, st
 
     def step_metrics(self, ticket):
         """(loss, accuracy) of the step `ticket` was issued for; blocks until that step (not later ones) has finished."""
@@ -1085,11 +1128,15 @@ class Transformer:
                     if show_progress_bar and rank == 0 and (st % 10 == 1):
                         print('\r- loss: {:.4f} - accuracy: {:.4f}'.format(loss, acc), end='', flush=True)   # :939
 
-            for x, y in dataset:                                                 # :914
+            for batch in dataset:                                                # :914
                 lr = warmup_lr(learning_rate, step, warmup_steps)
                 micro += 1
                 ep_batches += 1
-                pending.append((self.train_step_async(x, y, lr), step, lr, micro == k))
+                if isinstance(batch, DeviceBatch):                               # built on the device from its plan
+                    ticket = self.train_step_dataset(batch.dataset, batch.plan, lr)
+                else:
+                    ticket = self.train_step_async(batch[0], batch[1], lr)
+                pending.append((ticket, step, lr, micro == k))
                 retire(1)
                 if micro < k:                                                    # a micro-step that does not update: no optimiser step yet
                     continue

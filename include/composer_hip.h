@@ -447,6 +447,50 @@ int cmp_decode_batch_begin_ex(cmp_model* m, const int32_t* prompts, const int32_
 int cmp_k_sample_rows_ex(void* stream, const float* logits, int ldz, int B, int V, const float* temperature, const int32_t* top_k,
                          const float* top_p, uint64_t seed, uint32_t counter, int32_t* ids_out);
 
+/* ---- device dataset: train-time augmentation (transpose, time stretch, random crop) in front of the train step --------------
+ * The reference augments offline (composer/dataset/preprocess.py:84-100 writes transposed and stretched copies of every piece).
+ * Here the id stream of the training set lives in HBM as uint16 and one kernel cuts, transposes and re-times the rows of a batch
+ * straight into the buffers the train step reads; the host sends 16 bytes per row.  Integers only: every result is bitwise what
+ * the host restatement composer_amd.augment computes, and no tolerance appears anywhere.  The contract:
+ *   Layout: given by the caller, never hard-coded -- the cmp_event_grammar fields note_on0, note_off0 (128 consecutive ids each,
+ *     id - base = the pitch), time_shift0 and time_shift_n = M (id time_shift0 + j counts j + 1 steps); the other fields are checked
+ *     as a grammar's and not used.
+ *   Row plan: (offset, transpose k, stretch f), f in 1/1024ths, 512 <= f <= 1536; f = 1024 is the identity.  |k| <= 127.
+ *   Source span: src = ids[offset : offset + S], S = min(2 (W + 1), n - offset); 0 <= offset <= n - (W + 1).
+ *   Transpose: a NOTE_ON / NOTE_OFF id of pitch p becomes pitch clip(p + k, 0, 127) (the reference's rule, sequence.py:379, per
+ *     token); every other id is untouched.
+ *   Stretch: R(t) = (t f + 512) >> 10 on 64-bit integers.  Walking src with the running unstretched time t, every maximal run of
+ *     consecutive TIME_SHIFT ids, r steps in all, is replaced by d = R(t + r) - R(t) steps, emitted as d / M ids of M steps and
+ *     then one id of d % M steps if that is not zero (notes.py:116-120); a run with d = 0 vanishes; then t += r.  The rounding is
+ *     cumulative: the emitted steps of a span sum to R(its total), nothing drifts.  A run cut by either end of the span is the
+ *     part inside it.
+ *   Output: out = the first W + 1 emitted ids; x = out[:W], y = out[1:].
+ *   Identity: f = 1024 does not walk at all: out = src[:W + 1], transposed (re-chunking would merge a non-canonical run such as
+ *     30 + 50 steps into one id of 80).
+ *   Fallback: a span that emits fewer than W + 1 ids gives the f = 1024 row, still transposed, with CMP_BATCH_FALLBACK set.
+ *   Status, int32 [B, 2]: (emitted ids clipped to W + 1 -- W + 1 for an identity row --, flag bits).
+ * Refusals (CMP_ERR_INVALID before any device work, the reason in cmp_last_error): an offset outside [0, n - (W + 1)]; f outside
+ *   [512, 1536]; |k| > 127; a plan that is not all identity on a dataset without a layout; W > 2^20; with a model, a dataset
+ *   whose largest id is >= V or whose layout is not a grammar layout inside [0, V) (the rules of cmp_decode_grammar). */
+#define CMP_BATCH_FALLBACK 1
+#define CMP_BATCH_REFUSED 2        /* cmp_k_batch_rows only: a row of the DEVICE plan the host entry points refuse; nothing read, x / y not written */
+typedef struct cmp_dataset cmp_dataset;
+typedef struct cmp_batch_row { int64_t offset; int32_t transpose; int32_t stretch_q10; } cmp_batch_row;
+/* Uploads the n ids once (host uint16) and records the largest.  layout: null only if every later plan is the identity. */
+int cmp_dataset_create(cmp_ctx* ctx, const uint16_t* ids, int64_t n, const cmp_event_grammar* layout, cmp_dataset** out);
+int cmp_dataset_destroy(cmp_dataset* ds);
+/* The kernel alone (dev pointers): ids_dev uint16 [n], plan_dev [B], x / y int32 [B, W], status int32 [B, 2]; layout (host) may be
+ * null for identity plans.  Reads ids_dev[offset : offset + S] of every row and nothing else of the stream. */
+int cmp_k_batch_rows(void* stream, const uint16_t* ids_dev, int64_t n, const cmp_event_grammar* layout, const cmp_batch_row* plan_dev,
+                     int B, int W, int32_t* x, int32_t* y, int32_t* status);
+/* Builds a batch from a HOST plan and reads it back (host int32 [B, W] twice, [B, 2]; status_host may be null): tests, debugging. */
+int cmp_dataset_batch(cmp_dataset* ds, const cmp_batch_row* plan, int B, int W, int32_t* x_host, int32_t* y_host, int32_t* status_host);
+/* cmp_train_step_async fed by a plan: the same step, the same kind of ticket (cmp_train_metrics_wait[_ex], train options and data
+ * parallelism unchanged).  The plan travels through the pinned stage of the ticket's slot -- B * 16 bytes in place of B * T * 8 --,
+ * the kernel writes x and y into that slot's device stage on the compute stream and the step reads them there.  ds and m must
+ * share a context. */
+int cmp_train_step_dataset(cmp_model* m, cmp_dataset* ds, const cmp_batch_row* plan, int B, int T, float lr, int64_t* ticket);
+
 /* ---- live kernel timing (bench.py roofline): HIP events around every launch of ONE kernel class on the
  * stream it is launched on.  cls: 0 gemm forward (A[M,K].B[K,N]), 1 gemm dgrad (B stored [N,K]), 2 gemm wgrad
  * (A stored [K,M]), 3 attention forward, 4 attention dQ, 5 attention dK/dV, 6 layernorm fwd, 7 adam.
