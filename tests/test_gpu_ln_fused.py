@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from oracle import transformer_oracle as O
+import row_bounds as RB
 
 pytestmark = pytest.mark.gpu
 FP32, BF16 = 0, 1
@@ -76,6 +77,12 @@ def ln64(x64, gamma, beta):
     mu = x64.mean(-1, keepdims=True)
     var = ((x64 - mu) ** 2).mean(-1, keepdims=True)
     return (x64 - mu) / np.sqrt(var + EPS) * gamma + beta
+
+
+def seg_offsets(E, amp=3.0):
+    """+amp, -amp, +amp, ... per 256-column segment: on rows of spread 2 the between-segment term 256 d^2 of the statistics merge is
+    two thirds of a row's M2 (row_bounds.SEG_SHARE_MIN is asserted where it is used), so a merge that forgot it would show."""
+    return np.repeat(amp * (-1.0) ** np.arange(E // 256), 256)[None, :]
 
 
 def rel(a, b):
@@ -221,7 +228,7 @@ def test_a_launch_that_cannot_carry_the_epilogue_fails_loudly(lib):
 def test_layernorm_backward_from_partials_writes_the_forward_output(lib, E, p):
     rows = 1500
     rng = np.random.default_rng(E + int(10 * p))
-    x = bf(rng.normal(1.0, 2.0, (rows, E)))
+    x = bf(rng.normal(1.0, 2.0, (rows, E)) + seg_offsets(E))
     dy = bf(rng.normal(0, 1.0, (rows, E)))
     res = bf(rng.normal(0, 1.0, (rows, E)))
     g = (1 + 0.3 * rng.normal(size=E)).astype(np.float32)
@@ -249,6 +256,12 @@ def test_layernorm_backward_from_partials_writes_the_forward_output(lib, E, p):
     want_mask = np.where(keep, stored / (1 - p), 0.0)
     assert rel(dmask.double().cpu().numpy(), want_mask) < 5e-3          # written also with p = 0: the fused path's masked copy
     assert rel(csum.cpu().numpy(), dmask.double().cpu().numpy().sum(0)) < 1e-4
+    # ... and every element inside its own bound (tests/row_bounds.py)
+    part_h, zero = part.cpu().numpy(), np.zeros(E, np.float32)
+    assert RB.merge_ref(part_h)["share"].min() >= RB.SEG_SHARE_MIN
+    print(RB.figures("ln_bwd_parts rows %d E %d p %g" % (rows, E, p), RB.ln_check(
+        BF16, x64, g, dy=dy64, part=part_h, beta=be, eps=EPS, resid=res, dx=dx, yout=yout, dgamma=dg, dbeta=db, start_g=zero, start_b=zero,
+        dmask=dmask, keep=keep if p > 0 else None, p=p, colsum=csum, start_cs=zero)))
 
 
 # --------------------------------------------------------------------------------------------- round 6: the backward pass without u / n
@@ -299,7 +312,7 @@ def test_layernorm_backward_takes_a_prescaled_gradient(lib, E, p):
     copy, its column sums and both parameter gradients are those of the plain form on the true gradient."""
     rows = 1300
     rng = np.random.default_rng(E + int(10 * p) + 1)
-    x = bf(rng.normal(1.0, 2.0, (rows, E)))
+    x = bf(rng.normal(1.0, 2.0, (rows, E)) + seg_offsets(E))
     x64 = x.double().cpu().numpy()
     mu, var = x64.mean(-1, keepdims=True), x64.var(-1, keepdims=True)
     rs = 1 / np.sqrt(var + EPS)
@@ -329,6 +342,13 @@ def test_layernorm_backward_takes_a_prescaled_gradient(lib, E, p):
     assert rel(db.cpu().numpy(), dy64.sum(0)) < 2e-4
     keep = O.dropout_keep_rows(5, 2, rows, E, p) if p > 0 else np.ones((rows, E), bool)
     assert rel(dmask.double().cpu().numpy(), np.where(keep, dx.double().cpu().numpy() / (1 - p), 0.0)) < 5e-3
+    # ... and every element inside its own bound (tests/row_bounds.py), on the statistics the merge kernel wrote
+    part_h, zero = part.cpu().numpy(), np.zeros(E, np.float32)
+    assert RB.merge_ref(part_h)["share"].min() >= RB.SEG_SHARE_MIN
+    print(RB.figures("ln_stats_merge rows %d E %d" % (rows, E), RB.merge_check(part_h, mean_d, rstd_d, EPS)))
+    print(RB.figures("ln_bwd_prescaled rows %d E %d p %g" % (rows, E, p), RB.ln_check(
+        BF16, x64, g, dy=dys, stats=(mean_d, rstd_d), prescaled=True, resid=res, dx=dx, dgamma=dg, dbeta=db, start_g=zero, start_b=zero,
+        dmask=dmask, keep=keep if p > 0 else None, p=p, colsum=csum, start_cs=zero)))
 
 
 # (module-level: tests/test_attn_plan_host.py holds the cases to the launcher's plan on the CPU)
