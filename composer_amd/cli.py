@@ -1,4 +1,4 @@
-"""`composer train | evaluate | generate | score | make-config | summary` for the Transformer hot path.
+"""`composer train | evaluate | generate | score | novelty | make-config | summary` for the Transformer hot path.
 
 Mirrors the commands, arguments and defaults of the reference's composer/cli.py (train :516-589, evaluate :591-615,
 generate :617-680, make-config :69-78, summary :424-440) with the TensorFlow model replaced by the HIP one.  Out of
@@ -8,7 +8,9 @@ Documented divergences: `--temperature 0` means greedy argmax (the reference div
 besides the reference's MIDI prompt (`--prompt`, read by composer_amd.midi instead of pretty_midi) a prompt can be given
 as event ids (`--prompt-ids` / `--prompt-data`), and an output path ending in `.data` gets event ids instead of a MIDI
 file; `--decode-mode` selects the literal loop of cli.py:663-676 or a real KV cache.  `score` (not in the reference) prints the
-per-event likelihood of MIDI / `.data` files under a restored model; `generate --keep-best` ranks the samples by it."""
+per-event likelihood of MIDI / `.data` files under a restored model; `generate --keep-best` ranks the samples by it.  `novelty` (not in
+the reference either) finds the longest verbatim match of every event of such files in a dataset split; `generate --novelty-against`
+prints it for the samples."""
 import datetime
 import json
 import logging
@@ -398,15 +400,33 @@ def evaluate(model_type, dataset_path, restoredir, use_generator, max_files):
 @click.option('--max-polyphony', default=None, type=int, metavar='N',
               help='Never more than N notes sounding at once (N >= 1): no NOTE_ON is sampled while N pitches sound. '
                    'Defaults to off.')
+@click.option('--novelty-against', default=None, metavar='DATASET',
+              help='After decoding, match every written sample against the train split of this directory dataset and print, per '
+                   'sample, its longest verbatim match, where it lies and the share of the sample covered by matches (the generated '
+                   'events only: the prompt is usually taken from a real piece). Defaults to off.')
+@click.option('--novelty-min-match', default=None, type=int, metavar='K',
+              help='--novelty-against: the shortest run that counts as a match. Defaults to 16.')
+@click.option('--novelty-transpose', default=None, type=int, metavar='N',
+              help='--novelty-against: also find copies transposed by up to N semitones (0-24). Defaults to 0.')
 def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt_data, prompt_length, generate_length,
              temperature, decode_mode, slide_keep, top_k, top_p, constrain, pitch_range, num_samples, keep_best, duration,
-             max_polyphony):
+             max_polyphony, novelty_against, novelty_min_match, novelty_transpose):
     """Generate a MIDI file (cli.py:617-680): MIDI prompt -> event ids -> model -> event ids -> MIDI.  An output path
     ending in `.data` gets the event ids in the dataset's binary format instead of a MIDI file.  With --num-samples N > 1
     the N sequences are decoded as one batch and written to OUTPUT-0 ... OUTPUT-{N-1} (same suffix); --top-k / --top-p apply
     to every sample, and so do --constrain / --pitch-range, --duration and --max-polyphony."""
     from composer_amd import notes as nt
     from composer_amd import grammar as gm
+    if novelty_against is None:                                  # refused from the arguments, before any device use
+        for flag, value in (('--novelty-min-match', novelty_min_match), ('--novelty-transpose', novelty_transpose)):
+            if value is not None:
+                raise click.UsageError('{} goes with --novelty-against.'.format(flag))
+    else:
+        novelty_min_match, novelty_transpose = _novelty_options(16 if novelty_min_match is None else novelty_min_match,
+                                                                novelty_transpose or 0, '--novelty-min-match', '--novelty-transpose')
+        _novelty_dataset_dir(novelty_against, 'train')
+        if not 1 <= generate_length <= 32768:
+            raise click.UsageError('--novelty-against: --length {} outside [1, 32768].'.format(generate_length))
     if duration is not None and not (duration > 0 and math.isfinite(duration)):      # refused from the arguments (a NaN fails too)
         raise click.UsageError('--duration {}: SECONDS must be a number > 0.'.format(duration))
     if max_polyphony is not None and max_polyphony < 1:
@@ -499,9 +519,18 @@ def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt
         click.echo('sample {}: {} events, {:.3f} s, finished {}'.format(
             i, len(ids), (st.g.time_steps - (st.t_end - timed.time_steps)) * d.time_step_increment / 1000.0,
             'yes' if st.done_at >= 0 else 'no'), err=True)
+    def novelty_report(samples):                                 # one line per written sample, from one batched device call
+        if novelty_against is None:
+            return
+        corpus = open_novelty_corpus(novelty_against, config, 'train')
+        for i, r in enumerate(corpus.match([np.asarray(s, np.int32) for s in samples], min_match=novelty_min_match,
+                                           transpose=novelty_transpose)):
+            click.echo('novelty: sample {} {}'.format(i, r.line()), err=True)
+        corpus.close()
     if num_samples == 1 and keep_best is None:
         ids = model.generate(x, generate_length, temperature=temperature, mode=decode_mode, **slide)
         report(0, ids)
+        novelty_report([ids])
         _write_generated(list(x) + ids.tolist(), out, d)         # prompt + generated (cli.py:676)
         click.echo(','.join(str(int(i)) for i in ids))
         return
@@ -516,6 +545,7 @@ def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt
         order = sorted(range(num_samples), key=lambda i: (-means[i], i))[:keep_best]
         click.echo('keep-best: kept {}'.format(','.join(str(i) for i in order)), err=True)
         batch = [batch[i] for i in order]
+    novelty_report(batch)
     for i, ids in enumerate(batch):
         report(i, ids)
         _write_generated(list(x) + ids.tolist(), out.with_name('{}-{}{}'.format(out.stem, i, out.suffix)), d)
@@ -601,6 +631,85 @@ def score(model_type, restoredir, files, slide_keep, by_event_type, json_out):
         keep = window // 2 if slide_keep is None else slide_keep
         with open(json_out, 'w') as fh:
             json.dump({'window_size': window, 'slide_keep': keep, 'files': report}, fh)
+
+
+def _novelty_options(min_match, transpose, flag_min_match='--min-match', flag_transpose='--transpose'):
+    from composer_amd import novelty as nv
+    if min_match < 1:
+        raise click.UsageError('{} {}: must be >= 1.'.format(flag_min_match, min_match))
+    if not 0 <= transpose <= nv.MAX_TRANSPOSE:
+        raise click.UsageError('{} {}: must be in [0, {}].'.format(flag_transpose, transpose, nv.MAX_TRANSPOSE))
+    return min_match, transpose
+
+
+def _novelty_dataset_dir(dataset_path, split):
+    p = Path(dataset_path)
+    if not p.is_dir() or not (p / split).is_dir():
+        raise click.UsageError('\'{}\' is not a directory dataset with a \'{}\' folder: the novelty check reads the pieces of '
+                               'a split one by one.'.format(dataset_path, split))
+    return p / split
+
+
+def open_novelty_corpus(dataset_path, config, split='train', max_files=None):
+    """The split of a directory dataset as a composer_amd.novelty.Corpus: its files in sorted order, one piece each, named relative to
+    the dataset path."""
+    from composer_amd import grammar as gm
+    from composer_amd import novelty as nv
+    root = _novelty_dataset_dir(dataset_path, split)
+    files = ds.get_processed_files(root)
+    if max_files is not None:
+        files = files[:max_files]
+    d = config.dataset
+    settings = (d.time_step_increment, d.max_time_steps, d.velocity_bins)
+    try:
+        ids, starts, names = ds.read_id_stream_pieces(files, expect_settings=settings)
+    except ValueError as e:
+        raise click.ClickException(str(e))
+    if len(ids) < 2:
+        raise click.ClickException('\'{}\' holds fewer than 2 events.'.format(root))
+    vel = ds.event_ranges(ds.event_value_ranges(*settings))[ds.VELOCITY]
+    names = [str(Path(f).relative_to(dataset_path)) for f in names]
+    return nv.Corpus(ids, starts, names, gm.EventGrammar.from_dataset_params(*settings, rules=0), (vel.start, len(vel)),
+                     time_step_ms=d.time_step_increment)
+
+
+@cli.command()
+@click.argument('dataset-path')
+@click.argument('files', nargs=-1, required=True)
+@click.option('-c', '--config', 'config_filepath', default=None)
+@click.option('--restoredir', default=None, type=str, help='Take the configuration from this model directory instead of -c.')
+@click.option('--split', default='train', help='The folder of DATASET-PATH to match against. Defaults to train.')
+@click.option('--max-files', default=None, type=int)
+@click.option('--min-match', default=16, type=int, help='The shortest run that counts as a match. Defaults to 16.')
+@click.option('--transpose', default=0, type=int, metavar='N', help='Also find copies transposed by up to N semitones (0-24). Defaults to 0.')
+@click.option('--ignore-velocity', is_flag=True, default=False, help='Every VELOCITY event equals every other.')
+@click.option('--json', 'json_out', default=None, help='Write the figures and the per-event arrays to this JSON file.')
+def novelty(dataset_path, files, config_filepath, restoredir, split, max_files, min_match, transpose, ignore_velocity, json_out):
+    """Is this piece new, or a passage of the dataset played back?  For every event of every FILE (.mid / .midi / .data) the longest
+    run that occurs verbatim in the split, on the device.  One line per file: events, the longest match in events and seconds, where it
+    lies (file, event offset, transposition) and the share of the file covered by matches of at least --min-match events.  A
+    time-stretched copy re-chunks its TIME_SHIFT runs and is not found."""
+    _novelty_options(min_match, transpose)                       # refused from the arguments, before any device use
+    if config_filepath is not None and restoredir is not None:
+        raise click.UsageError('-c and --restoredir both name a configuration: give one.')
+    _novelty_dataset_dir(dataset_path, split)
+    config = get_config_from_restoredir(restoredir) if restoredir is not None else cfgmod.get(config_filepath or get_default_config())
+    seqs = [read_score_file(f, config.dataset) for f in files]
+    for f, s in zip(files, seqs):
+        if len(s) == 0:
+            raise click.ClickException('{} holds no events.'.format(f))
+        if len(s) > 32768:
+            raise click.ClickException('{} holds {} events: at most 32768 per file.'.format(f, len(s)))
+    corpus = open_novelty_corpus(dataset_path, config, split, max_files)
+    reports = corpus.match(seqs, min_match=min_match, transpose=transpose, ignore_velocity=ignore_velocity)
+    corpus.close()
+    for f, r in zip(files, reports):
+        click.echo('{}: {}'.format(f, r.line()))
+    if json_out is not None:
+        with open(json_out, 'w') as fh:
+            json.dump({'dataset': str(dataset_path), 'split': split, 'min_match': min_match, 'transpose': transpose,
+                       'ignore_velocity': bool(ignore_velocity), 'corpus_events': int(len(corpus.ids)),
+                       'files': [dict(file=str(f), **r.to_dict()) for f, r in zip(files, reports)]}, fh)
 
 
 def _write_generated(all_ids, out, d):

@@ -259,6 +259,7 @@ extern "C" int cmp_dataset_destroy(cmp_dataset* d) {
     hipSetDevice(d->ctx->device);
     hipStreamSynchronize(d->ctx->stream);          // a train step that reads the stream may still be in flight
     if (d->ids_dev) (void)hipFree(d->ids_dev);
+    if (d->start_bits_dev) (void)hipFree(d->start_bits_dev);
     delete d;
     return CMP_OK;
 }

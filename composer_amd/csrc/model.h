@@ -248,6 +248,8 @@ struct cmp_dataset {
     int max_id = 0;
     bool has_layout = false;
     cmp_event_grammar layout = {};
+    uint32_t* start_bits_dev = nullptr;        // novelty.hip (cmp_dataset_set_pieces): bit p % 32 of word p / 32 = p is a piece start; null: one piece
+    int64_t n_pieces = 1;
 };
 // batch.hip: every refusal of the contract for a HOST plan (V = 0: no model to check the ids and the layout against), and the launch
 int batch_plan_check(const char* who, const cmp_dataset* ds, const cmp_batch_row* plan, int B, int W, int V);

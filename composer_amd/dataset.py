@@ -266,6 +266,26 @@ def read_id_stream(filepaths, expect_settings=None):
     return np.concatenate(parts) if parts else np.zeros(0, np.uint16)
 
 
+def read_id_stream_pieces(filepaths, expect_settings=None):
+    """read_id_stream with the pieces kept apart: (ids uint16, starts int64 [files], names [files]) -- starts[i] is the offset of
+    file i's first id in the stream (an empty file shares its offset with the next one).  A file without events after which nothing
+    follows is left out, so that every start lies inside the stream."""
+    parts, starts, names, off = [], [], [], 0
+    for p in filepaths:
+        ids, settings = read_data_file(p)
+        if expect_settings is not None and tuple(settings) != tuple(expect_settings):
+            raise ValueError('%s was preprocessed with %s but the config says %s' % (p, settings, tuple(expect_settings)))
+        parts.append(ids)
+        starts.append(off)
+        names.append(str(p))
+        off += len(ids)
+    while starts and starts[-1] >= off and len(starts) > 1:
+        starts.pop()
+        names.pop()
+    ids = np.concatenate(parts) if parts else np.zeros(0, np.uint16)
+    return ids, np.asarray(starts, np.int64), names
+
+
 def load_dataset(filepaths, batch_size, window_size, shuffle=True, seed=0, rank=0, world_size=1, expect_settings=None):
     """models/__init__.py:238-313 without tf.data."""
     ids = read_id_stream(filepaths, expect_settings)

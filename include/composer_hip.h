@@ -491,6 +491,56 @@ int cmp_dataset_batch(cmp_dataset* ds, const cmp_batch_row* plan, int B, int W, 
  * share a context. */
 int cmp_train_step_dataset(cmp_model* m, cmp_dataset* ds, const cmp_batch_row* plan, int B, int T, float lr, int64_t* ticket);
 
+/* ---- novelty check: the longest training-set match of every event of a sample ------------------------------------------------
+ * Is a sample new, or a passage of the training set played back?  A high cmp_score cannot tell: a memorised passage scores best.
+ * For every event of a query this section finds the longest run that occurs verbatim in the id stream of a cmp_dataset, optionally
+ * transposed (the reference's preprocess and the train-time augmentation both put transposed copies in front of the model).
+ * Integers only: every result is bitwise what the host restatement composer_amd.novelty.match_table computes, and no tolerance
+ * appears anywhere.  The contract:
+ *   Corpus: c[0..n), the uint16 id stream; n < 2^40.  Piece starts: a sorted (non-decreasing) list of offsets in [0, n), one per
+ *     file, the first of them 0; a dataset without a list is one piece.  A match never continues across a start.
+ *   Queries: B ragged rows x[b][0..lens[b]), int32 [B][ld]; 1 <= B <= 256, 1 <= lens[b] <= ld <= 32768, every id in [0, 65535).
+ *   Options: min_match >= 1; transpose N, 0 <= N <= 24; velocity0 / velocity_n: the VELOCITY id range folded into one class
+ *     (velocity_n = 0: velocities must match exactly; passed explicitly because cmp_event_grammar does not name the range).  The
+ *     layout (note_on0, note_off0: 128 consecutive ids each, id - base = the pitch) is required as soon as N > 0.
+ *   Token equality under a transposition k in [-N, N]: a NOTE_ON / NOTE_OFF of pitch p in the QUERY stands for pitch p + k if
+ *     0 <= p + k <= 127 and otherwise equals nothing -- never clipped: the augmentation's clip rule merges pitches and would invent
+ *     matches.  With velocity folding every id of the range equals every other, in query and corpus alike.  Every other id equals
+ *     itself.  Corpus tokens are never transposed.
+ *   Match length: m(s, p, k) = 0 if x[s] under k differs from c[p], else 1 + m(s + 1, p + 1, k), where the continuation counts as 0
+ *     when s + 1 == len, when p + 1 == n, or when p + 1 is a piece start.
+ *   Result per query position s: (len, pos, k) = the maximum of m(s, p, k) over all p and k under the total order: larger m; then
+ *     smaller |k|; then negative k before positive k; then smaller p.  A maximum below min_match gives (0, -1, 0), and so does every
+ *     position s >= lens[b] of a padded row.  The order is total, so the result does not depend on the order in which workgroups
+ *     finish: the device takes an atomic maximum of the 64-bit key (len << 48 | (255 - rank(k)) << 40 | (2^40 - 1 - p)), rank
+ *     0, -1, +1, -2, +2 ... -> 0, 1, 2, 3, 4 ...
+ *   Refusals (CMP_ERR_INVALID before any device work, the reason in cmp_last_error): B, ld, lens, min_match or N outside the ranges
+ *     above; a query id outside [0, 65535); N > 0 without a layout; a velocity range outside [0, 65536) or overlapping the note
+ *     ranges; note ranges outside [0, 65536) or overlapping each other; starts that are unsorted, outside [0, n) or do not begin
+ *     with 0; n >= 2^40.
+ *   Known limit: a time-stretched copy re-chunks its TIME_SHIFT runs and is not found. */
+typedef struct cmp_novelty_opts {
+    int32_t min_match;
+    int32_t transpose;         /* N: every k in [-N, N] is tried */
+    int32_t velocity0;
+    int32_t velocity_n;        /* 0: no folding */
+} cmp_novelty_opts;
+/* Records the piece starts of the dataset's stream (HOST array of n_pieces offsets) as a device bit vector of ceil(n / 32) words, bit
+ * p % 32 of word p / 32 set: p is a start.  Replaces an earlier list; cmp_dataset_destroy frees it. */
+int cmp_dataset_set_pieces(cmp_dataset* ds, const int64_t* starts, int n_pieces);
+/* HOST arrays: x int32 [B][ld], lens [B]; len_out / k_out int32 [B][ld], pos_out int64 [B][ld].  The layout is the dataset's.
+ * Synchronises. */
+int cmp_novelty(cmp_dataset* ds, const int32_t* x, const int32_t* lens, int B, int ld, const cmp_novelty_opts* opts, int32_t* len_out,
+                int64_t* pos_out, int32_t* k_out);
+/* The kernels alone (dev pointers; layout and opts on the host): ids_dev uint16 [n], n >= 1; start_bits_dev ceil(n / 32) words or
+ * null (one piece).  Writes every element of the three outputs.  No workspace is allocated: pos_out holds the packed keys
+ * between the matching kernel and the small kernel that unpacks them in place.  The host cannot see lens_dev and x_dev: a length is
+ * clamped to [0, ld] and a query id outside [0, 65535) equals nothing.  Reads ids_dev[0 .. n), the start bits of those positions,
+ * x_dev[b][0 .. lens[b]) and lens_dev[0 .. B), and nothing else. */
+int cmp_k_novelty(void* stream, const uint16_t* ids_dev, int64_t n, const uint32_t* start_bits_dev, const cmp_event_grammar* layout,
+                  const int32_t* x_dev, const int32_t* lens_dev, int B, int ld, const cmp_novelty_opts* opts, int32_t* len_out,
+                  int64_t* pos_out, int32_t* k_out);
+
 /* ---- live kernel timing (bench.py roofline): HIP events around every launch of ONE kernel class on the
  * stream it is launched on.  cls: 0 gemm forward (A[M,K].B[K,N]), 1 gemm dgrad (B stored [N,K]), 2 gemm wgrad
  * (A stored [K,M]), 3 attention forward, 4 attention dQ, 5 attention dK/dV, 6 layernorm fwd, 7 adam.
