@@ -48,6 +48,11 @@ class NoveltyOpts(C.Structure):
     _fields_ = [("min_match", C.c_int32), ("transpose", C.c_int32), ("velocity0", C.c_int32), ("velocity_n", C.c_int32)]
 
 
+class CopyGuardOpts(C.Structure):
+    """cmp_copy_guard_opts: the options of a copy guard (composer_amd.novelty.Corpus.guard builds it)."""
+    _fields_ = [("max_copy", C.c_int32), ("transpose", C.c_int32), ("velocity0", C.c_int32), ("velocity_n", C.c_int32)]
+
+
 class GemmPlanInfo(C.Structure):
     """cmp_gemm_plan_info: the launcher's decision for one cmp_k_gemm argument list (host only; tests/test_gemm_plan_host.py)."""
     _fields_ = [(n, C.c_int32) for n in ("family", "a_km", "b_km", "swap", "kind", "lnm", "np", "diag", "grid_x", "grid_y", "grid_z", "block")] + \
@@ -117,6 +122,9 @@ SIGNATURES = {
     "cmp_dataset_set_pieces": (_i, [_P, _P, _i]),
     "cmp_novelty": (_i, [_P, _P, _P, _i, _i, C.POINTER(NoveltyOpts), _P, _P, _P]),
     "cmp_k_novelty": (_i, [_P, _P, _i64, _P, C.POINTER(EventGrammar), _P, _P, _i, _i, C.POINTER(NoveltyOpts), _P, _P, _P]),
+    "cmp_decode_copy_guard": (_i, [_P, _i, _P, C.POINTER(CopyGuardOpts)]),
+    "cmp_decode_copy_guard_state": (_i, [_P, _i, _i, C.POINTER(_i64)]),
+    "cmp_k_copy_bans": (_i, [_P, _P, _i64, _P, C.POINTER(EventGrammar), C.POINTER(CopyGuardOpts), _P, _P, _i, _i, _i, _P, _P, _P]),
     "cmp_present_get": (_i, [_P, _i, _i, _i, _P]),
     "cmp_forward_generation": (_i, [_P, C.POINTER(_i64)]),
     "cmp_present_get_at": (_i, [_P, _i, _i, _i, _i64, _P]),
@@ -191,7 +199,8 @@ _ADDED_LATER = {"cmp_gemm_ln_scale_next", "cmp_attn_bwd_ln_next", "cmp_k_layerno
                 "cmp_train_options_get", "cmp_train_grad_stats", "cmp_train_metrics_wait_ex", "cmp_k_adam_dev", "cmp_k_grad_clip_ws", "cmp_k_grad_clip",
                 "cmp_decode_grammar", "cmp_decode_grammar_state", "cmp_k_sample_banned", "cmp_score", "cmp_k_score_rows", "cmp_gemm_plan",
                 "cmp_attn_plan", "cmp_attn_caps", "cmp_decode_budget", "cmp_decode_budget_state", "cmp_dataset_create", "cmp_dataset_destroy",
-                "cmp_k_batch_rows", "cmp_dataset_batch", "cmp_train_step_dataset", "cmp_dataset_set_pieces", "cmp_novelty", "cmp_k_novelty"}
+                "cmp_k_batch_rows", "cmp_dataset_batch", "cmp_train_step_dataset", "cmp_dataset_set_pieces", "cmp_novelty", "cmp_k_novelty",
+                "cmp_decode_copy_guard", "cmp_decode_copy_guard_state", "cmp_k_copy_bans"}
 
 _lib = None
 

@@ -408,15 +408,25 @@ def evaluate(model_type, dataset_path, restoredir, use_generator, max_files):
               help='--novelty-against: the shortest run that counts as a match. Defaults to 16.')
 @click.option('--novelty-transpose', default=None, type=int, metavar='N',
               help='--novelty-against: also find copies transposed by up to N semitones (0-24). Defaults to 0.')
+@click.option('--max-copy', default=None, type=int, metavar='M',
+              help='--novelty-against: never extend a verbatim match of prompt + sample with the train split past M events (1-64; '
+                   'copies transposed by up to --novelty-transpose semitones count): the event that would is not sampled. TIME_SHIFT '
+                   'events are exempt. Defaults to off.')
 def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt_data, prompt_length, generate_length,
              temperature, decode_mode, slide_keep, top_k, top_p, constrain, pitch_range, num_samples, keep_best, duration,
-             max_polyphony, novelty_against, novelty_min_match, novelty_transpose):
+             max_polyphony, novelty_against, novelty_min_match, novelty_transpose, max_copy):
     """Generate a MIDI file (cli.py:617-680): MIDI prompt -> event ids -> model -> event ids -> MIDI.  An output path
     ending in `.data` gets the event ids in the dataset's binary format instead of a MIDI file.  With --num-samples N > 1
     the N sequences are decoded as one batch and written to OUTPUT-0 ... OUTPUT-{N-1} (same suffix); --top-k / --top-p apply
     to every sample, and so do --constrain / --pitch-range, --duration and --max-polyphony."""
     from composer_amd import notes as nt
     from composer_amd import grammar as gm
+    if max_copy is not None:                                     # refused from the arguments, before any device use
+        from composer_amd import novelty as nv
+        if novelty_against is None:
+            raise click.UsageError('--max-copy goes with --novelty-against: DATASET is the corpus that must not be copied.')
+        if not 1 <= max_copy <= nv.MAX_COPY:
+            raise click.UsageError('--max-copy {}: must be in [1, {}].'.format(max_copy, nv.MAX_COPY))
     if novelty_against is None:                                  # refused from the arguments, before any device use
         for flag, value in (('--novelty-min-match', novelty_min_match), ('--novelty-transpose', novelty_transpose)):
             if value is not None:
@@ -519,22 +529,37 @@ def generate(model_type, restoredir, output_filepath, prompt, prompt_ids, prompt
         click.echo('sample {}: {} events, {:.3f} s, finished {}'.format(
             i, len(ids), (st.g.time_steps - (st.t_end - timed.time_steps)) * d.time_step_increment / 1000.0,
             'yes' if st.done_at >= 0 else 'no'), err=True)
+    guard_corpus = None
+    if max_copy is not None:
+        # the corpus goes to the device before the decode: every draw is checked against it (cmp_decode_copy_guard)
+        guard_corpus = open_novelty_corpus(novelty_against, config, 'train')
+        slide.update(copy_guard=guard_corpus.guard(max_copy, transpose=novelty_transpose))
+        click.echo('copy-guard: max-copy {} transpose {} against {} events'.format(max_copy, novelty_transpose, len(guard_corpus.ids)),
+                   err=True)
+
+    def guard_report(batched, n):                                # one line per decoded sample: the columns the rule took away
+        if guard_corpus is not None:
+            for i in range(n):
+                click.echo('copy-guard: sample {} banned_columns {}'.format(i, model.decode_copy_guard_state(batched, i)), err=True)
+
     def novelty_report(samples):                                 # one line per written sample, from one batched device call
         if novelty_against is None:
             return
-        corpus = open_novelty_corpus(novelty_against, config, 'train')
+        corpus = guard_corpus or open_novelty_corpus(novelty_against, config, 'train')
         for i, r in enumerate(corpus.match([np.asarray(s, np.int32) for s in samples], min_match=novelty_min_match,
                                            transpose=novelty_transpose)):
             click.echo('novelty: sample {} {}'.format(i, r.line()), err=True)
         corpus.close()
     if num_samples == 1 and keep_best is None:
         ids = model.generate(x, generate_length, temperature=temperature, mode=decode_mode, **slide)
+        guard_report(False, 1)
         report(0, ids)
         novelty_report([ids])
         _write_generated(list(x) + ids.tolist(), out, d)         # prompt + generated (cli.py:676)
         click.echo(','.join(str(int(i)) for i in ids))
         return
     batch = model.generate_batch([x] * num_samples, generate_length, temperature=temperature, mode=decode_mode, **slide)
+    guard_report(True, num_samples)
     if keep_best is not None:
         # prompt ++ ids of every sample under the scoring contract (the run's --slide-keep when it slid); only the generated
         # positions count.  Sample i was drawn with seed + i.

@@ -620,11 +620,12 @@ __global__ __launch_bounds__(256) void dec_slide_sample_kernel(const float* __re
                                                                DecRowList rl, int r0, int32_t* __restrict__ ids, int cap,
                                                                const float* __restrict__ wte, const float* __restrict__ wpe,
                                                                float* __restrict__ x, int E, int keep, float* __restrict__ zout,
-                                                               const unsigned* __restrict__ banw) {
+                                                               const unsigned* __restrict__ banw, int ban_stride) {
     extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
     __shared__ int bi[4];
     const int tid = threadIdx.x, b = rl.row[r0 + blockIdx.x];
+    banw += (int64_t)b * ban_stride;       // a guarded chain: the row's own words (stride 0: the chain's static words)
     const float* z = logits + ((int64_t)blockIdx.x * keep + keep - 1) * ldz;
     DecRow* rs = st + b;
     const unsigned ctr = rs->rng;
@@ -720,8 +721,9 @@ static int enqueue_token_step(cmp_model* m, DecodeState* d) {
     }
     CHECK_RC(launch_gemv2(s, 0, 1, R.x, m->P + m->off_lnf_g, m->P + m->off_lnf_b, eps, m->P + m->off_wte, nullptr, nullptr,
                           R.logits, nullptr, E, m->V, m->D));
+    CHECK_RC(dec_enqueue_guard(m, d->rows, d->w, DecRowList{}, -1, 0, 1));
     dec_sample2_kernel<<<1, 256, trunc_lds_bytes(m->V), s>>>(R.logits, 0, m->V, R.st, R.ids, R.cap, m->P + m->off_wte,
-                                                             m->P + m->off_wpe, R.x, E, m->W, 0, d->w.banw);
+                                                             m->P + m->off_wpe, R.x, E, m->W, 0, dec_ban_words(R, d->w));
     KERNEL_CHECK();
     return CMP_OK;
 }
@@ -806,6 +808,10 @@ int dec_rows_alloc(cmp_model* m, DecRows& R, int B) {
     CHECK_RC(dec_alloc(al, &R.logits, Bz * m->ldz * 4));
     CHECK_RC(dec_alloc(al, &R.prompts, Bz * W * 4));
     CHECK_RC(dec_alloc(al, &R.plen, Bz * 4));
+    CHECK_RC(dec_alloc(al, &R.cgwords, Bz * grammar_words(m->V) * 4));
+    CHECK_RC(dec_alloc(al, &R.cghist, Bz * DEC_GUARD_MAX_M * 4));
+    CHECK_RC(dec_alloc(al, &R.cglens, Bz * 4));
+    CHECK_RC(dec_alloc(al, &R.cgcount, Bz * 8));
     R.kc.assign(m->L, nullptr);
     R.vc.assign(m->L, nullptr);
     for (int i = 0; i < m->L; i++) {
@@ -831,7 +837,7 @@ int dec_check_budget(const char* who, const DecGrammarCfg& c, const DecBudgetCfg
 }
 
 DecRow dec_row_init(int mode, int P, unsigned seed, float temperature, int top_k, float top_p, const DecGrammarCfg& c,
-                    const DecBudgetCfg& bc, const int32_t* prompt) {
+                    const DecBudgetCfg& bc, const int32_t* prompt, bool guarded) {
     DecRow h = {};
     h.pos = (mode == CMP_DECODE_KV) ? P : 0;     // position of the first generated token when it is fed back
     h.advance = (mode == CMP_DECODE_KV) ? 1 : 0;
@@ -844,7 +850,7 @@ DecRow dec_row_init(int mode, int P, unsigned seed, float temperature, int top_k
     h.bd.t_end = bc.time_steps > 0 ? h.gr.time_steps + bc.time_steps : 0;
     h.bd.max_polyphony = bc.max_polyphony;
     h.bd.done_at = -1;
-    if (bc.time_steps > 0 || bc.max_polyphony > 0) h.gr.active = 1;
+    if (bc.time_steps > 0 || bc.max_polyphony > 0 || guarded) h.gr.active = 1;      // a guarded row always reads its ban words
     return h;
 }
 
@@ -869,13 +875,15 @@ int dec_prefill_row(cmp_model* m, DecRows& R, const DecWeights& w, int b, const 
     hipStream_t s = m->ctx->stream;
     CHECK_RC(ensure_workspace(m, 1, P));
     HIP_CHECK(hipMemcpyAsync(m->x_dev, prompt, (size_t)P * 4, hipMemcpyHostToDevice, s));
-    if (R.keep > 0) HIP_CHECK(hipMemcpyAsync(R.prompts + (int64_t)b * m->W, m->x_dev, (size_t)P * 4, hipMemcpyDeviceToDevice, s));
+    if (R.keep > 0 || R.guard.on())
+        HIP_CHECK(hipMemcpyAsync(R.prompts + (int64_t)b * m->W, m->x_dev, (size_t)P * 4, hipMemcpyDeviceToDevice, s));
     CHECK_RC(model_forward(m, m->x_dev, 1, P, false, 0));
     if (R.mode == CMP_DECODE_KV) {
         DecRowList rl = {};
         rl.row[0] = (unsigned char)b;
         CHECK_RC(dec_cache_fill(m, R, P, rl, 0, 1));
     }
+    CHECK_RC(dec_enqueue_guard(m, R, w, DecRowList{}, -1, b, 1));
     CHECK_RC(decb_launch_sample(m, R, w, m->logits + (int64_t)(P - 1) * m->ldz, 1, b, 1));
     HIP_CHECK(hipStreamSynchronize(s));
     return CMP_OK;
@@ -898,12 +906,82 @@ int dec_enqueue_slide(cmp_model* m, DecRows& R, const DecWeights& w, const DecRo
         KERNEL_CHECK();
         CHECK_RC(model_forward(m, m->x_dev, nc, keep, false, 0));
         CHECK_RC(dec_cache_fill(m, R, keep, rl, r0, nc));
+        if (r0 == 0) CHECK_RC(dec_enqueue_guard(m, R, w, rl, nb, 0, R.B));      // one scan for all the rows of this slide
         dec_slide_sample_kernel<<<nc, 256, trunc_lds_bytes(m->V), s>>>(m->logits, m->ldz, m->V, R.st, rl, r0, R.ids, R.cap, m->P + m->off_wte,
-                                                                       m->P + m->off_wpe, R.x, m->E, keep, R.logits, w.banw);
+                                                                       m->P + m->off_wpe, R.x, m->E, keep, R.logits, dec_ban_words(R, w),
+                                                                       dec_ban_stride(m, R));
         KERNEL_CHECK();
         R.fwd_calls++;
     }
     R.row_slides += nb;
+    return CMP_OK;
+}
+
+// ---- copy guard (composer_hip.h, "copy guard"; the scan itself: copyguard.hip) ----
+// Row b = row0 + blockIdx.x: the last min(t, M) ids of its history prompt ++ ids so far, t = plen + produced, into hist[b][0 ..) and
+// their count into lens[b] -- or 0 for a row that does not draw in this launch (held, or not in the list) and for a row outside PLAY,
+// whose samplers do not read the ban words: such a row gets its static words alone and adds nothing to its counter.
+__global__ __launch_bounds__(64) void dec_guard_gather_kernel(const DecRow* __restrict__ st, const int32_t* __restrict__ prompts,
+                                                              const int32_t* __restrict__ plen, const int32_t* __restrict__ ids,
+                                                              int cap, int W, int M, int row0, DecRowList rl, int nb,
+                                                              int32_t* __restrict__ hist, int32_t* __restrict__ lens) {
+    const int b = row0 + blockIdx.x, tid = threadIdx.x;
+    const DecRow* rs = st + b;
+    bool live = nb < 0 ? rs->hold == 0 : false;
+    for (int i = 0; i < nb; i++) live = live || rl.row[i] == b;
+    const bool any = (rs->gr.sounding[0] | rs->gr.sounding[1] | rs->gr.sounding[2] | rs->gr.sounding[3]) != 0u || rs->gr.pedal != 0;
+    live = live && budget_phase(rs->bd.t_end, rs->gr.time_steps, any) == CMP_BUDGET_PLAY;
+    const int P = min(max(plen[b], 0), W);
+    const int t = P + min(max(rs->produced, 0), cap);
+    const int n = live ? min(t, M) : 0;
+    if (tid == 0) lens[b] = n;
+    if (tid < n) {
+        const int j = t - n + tid;                    // 0 <= j < t: j < P <= W reads the prompt, j - P < produced <= cap the ids
+        hist[(int64_t)b * DEC_GUARD_MAX_M + tid] = j < P ? prompts[(int64_t)b * W + j] : ids[(int64_t)b * cap + (j - P)];
+    }
+}
+
+int dec_enqueue_guard(cmp_model* m, DecRows& R, const DecWeights& w, const DecRowList& rl, int nb, int row0, int nrows) {
+    if (!R.guard.on()) return CMP_OK;
+    hipStream_t s = m->ctx->stream;
+    const int M = R.guard.opts.max_copy, nw = grammar_words(m->V);
+    dec_guard_gather_kernel<<<nrows, 64, 0, s>>>(R.st, R.prompts, R.plen, R.ids, R.cap, m->W, M, row0, rl, nb, R.cghist, R.cglens);
+    KERNEL_CHECK();
+    return copy_guard_run(s, R.guard, R.cghist + (int64_t)row0 * DEC_GUARD_MAX_M, R.cglens + row0, nrows, DEC_GUARD_MAX_M, m->V, w.banw,
+                          R.cgwords + (int64_t)row0 * nw, R.cgcount + row0, true);
+}
+
+extern "C" int cmp_decode_copy_guard(cmp_model* m, int batched, cmp_dataset* ds, const cmp_copy_guard_opts* opts) {
+    CMP_REQUIRE(m, "decode_copy_guard: null model");
+    DecGuardCfg& cur = m->guard[batched ? 1 : 0];       // read by the chain's next begin
+    DecGuardCfg g;
+    if (ds) {
+        CMP_REQUIRE(opts, "decode_copy_guard: null options");
+        CHECK_RC(copy_guard_check("decode_copy_guard", ds->n, ds->has_layout ? &ds->layout : nullptr, opts));
+        CMP_REQUIRE(ds->ctx->device == m->ctx->device, "decode_copy_guard: the dataset lives on device %d, the model on device %d",
+                    ds->ctx->device, m->ctx->device);
+        g.ids = ds->ids_dev;
+        g.n = ds->n;
+        g.start_bits = ds->start_bits_dev;
+        g.layout = ds->layout;
+        g.opts = *opts;
+    }
+    g.epoch = cur.epoch + 1;
+    cur = g;
+    return CMP_OK;
+}
+
+extern "C" int cmp_decode_copy_guard_state(cmp_model* m, int batched, int row, int64_t* banned_columns) {
+    CMP_REQUIRE(m && banned_columns, "decode_copy_guard_state: null argument");
+    const DecRows* R = dec_rows_of(m, batched);
+    CHECK_RC(dec_require_begun("decode_copy_guard_state", R && R->begun, dec_begin_name(batched)));
+    if (batched) CMP_REQUIRE(row >= 0 && row < R->B, "decode_copy_guard_state: row %d outside the batch of %d rows", row, R->B);
+    else CMP_REQUIRE(row == 0, "decode_copy_guard_state: row %d of the batch-1 chain (row 0 only)", row);
+    *banned_columns = 0;
+    if (!R->guard.on()) return CMP_OK;
+    HIP_CHECK(hipSetDevice(m->ctx->device));
+    HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+    HIP_CHECK(hipMemcpy(banned_columns, R->cgcount + row, 8, hipMemcpyDeviceToHost));
     return CMP_OK;
 }
 
@@ -937,23 +1015,36 @@ static int decode_begin_impl(cmp_model* m, const int32_t* prompt, int P, int mod
     if (!d) m->dec = d = new DecodeState();
     DecRows& R = d->rows;
     R.begun = false;
+    // a guard attached or detached since the capture: the chain is captured again, with or without the scan
+    const bool recapture = d->built && d->guard_epoch != m->guard[0].epoch;
+    if (recapture) {
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (d->exec) hipGraphExecDestroy(d->exec);
+        if (d->graph) hipGraphDestroy(d->graph);
+        d->exec = nullptr;
+        d->graph = nullptr;
+    }
     if (!d->built) CHECK_RC(dec_rows_alloc(m, R, 1));
     CHECK_RC(dec_weights_refresh(m, d->w));
     R.B = 1;
     R.mode = mode;
     R.keep = keep;
     R.row_slides = R.fwd_calls = 0;
-    const DecRow h = dec_row_init(mode, P, (unsigned)seed, temperature, top_k, top_p, m->gram[0], m->budget[0], prompt);
+    R.guard = m->guard[0];
+    const DecRow h = dec_row_init(mode, P, (unsigned)seed, temperature, top_k, top_p, m->gram[0], m->budget[0], prompt, R.guard.on());
     HIP_CHECK(grammar_upload(m->gram[0], m->V, d->w.banw, s));
     HIP_CHECK(hipMemcpyAsync(R.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
-    if (keep > 0) HIP_CHECK(hipMemcpyAsync(R.plen, &P, 4, hipMemcpyHostToDevice, s));
+    if (keep > 0 || R.guard.on()) HIP_CHECK(hipMemcpyAsync(R.plen, &P, 4, hipMemcpyHostToDevice, s));
+    if (R.guard.on()) HIP_CHECK(hipMemsetAsync(R.cgcount, 0, 8, s));
     CHECK_RC(dec_prefill_row(m, R, d->w, 0, prompt, P));
     R.produced = 1;
     R.returned = 0;
     d->pos = h.pos;
-    if (!d->built) {                            // the per-token chain, captured once per decode state
+    if (!d->built || recapture) {               // the per-token chain, captured once per decode state and guard
+        d->built = false;
         if (graph_on) CHECK_RC(dec_capture(s, [&] { return enqueue_token_step(m, d); }, &d->graph, &d->exec));
         d->graph_on = graph_on;
+        d->guard_epoch = m->guard[0].epoch;
         d->built = true;
     }
     R.begun = true;

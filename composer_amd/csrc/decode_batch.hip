@@ -266,11 +266,12 @@ __global__ __launch_bounds__(256) void decb_sample_kernel(const float* __restric
                                                           int row0, int32_t* __restrict__ ids, int cap,
                                                           const float* __restrict__ wte, const float* __restrict__ wpe,
                                                           float* __restrict__ x, int E, int W, int first,
-                                                          const unsigned* __restrict__ banw) {
+                                                          const unsigned* __restrict__ banw, int ban_stride) {
     extern __shared__ __attribute__((aligned(16))) unsigned char trunc_lds[];
     __shared__ float bv[4];
     __shared__ int bi[4];
     const int tid = threadIdx.x, b = row0 + blockIdx.x;
+    banw += (int64_t)b * ban_stride;       // a guarded chain: the row's own words (stride 0: the chain's static words)
     const float* z = logits + (int64_t)blockIdx.x * ldz;
     DecRow* rs = st + b;
     if (rs->hold) return;                  // the row's slide draws this step's id (workgroup-uniform); its grammar state stays
@@ -382,7 +383,8 @@ static int launch_attn(hipStream_t s, cmp_model* m, const DecRows& R, int layer,
 
 int decb_launch_sample(cmp_model* m, DecRows& R, const DecWeights& w, const float* logits, int nrows, int row0, int first) {
     decb_sample_kernel<<<nrows, 256, trunc_lds_bytes(m->V), m->ctx->stream>>>(logits, m->ldz, m->V, R.st, row0, R.ids, R.cap, m->P + m->off_wte,
-                                                                            m->P + m->off_wpe, R.x, m->E, m->W, first, w.banw);
+                                                                            m->P + m->off_wpe, R.x, m->E, m->W, first, dec_ban_words(R, w),
+                                                                            dec_ban_stride(m, R));
     KERNEL_CHECK();
     return CMP_OK;
 }
@@ -410,6 +412,7 @@ static int enqueue_batch_step(cmp_model* m, DecodeBatchState* d, int B) {
     }
     CHECK_RC(launch_proj(s, 0, 1, R.x, m->P + m->off_lnf_g, m->P + m->off_lnf_b, eps, m->P + m->off_wte, nullptr, nullptr,
                          R.logits, m->ldz, nullptr, E, m->V, m->D, B));
+    CHECK_RC(dec_enqueue_guard(m, R, d->w, DecRowList{}, -1, 0, B));
     return decb_launch_sample(m, R, d->w, R.logits, B, 0, 0);
 }
 
@@ -450,6 +453,11 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
         decb_drop_graphs(d);
         d->graph_on = graph_on;
     }
+    if (d->guard_epoch != m->guard[1].epoch) {  // a guard attached or detached since: the chains are captured again, with or without the scan
+        HIP_CHECK(hipStreamSynchronize(s));
+        decb_drop_graphs(d);
+        d->guard_epoch = m->guard[1].epoch;
+    }
     if (B > R.capB) {                           // the captured chains hold the old buffers: they go with them
         HIP_CHECK(hipStreamSynchronize(s));
         decb_drop_graphs(d);
@@ -460,16 +468,19 @@ static int decode_batch_begin_impl(cmp_model* m, const int32_t* prompts, const i
     R.mode = mode;
     R.keep = keep;
     R.row_slides = R.fwd_calls = 0;
+    R.guard = m->guard[1];
     std::vector<DecRow> h(B);
     d->pos.assign(B, 0);
     for (int b = 0; b < B; b++) {
         h[b] = dec_row_init(mode, lens[b], (unsigned)(seed + (uint64_t)b), temperature ? temperature[b] : temperature0,
-                            top_k ? top_k[b] : 0, top_p ? top_p[b] : 1.0f, m->gram[1], m->budget[1], prompts + (int64_t)b * ld);
+                            top_k ? top_k[b] : 0, top_p ? top_p[b] : 1.0f, m->gram[1], m->budget[1], prompts + (int64_t)b * ld,
+                            R.guard.on());
         d->pos[b] = h[b].pos;
     }
     HIP_CHECK(grammar_upload(m->gram[1], m->V, d->w.banw, s));
     HIP_CHECK(hipMemcpyAsync(R.st, h.data(), (size_t)B * sizeof(DecRow), hipMemcpyHostToDevice, s));
-    if (keep > 0) HIP_CHECK(hipMemcpyAsync(R.plen, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    if (keep > 0 || R.guard.on()) HIP_CHECK(hipMemcpyAsync(R.plen, lens, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    if (R.guard.on()) HIP_CHECK(hipMemsetAsync(R.cgcount, 0, (size_t)B * 8, s));
     // prefill, one row at a time through the batch-1 chain's own call: a row's first id is the batch-1 first id for seed + b
     for (int b = 0; b < B; b++) CHECK_RC(dec_prefill_row(m, R, d->w, b, prompts + (int64_t)b * ld, lens[b]));
     R.B = B;

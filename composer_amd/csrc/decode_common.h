@@ -457,6 +457,7 @@ static inline hipError_t grammar_upload(const DecGrammarCfg& c, int V, unsigned*
 
 // ---- the state of a chain ----------------------------------------------------------------------------------------------------
 #define DECB_MAX_ROWS 256
+#define DEC_GUARD_MAX_M 64
 
 struct DecRow {          // device-resident per-row loop state (the captured chain does not depend on it); the batch-1 chain has one
     int pos;             // position id of the token about to be consumed (first member: all the batch-1 attention reads)
@@ -503,6 +504,13 @@ struct DecRows {
     int32_t* prompts = nullptr;         // [capB][W]
     int32_t* plen = nullptr;            // [capB]
     std::vector<float*> kc, vc;         // per layer, [capB] x K [H][D/4][W][4], V [H][W][D]
+    // copy guard (composer_hip.h, "copy guard"): the guard this decode began under (off: the buffers are not touched), every row's
+    // own ban words -- what a guarded chain's samplers read in place of the static words --, its window of history ids and its counter
+    DecGuardCfg guard;
+    uint32_t* cgwords = nullptr;        // [capB][ceil(V / 32)]
+    int32_t* cghist = nullptr;          // [capB][DEC_GUARD_MAX_M]
+    int32_t* cglens = nullptr;          // [capB]
+    unsigned long long* cgcount = nullptr;      // [capB] banned_columns
     std::vector<void*> allocs;          // sized by capB (replaced when a larger B is asked for)
     int B = 0, mode = 0;
     int keep = 0;                       // 0: plain kv / literal decode
@@ -519,6 +527,7 @@ struct DecodeState {                    // the batch-1 chain (decode.hip)
     int pos = 0;                        // host mirror of the row's position (kv-mode window check; when to slide)
     bool built = false;                 // buffers allocated, chain captured (reused by later cmp_decode_begin calls)
     bool graph_on = false;
+    int64_t guard_epoch = 0;            // DecGuardCfg::epoch the chain was captured under
 };
 
 struct DecodeBatchState {               // the batched chain (decode_batch.hip)
@@ -526,6 +535,7 @@ struct DecodeBatchState {               // the batched chain (decode_batch.hip)
     DecRows rows;
     std::map<int, std::pair<hipGraph_t, hipGraphExec_t>> graphs;     // captured chain per B
     bool graph_on = true;
+    int64_t guard_epoch = 0;            // DecGuardCfg::epoch the chains were captured under
     std::vector<int> pos;               // host mirror of each row's position (kv-mode window check; which rows slide at which step)
 };
 
@@ -564,8 +574,14 @@ void dec_rows_free(DecRows& R);
 int dec_rows_alloc(cmp_model* m, DecRows& R, int B);
 int dec_check_budget(const char* who, const DecGrammarCfg& c, const DecBudgetCfg& bc);      // the begin-time refusals of a budget
 DecRow dec_row_init(int mode, int P, unsigned seed, float temperature, int top_k, float top_p, const DecGrammarCfg& c,
-                    const DecBudgetCfg& bc, const int32_t* prompt);
+                    const DecBudgetCfg& bc, const int32_t* prompt, bool guarded = false);
 int dec_prefill_row(cmp_model* m, DecRows& R, const DecWeights& w, int b, const int32_t* prompt, int P);
 int dec_enqueue_slide(cmp_model* m, DecRows& R, const DecWeights& w, const DecRowList& rl, int nb);
+// Copy guard: the scan in front of a draw of rows row0 .. row0 + nrows - 1 (nothing on an unguarded chain).  nb < 0: every row of the
+// range that is not held draws; nb >= 0: the rows rl.row[0 .. nb) do.  Every other row of the range gets its static words alone.
+int dec_enqueue_guard(cmp_model* m, DecRows& R, const DecWeights& w, const DecRowList& rl, int nb, int row0, int nrows);
+// the ban words the samplers of a chain read, and their stride per row (0: one vector for all rows)
+static inline const unsigned* dec_ban_words(const DecRows& R, const DecWeights& w) { return R.guard.on() ? R.cgwords : w.banw; }
+static inline int dec_ban_stride(const cmp_model* m, const DecRows& R) { return R.guard.on() ? grammar_words(m->V) : 0; }
 // decode_batch.hip: decb_sample_kernel for rows row0 .. row0 + nrows - 1 from `logits` (one row each, stride ldz)
 int decb_launch_sample(cmp_model* m, DecRows& R, const DecWeights& w, const float* logits, int nrows, int row0, int first);

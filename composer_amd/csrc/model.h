@@ -22,6 +22,19 @@ struct DecBudgetCfg {
     int32_t max_polyphony = 0;
 };
 
+// ... and cmp_decode_copy_guard (ids null: off).  Plain values: the dataset's pointers as they were when the guard was attached.
+// epoch: bumped by every accepted cmp_decode_copy_guard call of the chain -- a captured per-token chain holds these values in its
+// nodes, so a begin that finds another epoch than the one its graphs were captured under drops them
+struct DecGuardCfg {
+    const uint16_t* ids = nullptr;
+    int64_t n = 0;
+    const uint32_t* start_bits = nullptr;
+    cmp_event_grammar layout = {};
+    cmp_copy_guard_opts opts = {};
+    int64_t epoch = 0;
+    bool on() const { return ids != nullptr; }
+};
+
 struct GradClipStats { double norm; float scale; float factor; };     // elementwise.hip: grad_clip_finish_kernel
 
 struct Metrics {
@@ -224,6 +237,7 @@ struct cmp_model {
     DecodeBatchState* decb = nullptr;  // batched decode (decode_batch.hip): its own buffers, KV caches and captured chains
     DecGrammarCfg gram[2];             // event grammar of the batch-1 chain [0] and of the batched chain [1] (cmp_decode_grammar)
     DecBudgetCfg budget[2];            // time budget and polyphony cap of the two chains, likewise (cmp_decode_budget)
+    DecGuardCfg guard[2];              // copy guard of the two chains, likewise (cmp_decode_copy_guard)
     int gemm_role = -1;                // profiler class of the GEMMs being enqueued (0 while the forward pass is)
 
     // dropout seed of this replica: the model seed with the data-parallel rank folded in (rank 0: the seed itself)
@@ -251,6 +265,13 @@ struct cmp_dataset {
     uint32_t* start_bits_dev = nullptr;        // novelty.hip (cmp_dataset_set_pieces): bit p % 32 of word p / 32 = p is a piece start; null: one piece
     int64_t n_pieces = 1;
 };
+// novelty.hip: the refusals of the novelty options that the copy guard shares (layout and velocity ranges, n)
+int nov_check(const char* who, int64_t n, const cmp_event_grammar* g, int B, int ld, const cmp_novelty_opts* o);
+// copyguard.hip: the scan in front of a draw -- words_out [B][nw] = static words | copy bans, count_out [B] (accumulate: added to, not
+// zeroed: the per-row counter of a chain)
+int copy_guard_check(const char* who, int64_t n, const cmp_event_grammar* layout, const cmp_copy_guard_opts* o);
+int copy_guard_run(hipStream_t s, const DecGuardCfg& g, const int32_t* hist, const int32_t* lens, int B, int ld, int V,
+                   const uint32_t* static_words, uint32_t* words_out, unsigned long long* count_out, bool accumulate);
 // batch.hip: every refusal of the contract for a HOST plan (V = 0: no model to check the ids and the layout against), and the launch
 int batch_plan_check(const char* who, const cmp_dataset* ds, const cmp_batch_row* plan, int B, int W, int V);
 int batch_rows_run(hipStream_t s, const cmp_dataset* ds, const cmp_batch_row* plan_dev, int B, int W, int32_t* x, int32_t* y,

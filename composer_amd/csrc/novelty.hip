@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void novelty_unpack_kernel(const int32_t* __re
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 // every refusal that can be decided from the host arguments the bare launch and the dataset entry point share
-static int nov_check(const char* who, int64_t n, const cmp_event_grammar* g, int B, int ld, const cmp_novelty_opts* o) {
+int nov_check(const char* who, int64_t n, const cmp_event_grammar* g, int B, int ld, const cmp_novelty_opts* o) {
     CMP_REQUIRE(n >= 1 && n < (1LL << 40), "%s: n=%lld ids outside [1, 2^40)", who, (long long)n);
     CMP_REQUIRE(B >= 1 && B <= NOV_MAX_B, "%s: B=%d outside [1, %d]", who, B, NOV_MAX_B);
     CMP_REQUIRE(ld >= 1 && ld <= NOV_MAX_LD, "%s: ld=%d outside [1, %d]", who, ld, NOV_MAX_LD);

@@ -5,13 +5,25 @@
 needs no model) and turns the arrays into `NoveltyReport`s: the longest match and where it lies, the share of the query covered by
 reported matches, the longest match's duration.
 
-Known limit: a time-stretched copy re-chunks its TIME_SHIFT runs and is not found."""
+Known limit: a time-stretched copy re-chunks its TIME_SHIFT runs and is not found.
+
+Copy guard (include/composer_hip.h, "copy guard"; the scan: composer_amd/csrc/copyguard.hip).  With a guard attached to a decode
+chain no draw extends a verbatim match of the row's history h = prompt ++ ids so far (t = len(h)) with the corpus past max_copy = M
+events.  `copy_bans` restates the ban set of one draw: column v is banned iff v is not a TIME_SHIFT id, t >= M, and there are a corpus
+position p, M <= p < n, and a k in [-N, N] such that h[t - M + j] under k equals c[p - M + j] for j = 0 .. M - 1, v under k equals
+c[p], and none of p - M + 1 .. p is a piece start.  Token equality under k is `map_query`'s (a moved pitch that leaves 0 .. 127
+equals nothing, folded velocities equal each other, corpus tokens are never transposed).  TIME_SHIFT ids are exempt: no dynamic rule
+of the decode ever bans one, the time budget relies on it.  The bans are ORed with the chain's static vector and the grammar's and
+budget's bans in PLAY and ignored in ENDING and DONE.  So in prompt ++ ids every drawn event that is the (M + 1)-th or a later event
+of a match is a TIME_SHIFT; with a prompt of at most M events every match of more than M events consists of TIME_SHIFT events only
+from its (M + 1)-th event on."""
 import ctypes as C
 
 import numpy as np
 
 MAX_B, MAX_LD, MAX_TRANSPOSE = 256, 32768, 24
 MAX_N = 1 << 40
+MAX_COPY = 64
 
 
 def rank_order(transpose):
@@ -145,6 +157,80 @@ def coverage_of(length):
     return float((np.cumsum(edge[:L]) > 0).sum()) / L
 
 
+def check_guard_options(max_copy, transpose, velocity_range, layout):
+    """Every refusal of a copy guard's options that the library states, as a ValueError -> (M, N, (velocity0, velocity_n))."""
+    max_copy, transpose = int(max_copy), int(transpose)
+    if not 1 <= max_copy <= MAX_COPY:
+        raise ValueError('max_copy=%d outside [1, %d]' % (max_copy, MAX_COPY))
+    if not 0 <= transpose <= MAX_TRANSPOSE:
+        raise ValueError('transpose=%d outside [0, %d]' % (transpose, MAX_TRANSPOSE))
+    if layout is None:
+        raise ValueError('a copy guard needs the event layout (which ids are TIME_SHIFT and notes)')
+    _, N, vel = check_options(1, transpose, velocity_range, layout)
+    return max_copy, N, vel
+
+
+def copy_bans(corpus, starts, history, V, layout, max_copy, transpose=0, velocity_range=None):
+    """bool [V]: the columns the copy rule bans for a row whose history is `history` (the contract at the top of this file), all
+    corpus positions at once per k."""
+    M, N, vel = check_guard_options(max_copy, transpose, velocity_range, layout)
+    c = np.asarray(corpus).astype(np.int64).reshape(-1)
+    n = len(c)
+    if n < 1:
+        raise ValueError('the corpus is empty')
+    st = check_starts(starts, n)
+    h = np.asarray(history, np.int64).reshape(-1)
+    V = int(V)
+    bans = np.zeros(V, bool)
+    if len(h) < M or n <= M:
+        return bans
+    w = h[len(h) - M:]
+    w = np.where((w < 0) | (w >= 65535), -1, w)                   # such an id equals nothing
+    cols = np.arange(V, dtype=np.int64)
+    cols = np.where(cols >= 65535, -1, cols)
+    cf = np.where((c >= vel[0]) & (c < vel[0] + vel[1]), vel[0], c)
+    is_start = np.zeros(n + 1, np.int64)
+    is_start[st] = 1
+    cs = np.cumsum(is_start)
+    p = np.arange(M, n)
+    free = (cs[p] - cs[p - M]) == 0                               # no start among p - M + 1 .. p
+    for k in range(-N, N + 1):
+        wk = map_query(w, k, layout, vel)
+        hit = free.copy()
+        for j in range(M):
+            hit &= cf[j:j + n - M] == wk[j]                      # c[p - M + j] for p = M .. n - 1
+        if not hit.any():
+            continue
+        targets = np.unique(cf[M:][hit])
+        vk = map_query(cols, k, layout, vel)
+        bans |= np.isin(vk, targets) & (vk >= 0)
+    ts0, tsn = int(layout.time_shift0), int(layout.time_shift_n)
+    bans[max(ts0, 0):max(ts0 + tsn, 0)] = False
+    return bans
+
+
+class CopyGuard:
+    """What `Transformer.generate(..., copy_guard=)` takes: a corpus and the options of the rule (`Corpus.guard` builds it)."""
+
+    def __init__(self, corpus, max_copy, transpose=0, ignore_velocity=False):
+        if ignore_velocity and corpus.velocity_range is None:
+            raise ValueError('ignore_velocity needs the corpus\'s velocity_range')
+        self.corpus = corpus
+        self.velocity_range = corpus.velocity_range if ignore_velocity else None
+        self.max_copy, self.transpose, self._vel = check_guard_options(max_copy, transpose, self.velocity_range, corpus.layout)
+
+    def attach_args(self):
+        """(cmp_dataset handle, cmp_copy_guard_opts) for cmp_decode_copy_guard; opens the corpus's dataset."""
+        from . import _lib
+        self.corpus._open()
+        return self.corpus._ds, _lib.CopyGuardOpts(self.max_copy, self.transpose, self._vel[0], self._vel[1])
+
+    def bans(self, history, V):
+        """`copy_bans` of one history under this guard (host)."""
+        return copy_bans(self.corpus.ids, self.corpus.starts, history, V, self.corpus.layout, self.max_copy, self.transpose,
+                         self.velocity_range)
+
+
 class NoveltyReport:
     """The arrays of one query and what they say.  longest: (length, query position, file name, offset in that file, k) of the longest
     match (the first of equals; (0, -1, None, -1, 0) when nothing reached min_match); coverage: `coverage_of`; longest_seconds: the
@@ -205,6 +291,7 @@ class Corpus:
         self.layout, self.velocity_range, self.time_step_ms, self.device = layout, velocity_range, time_step_ms, int(device)
         check_options(1, 0, velocity_range, layout)
         self._lib = self._ctx = self._ds = None
+        self.generation = 0                      # counts the datasets opened: a model re-attaches a guard whose corpus was reopened
 
     def _open(self):
         if self._ds is not None:
@@ -221,6 +308,7 @@ class Corpus:
         _lib.check(self._lib.cmp_dataset_create(ctx, self.ids.ctypes.data_as(C.c_void_p), len(self.ids),
                                                 C.byref(layout) if layout is not None else None, C.byref(h)), 'cmp_dataset_create')
         self._ds = h
+        self.generation += 1
         _lib.check(self._lib.cmp_dataset_set_pieces(h, self.starts.ctypes.data_as(C.c_void_p), len(self.starts)), 'cmp_dataset_set_pieces')
 
     def close(self):
@@ -242,6 +330,11 @@ class Corpus:
         if ignore_velocity and self.velocity_range is None:
             raise ValueError('ignore_velocity needs the corpus\'s velocity_range')
         return check_options(min_match, transpose, self.velocity_range if ignore_velocity else None, self.layout)
+
+    def guard(self, max_copy, transpose=0, ignore_velocity=False):
+        """The `CopyGuard` to pass as `Transformer.generate(..., copy_guard=)` / `generate_batch(..., copy_guard=)`: decode never
+        extends a match with this corpus past max_copy events.  Keep the corpus open while a model holds the guard."""
+        return CopyGuard(self, max_copy, transpose, ignore_velocity)
 
     def match_arrays(self, sequences, min_match=16, transpose=0, ignore_velocity=False):
         """The padded [B, ld] arrays of cmp_novelty for up to 256 ragged sequences, one call."""

@@ -828,6 +828,33 @@ class Transformer:
         _lib.check(self._lib.cmp_decode_budget(self._h, batched, steps, cap), 'cmp_decode_budget')
         on[batched] = True
 
+    def _set_decode_copy_guard(self, batched, copy_guard):
+        """cmp_decode_copy_guard for the chain the next begin call belongs to (a `composer_amd.novelty.CopyGuard`, or None: off);
+        switched off again only if an earlier call of this object switched it on (as _set_decode_grammar).  The object holds the
+        guard -- and through it the corpus's dataset -- for as long as it is attached."""
+        held = getattr(self, '_copy_guard', None)
+        if held is None:
+            held = self._copy_guard = [None, None]
+        if copy_guard is None:
+            if held[batched] is not None:
+                _lib.check(self._lib.cmp_decode_copy_guard(self._h, batched, None, None), 'cmp_decode_copy_guard')
+                held[batched] = None
+            return
+        ds, opts = copy_guard.attach_args()            # (opens the corpus's dataset again if it was closed since)
+        key = (copy_guard, copy_guard.corpus.generation)
+        if held[batched] is not None and held[batched][0] is key[0] and held[batched][1] == key[1]:
+            return                                     # attached already, to this very dataset: the chain keeps its captured graph
+        _lib.check(self._lib.cmp_decode_copy_guard(self._h, batched, ds, C.byref(opts)), 'cmp_decode_copy_guard')
+        held[batched] = key
+
+    def decode_copy_guard_state(self, batched=False, row=0):
+        """banned_columns of a row after its latest id (cmp_decode_copy_guard_state): the columns the copy rule banned, summed over
+        the row's draws in PLAY, that the static vector had not.  0 on a chain begun without a guard."""
+        n = C.c_int64(0)
+        _lib.check(self._lib.cmp_decode_copy_guard_state(self._h, 1 if batched else 0, int(row), C.byref(n)),
+                   'cmp_decode_copy_guard_state')
+        return n.value
+
     def decode_budget_state(self, batched=False, row=0):
         """(steps_left, phase, done_at) of a row after its latest id (cmp_decode_budget_state): the steps of its time budget
         still to go, `composer_amd.grammar.PLAY` / `ENDING` / `DONE`, and the number of ids it had produced when it became DONE
@@ -868,7 +895,7 @@ class Transformer:
         return [out[b, :(d if d >= 0 else n)].copy() for b, d in enumerate(done)]
 
     def generate(self, prompt_ids, length, temperature=1.0, mode='kv', seed=None, slide_keep=None, top_k=0, top_p=1.0,
-                 grammar=None, banned_ids=None, duration_steps=None, max_polyphony=0):
+                 grammar=None, banned_ids=None, duration_steps=None, max_polyphony=0, copy_guard=None):
         """Returns `length` generated ids.  mode 'literal' restates cli.py:663-676 as written (no `past`),
         mode 'kv' is model(x, past=presents).  temperature <= 0 -> greedy argmax.  mode 'kv-slide' is 'kv' that goes on past
         window_size: when the cache is full the last `slide_keep` tokens (default window_size // 2) are re-encoded from position 0
@@ -882,12 +909,15 @@ class Transformer:
         duration_steps the generated part lasts exactly that many time steps and ends with every note released and the pedal
         up: `length` is then the cap on events, the ids come back as soon as the row is done (fewer than `length` of them), or
         all `length` ids when the cap came first (`decode_budget_state()[2]` is then -1).  max_polyphony: never more than that
-        many pitches sounding at once (0: no cap)."""
+        many pitches sounding at once (0: no cap).
+        copy_guard (`Corpus.guard(max_copy, ...)`): no draw extends a verbatim match of prompt ++ ids with the corpus past max_copy
+        events (cmp_decode_copy_guard; TIME_SHIFT ids are exempt); `decode_copy_guard_state()` counts the columns it banned."""
         p = np.ascontiguousarray(np.asarray(prompt_ids, dtype=np.int32).reshape(-1))
         top_k, top_p = check_sampling(top_k, top_p)
         steps, cap = self._check_decode_budget(grammar, banned_ids, duration_steps, max_polyphony)
         self._set_decode_grammar(0, grammar, banned_ids)
         self._set_decode_budget(0, steps, cap)
+        self._set_decode_copy_guard(0, copy_guard)
         filters = top_k != 0 or top_p != 1.0
         if mode == 'kv-slide':
             keep = self._slide_keep(slide_keep)
@@ -923,7 +953,7 @@ class Transformer:
         return out
 
     def generate_batch(self, prompts, length, temperature=1.0, mode='kv', seed=None, slide_keep=None, top_k=0, top_p=1.0,
-                       grammar=None, banned_ids=None, duration_steps=None, max_polyphony=0):
+                       grammar=None, banned_ids=None, duration_steps=None, max_polyphony=0, copy_guard=None):
         """B independent sequences decoded together: returns int32 [B, length].  `prompts` is a list of id sequences (ragged
         rows allowed); row b samples with seed + b, so it equals `generate(prompts[b], length, seed=seed + b)` in its first id
         and depends on nothing but its own prompt and seed.  Modes, temperature and slide_keep as in `generate`; in 'kv-slide'
@@ -933,10 +963,12 @@ class Transformer:
         duration_steps / max_polyphony as in `generate`: one budget for all rows, each row charged from its own prompt's time.
         With duration_steps the result is a list of B arrays of unequal length (row b cut where it was done, or all `length`
         ids when the cap came first); decoding stops when every row is done, so a finished row costs at most the filler steps
-        until the slowest row ends (plus the rest of that chunk of BUDGET_CHUNK steps)."""
+        until the slowest row ends (plus the rest of that chunk of BUDGET_CHUNK steps).
+        copy_guard as in `generate`: one guard for all rows, history and counter each row's own."""
         steps, cap = self._check_decode_budget(grammar, banned_ids, duration_steps, max_polyphony)
         self._set_decode_grammar(1, grammar, banned_ids)
         self._set_decode_budget(1, steps, cap)
+        self._set_decode_copy_guard(1, copy_guard)
         rows = [np.asarray(p, dtype=np.int64).reshape(-1) for p in prompts]
         slide = mode == 'kv-slide'
         if slide:

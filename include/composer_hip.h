@@ -541,6 +541,67 @@ int cmp_k_novelty(void* stream, const uint16_t* ids_dev, int64_t n, const uint32
                   const int32_t* x_dev, const int32_t* lens_dev, int B, int ld, const cmp_novelty_opts* opts, int32_t* len_out,
                   int64_t* pos_out, int32_t* k_out);
 
+/* ---- copy guard: decode never extends a training-set match past max_copy ----------------------------------------------------
+ * The novelty check diagnoses a copy; this section prevents one.  With a guard attached, at every draw of a decode chain the id
+ * that would complete a verbatim run of more than max_copy events somewhere in the corpus cannot be drawn: n-gram blocking
+ * against the training set, decided exactly (the corpus itself is scanned at every step: no Bloom filter, no false positive),
+ * inside the per-token chain, with no host round trip.  Integers only: the ban set is bitwise what the host restatement
+ * composer_amd.novelty.copy_bans computes.  The contract:
+ *   Configuration, per chain: a cmp_dataset with its stream c[0..n), n < 2^40, and its piece starts (none: one piece); the dataset
+ *     must have a layout (the rule has to know the TIME_SHIFT and the note ids).  max_copy M, 1 <= M <= 64; transpose N,
+ *     0 <= N <= 24; velocity0 / velocity_n as in cmp_novelty_opts (velocity_n = 0: no folding).
+ *   Token equality under a transposition k is cmp_novelty's, word for word: a history NOTE_ON / NOTE_OFF of pitch p stands for
+ *     p + k if that stays in 0..127 and otherwise equals nothing (never clipped); folded velocities all equal each other; every other
+ *     id equals itself; an id outside [0, 65535) equals nothing.  Corpus tokens are never transposed.
+ *   History of a row: h = prompt ++ ids so far, t = len(h).  The prompt counts: a prompt taken from a training piece must not simply
+ *     be continued.  The history is a function of the whole sequence: a kv-slide re-encode does not shorten it, the literal mode
+ *     carries it, and a held row of the batched chain is left alone.
+ *   Copy bans of a draw: column v is banned iff v is not a TIME_SHIFT id, t >= M, and there are a corpus position p, M <= p < n, and
+ *     a k in [-N, N] such that h[t - M + j] under k equals c[p - M + j] for j = 0 .. M - 1, v under k equals c[p], and none of
+ *     p - M + 1 .. p is a piece start (p - M may be one).  So with c[p] a note of pitch q the banned column is the note of pitch q - k
+ *     when that is in 0..127; with c[p] in a folded velocity range the whole range is banned; otherwise it is c[p] itself.
+ *   TIME_SHIFT is exempt because the grammar section promises that no dynamic rule ever bans a TIME_SHIFT, and the time budget
+ *     relies on that to reach t_end.
+ *   Consequence: in prompt ++ ids, every DRAWN event that is the (M + 1)-th or a later event of a match (cmp_novelty's, same N and
+ *     folding) is a TIME_SHIFT; with a prompt of at most M events, every match of more than M events consists of TIME_SHIFT events
+ *     only from its (M + 1)-th event on.  (A prompt that is itself a passage of the corpus stays the match it is.)
+ *   Composition: the copy bans are ORed with the chain's static vector and, in PLAY, with the grammar's and the budget's bans.  In
+ *     ENDING and DONE they are ignored exactly as the static vector is: the ending must always be able to finish.  The draw equals,
+ *     bit for bit, cmp_k_sample_ex on the logits row with the whole ban set at -inf (same temperature, top_k, top_p, seed and draw
+ *     counter).  The samplers are the grammar's: a guarded row reads its own ban words, which the scan fills in front of every draw
+ *     (the first draw after the prefill, the draws of a slide and the literal mode included).
+ *   Counter, per row on the device: banned_columns = the sum over the row's draws in PLAY of the number of columns the copy rule
+ *     banned that the static vector had not.
+ *   Off (no guard attached) is the code path without this section: every id of every entry point is what it was, bit for bit, and
+ *     the captured per-token chain has the nodes it had.  Attaching or detaching invalidates that chain's captured graphs: the next
+ *     begin captures the chain with or without the scan.
+ *   Refusals (CMP_ERR_INVALID before any device work, the reason in cmp_last_error): M or N out of range; a dataset without a
+ *     layout; a velocity range outside [0, 65536) or overlapping the note ranges (cmp_novelty's checks); a dataset on another device
+ *     than the model's.  A refused call leaves the configuration and a decode in progress as they were. */
+typedef struct cmp_copy_guard_opts {
+    int32_t max_copy;          /* M */
+    int32_t transpose;         /* N: every k in [-N, N] counts */
+    int32_t velocity0;
+    int32_t velocity_n;        /* 0: no folding */
+} cmp_copy_guard_opts;
+/* Configures the batch-1 chain (batched = 0) or the batched chain (batched != 0); takes effect at that chain's next begin call (any of
+ * them) and stays until replaced.  ds null: off (opts is not read).  The caller keeps ds alive, with its piece starts unchanged,
+ * while it is attached and while a decode begun under it goes on. */
+int cmp_decode_copy_guard(cmp_model* m, int batched, cmp_dataset* ds, const cmp_copy_guard_opts* opts);
+/* Row `row` of the chain (batch-1: row 0) after its latest id; synchronises.  0 on a chain begun without a guard.  CMP_ERR_STATE
+ * before begin, CMP_ERR_INVALID for a bad row. */
+int cmp_decode_copy_guard_state(cmp_model* m, int batched, int row, int64_t* banned_columns);
+/* The scan alone (dev pointers; layout and opts on the host): ids_dev uint16 [n], n >= 1; start_bits_dev ceil(n / 32) words or null
+ * (one piece); hist_dev int32 [B][ld], row b holds lens_dev[b] ids (clamped to [0, ld]; its last M are the window; an id outside
+ * [0, 65535) equals nothing); 1 <= B <= 256, ld >= 1; static_words_dev ceil(V / 32) words shared by all rows, or null (none);
+ * words_out uint32 [B][ceil(V / 32)] = the static words OR the copy bans of the row (bits at or above V: the static vector's);
+ * count_out int64 [B] = the bits the copy rule set that the static words had not.  Every element of both outputs is written.  Reads
+ * ids_dev[0 .. n), the start bits of those positions, hist_dev[b][lens[b] - M .. lens[b]) of the rows with lens[b] >= M,
+ * lens_dev[0 .. B) and the static words, and nothing else. */
+int cmp_k_copy_bans(void* stream, const uint16_t* ids_dev, int64_t n, const uint32_t* start_bits_dev, const cmp_event_grammar* layout,
+                    const cmp_copy_guard_opts* opts, const int32_t* hist_dev, const int32_t* lens_dev, int B, int ld, int V,
+                    const uint32_t* static_words_dev, uint32_t* words_out, int64_t* count_out);
+
 /* ---- live kernel timing (bench.py roofline): HIP events around every launch of ONE kernel class on the
  * stream it is launched on.  cls: 0 gemm forward (A[M,K].B[K,N]), 1 gemm dgrad (B stored [N,K]), 2 gemm wgrad
  * (A stored [K,M]), 3 attention forward, 4 attention dQ, 5 attention dK/dV, 6 layernorm fwd, 7 adam.
