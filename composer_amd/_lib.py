@@ -53,6 +53,16 @@ class CopyGuardOpts(C.Structure):
     _fields_ = [("max_copy", C.c_int32), ("transpose", C.c_int32), ("velocity0", C.c_int32), ("velocity_n", C.c_int32)]
 
 
+class EvalClasses(C.Structure):
+    """cmp_eval_classes: the disjoint id ranges a validation pass sums by (Transformer.evaluate_dataset builds it)."""
+    _fields_ = [("n", C.c_int32), ("lo", C.c_int32 * 8), ("hi", C.c_int32 * 8)]
+
+
+class EvalTable(C.Structure):
+    """cmp_eval_table: per class (slot n: every other id) the float64 NLL sum, the rows counted and the rows ranked first."""
+    _fields_ = [("nll", C.c_double * 9), ("count", C.c_int64 * 9), ("correct", C.c_int64 * 9)]
+
+
 class GemmPlanInfo(C.Structure):
     """cmp_gemm_plan_info: the launcher's decision for one cmp_k_gemm argument list (host only; tests/test_gemm_plan_host.py)."""
     _fields_ = [(n, C.c_int32) for n in ("family", "a_km", "b_km", "swap", "kind", "lnm", "np", "diag", "grid_x", "grid_y", "grid_z", "block")] + \
@@ -125,6 +135,9 @@ SIGNATURES = {
     "cmp_decode_copy_guard": (_i, [_P, _i, _P, C.POINTER(CopyGuardOpts)]),
     "cmp_decode_copy_guard_state": (_i, [_P, _i, _i, C.POINTER(_i64)]),
     "cmp_k_copy_bans": (_i, [_P, _P, _i64, _P, C.POINTER(EventGrammar), C.POINTER(CopyGuardOpts), _P, _P, _i, _i, _i, _P, _P, _P]),
+    "cmp_eval_dataset": (_i, [_P, _P, _i64, _i64, _i, _i, C.POINTER(EvalClasses), C.POINTER(EvalTable)]),
+    "cmp_k_eval_rows_ws": (_i64, [_i]),
+    "cmp_k_eval_rows": (_i, [_P, _P, _i, _P, _i, _i, C.POINTER(EvalClasses), _P, _P]),
     "cmp_present_get": (_i, [_P, _i, _i, _i, _P]),
     "cmp_forward_generation": (_i, [_P, C.POINTER(_i64)]),
     "cmp_present_get_at": (_i, [_P, _i, _i, _i, _i64, _P]),
@@ -200,7 +213,8 @@ _ADDED_LATER = {"cmp_gemm_ln_scale_next", "cmp_attn_bwd_ln_next", "cmp_k_layerno
                 "cmp_decode_grammar", "cmp_decode_grammar_state", "cmp_k_sample_banned", "cmp_score", "cmp_k_score_rows", "cmp_gemm_plan",
                 "cmp_attn_plan", "cmp_attn_caps", "cmp_decode_budget", "cmp_decode_budget_state", "cmp_dataset_create", "cmp_dataset_destroy",
                 "cmp_k_batch_rows", "cmp_dataset_batch", "cmp_train_step_dataset", "cmp_dataset_set_pieces", "cmp_novelty", "cmp_k_novelty",
-                "cmp_decode_copy_guard", "cmp_decode_copy_guard_state", "cmp_k_copy_bans"}
+                "cmp_decode_copy_guard", "cmp_decode_copy_guard_state", "cmp_k_copy_bans", "cmp_eval_dataset",
+                "cmp_k_eval_rows_ws", "cmp_k_eval_rows"}
 
 _lib = None
 

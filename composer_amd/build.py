@@ -22,7 +22,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libcomposer_hip.so")
 ROOT = os.path.dirname(HERE)
 SOURCES = ["elementwise.hip", "gemm.hip", "attention.hip", "model.hip", "decode.hip", "decode_batch.hip", "score.hip", "batch.hip",
-           "novelty.hip", "copyguard.hip"]
+           "novelty.hip", "copyguard.hip", "evalpass.hip"]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wno-unused-value", "-Wno-inline-asm", "-I" + os.path.join(ROOT, "include")]
 # per-source additions.  attention.hip: without SLP vectorisation -- hipcc packs neighbouring f32 multiplies / adds of the softmax

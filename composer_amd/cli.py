@@ -11,6 +11,7 @@ file; `--decode-mode` selects the literal loop of cli.py:663-676 or a real KV ca
 per-event likelihood of MIDI / `.data` files under a restored model; `generate --keep-best` ranks the samples by it.  `novelty` (not in
 the reference either) finds the longest verbatim match of every event of such files in a dataset split; `generate --novelty-against`
 prints it for the samples."""
+import collections
 import datetime
 import json
 import logging
@@ -28,7 +29,7 @@ from . import config as cfgmod
 from . import dataset as ds
 from . import tfrecord
 from .augment import check_augment_options
-from .transformer import ModelSaveFrequencyMode, Transformer, check_train_options
+from .transformer import ModelSaveFrequencyMode, Transformer, check_eval_options, check_train_options
 
 
 @unique
@@ -158,6 +159,58 @@ def augment_options_from(config, augment_transpose=None, augment_stretch=None, r
                             pick(random_crop, 'random_crop', False))
 
 
+def _eval_options(eval_freq=0, eval_max_windows=None, early_stop_patience=0, keep_best=False, source='transformer.train'):
+    try:
+        return check_eval_options(eval_freq, eval_max_windows, early_stop_patience, keep_best)
+    except (ValueError, TypeError) as e:
+        raise click.UsageError('{}: {}'.format(source, e))
+
+
+def eval_options_from(config, eval_freq=None, eval_split=None, eval_max_windows=None, early_stop_patience=None, keep_best_checkpoint=None):
+    """(eval_freq, eval_split, eval_max_windows, early_stop_patience, keep_best): the optional keys of `transformer.train` (absent in
+    the reference's files: off, split 'test'), overridden by the flags that were given; a bad value is a click.UsageError."""
+    t = config.transformer.train
+    pick = lambda flag, key, default: t.get(key, default) if flag is None else flag
+    freq, windows, patience, keep = _eval_options(pick(eval_freq, 'eval_freq', 0), pick(eval_max_windows, 'eval_max_windows', None),
+                                                  pick(early_stop_patience, 'early_stop_patience', 0),
+                                                  pick(keep_best_checkpoint, 'keep_best_checkpoint', False))
+    split = str(pick(eval_split, 'eval_split', 'test'))
+    if not split or '/' in split or split in ('.', '..'):
+        raise click.UsageError('transformer.train: eval_split \'{}\' must name a folder of the dataset path'.format(split))
+    return freq, split, windows, patience, keep
+
+
+def get_eval_stream(dataset_path, config, split='test', max_files=None):
+    """The id stream of a held-out split of a directory dataset (uint16, files in sorted order), read against the config's settings
+    like the train split.  No device use; what cannot be validated on is a click.UsageError."""
+    p = Path(dataset_path)
+    if not p.is_dir():
+        raise click.UsageError('--eval-freq needs a directory dataset with a \'{}\' folder: \'{}\' holds pre-cut batches (or does not '
+                               'exist)'.format(split, dataset_path))
+    files = ds.get_processed_files(p / split) if (p / split).is_dir() else []
+    if not files:
+        raise click.UsageError('--eval-split {}: \'{}\' is missing or holds no .data file'.format(split, p / split))
+    if max_files is not None:
+        files = files[:max_files]
+    d = config.dataset
+    try:
+        ids = ds.read_id_stream(files, expect_settings=(d.time_step_increment, d.max_time_steps, d.velocity_bins))
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    need = config.transformer.model.window_size + 1
+    if len(ids) < need:
+        raise click.UsageError('--eval-split {}: \'{}\' holds {} events, one window needs window_size + 1 = {}'.format(
+            split, p / split, len(ids), need))
+    return ids
+
+
+def event_class_ranges(config):
+    """{class name: range of ids} of the config's vocabulary, in id order: the classes of `score --by-event-type`."""
+    d = config.dataset
+    rg = ds.event_ranges(ds.event_value_ranges(d.time_step_increment, d.max_time_steps, d.velocity_bins))
+    return collections.OrderedDict((EVENT_TYPE_NAMES[t], r) for t, r in rg.items())
+
+
 def get_device_dataset(dataset_path, config, augment, max_files=None, rank=0, world_size=1, seed=0):
     """The train split of a directory dataset as a DeviceDataset: the files and their order are get_dataset's, the batches are built
     on the device (augment = (transpose, stretch, random_crop))."""
@@ -264,9 +317,22 @@ def summary(model_type, config_filepath):
 @click.option('--random-crop/--no-random-crop', default=None,
               help='Cut training rows at random offsets of the id stream instead of a fixed grid of windows. Overrides '
                    'transformer.train.random_crop.')
+@click.option('--eval-freq', default=None, type=int, metavar='N',
+              help='Validate on the held-out split every N optimiser steps, on the device: val_loss, val_accuracy and val_nll/<class> '
+                   'are logged (0 off). Overrides transformer.train.eval_freq.')
+@click.option('--eval-split', default=None, metavar='NAME',
+              help='The folder of DATASET-PATH to validate on. Defaults to test. Overrides transformer.train.eval_split.')
+@click.option('--eval-max-windows', default=None, type=int, metavar='N',
+              help='Validate on the first N windows of the split only. Overrides transformer.train.eval_max_windows.')
+@click.option('--early-stop-patience', default=None, type=int, metavar='P',
+              help='Stop after P validation passes in a row without a lower val_loss (0 off). Overrides '
+                   'transformer.train.early_stop_patience.')
+@click.option('--keep-best-checkpoint/--no-keep-best-checkpoint', default=None,
+              help='Keep the state with the lowest val_loss so far in <logdir>/best/. Overrides transformer.train.keep_best_checkpoint.')
 def train(model_type, dataset_path, logdir, restoredir, config_filepath, epochs, use_generator, max_files,
           save_frequency_mode, save_frequency, max_checkpoints, show_progress_bar, max_steps, checkpoint_format,
-          clip_norm, accumulate_steps, warmup_steps, augment_transpose, augment_stretch, random_crop):
+          clip_norm, accumulate_steps, warmup_steps, augment_transpose, augment_stretch, random_crop,
+          eval_freq, eval_split, eval_max_windows, early_stop_patience, keep_best_checkpoint):
     """Trains the specified model (cli.py:516-589)."""
     _require_transformer(model_type)
     for flag, value in (('--clip-norm', clip_norm), ('--accumulate-steps', accumulate_steps), ('--warmup-steps', warmup_steps)):
@@ -275,6 +341,10 @@ def train(model_type, dataset_path, logdir, restoredir, config_filepath, epochs,
     for flag, value in (('--augment-transpose', augment_transpose), ('--augment-stretch', augment_stretch)):
         if value is not None:
             _augment_options(**{flag[2:].replace('-', '_'): value}, source=flag)
+    for flag, value in (('--eval-freq', eval_freq), ('--eval-max-windows', eval_max_windows),
+                        ('--early-stop-patience', early_stop_patience)):
+        if value is not None:                                    # (a flag alone: the pairing rule waits for the config's keys)
+            _eval_options(**{'eval_freq': 1, flag[2:].replace('-', '_'): value}, source=flag)
     rank = int(os.environ.get('RANK', '0'))
     if restoredir is not None:
         config = get_config_from_restoredir(restoredir)
@@ -302,9 +372,16 @@ def train(model_type, dataset_path, logdir, restoredir, config_filepath, epochs,
     if any(augment) and not Path(dataset_path).is_dir():         # refused before any device use
         raise click.UsageError('--augment-transpose / --augment-stretch / --random-crop need a directory dataset: \'{}\' holds '
                                'pre-cut batches (or does not exist)'.format(dataset_path))
+    eval_freq, eval_split, eval_max_windows, early_stop_patience, keep_best = eval_options_from(
+        config, eval_freq, eval_split, eval_max_windows, early_stop_patience, keep_best_checkpoint)
+    eval_ids = get_eval_stream(dataset_path, config, eval_split, max_files) if eval_freq else None     # refused before any device use
     model, _ = create_model(model_type, config)
     rank, world = _init_distributed(model)
     _, seed = _runtime(config)
+    eval_dataset, eval_ranges = None, None
+    if eval_ids is not None:                                     # the whole split on every rank, in file order: one grid, one verdict
+        eval_dataset = ds.DeviceDataset(eval_ids, config.transformer.train.batch_size, config.transformer.model.window_size, shuffle=False)
+        eval_ranges = event_class_ranges(config)
     if any(augment):
         dataset = get_device_dataset(dataset_path, config, augment, max_files=max_files, rank=rank, world_size=world, seed=seed)
     else:                                                        # everything off: the host-cut windows, exactly as before
@@ -314,7 +391,9 @@ def train(model_type, dataset_path, logdir, restoredir, config_filepath, epochs,
                 learning_rate=config.transformer.train.learning_rate, save_frequency_mode=save_frequency_mode,
                 save_frequency=save_frequency, max_checkpoints=max_checkpoints,
                 show_progress_bar=show_progress_bar and rank == 0, max_steps=max_steps, checkpoint_format=checkpoint_format,
-                clip_norm=clip_norm, accumulate_steps=accumulate_steps, warmup_steps=warmup_steps)
+                clip_norm=clip_norm, accumulate_steps=accumulate_steps, warmup_steps=warmup_steps,
+                eval_dataset=eval_dataset, eval_freq=eval_freq, eval_max_windows=eval_max_windows,
+                early_stop_patience=early_stop_patience, keep_best=keep_best, eval_event_ranges=eval_ranges)
     if rank == 0 and model_logdir is not None:
         click.echo(str(model_logdir))
 
@@ -343,9 +422,30 @@ def export_dataset(model_type, preprocessed_path, output_path, config_filepath, 
 @click.argument('restoredir')
 @click.option('--use-generator/--no-use-generator', default=False)
 @click.option('--max-files', default=None, type=int)
-def evaluate(model_type, dataset_path, restoredir, use_generator, max_files):
+@click.option('--by-event-type', is_flag=True, default=False,
+              help='Evaluate ALL windows of the test split in one pass on the device and print the count, mean NLL and accuracy of every '
+                   'event class.')
+@click.option('--json', 'json_out', default=None, help='With --by-event-type: write the figures to this JSON file.')
+def evaluate(model_type, dataset_path, restoredir, use_generator, max_files, by_event_type, json_out):
     """Evaluate the specified model (cli.py:591-615)."""
     config = get_config_from_restoredir(restoredir)
+    if json_out is not None and not by_event_type:
+        raise click.UsageError('--json needs --by-event-type.')
+    if by_event_type:
+        _require_transformer(model_type)
+        ids = get_eval_stream(dataset_path, config, 'test', max_files)      # refused before any device use
+        model, _ = create_model(model_type, config)
+        model.load_from_checkpoint(restoredir)
+        report = model.evaluate_dataset(ids, event_ranges=event_class_ranges(config))
+        click.echo('loss {:.6f} accuracy {:.6f}'.format(report.loss, report.accuracy))
+        click.echo('events {} nll {:.9g} bits {:.9g} perplexity {:.9g} top1 {:.9g}'.format(
+            report.events, report.loss, report.bits_per_event, report.perplexity, report.accuracy))
+        for name, (count, nll, _) in report.by_event_type.items():
+            click.echo('  {}: count {} nll {:.9g}'.format(name, count, nll))
+        if json_out is not None:
+            with open(json_out, 'w') as fh:
+                json.dump(report.to_dict(), fh)
+        return
     model, _ = create_model(model_type, config)
     model.load_from_checkpoint(restoredir)
     model.compile(config.transformer.train.learning_rate)

@@ -238,6 +238,7 @@ struct cmp_model {
     DecGrammarCfg gram[2];             // event grammar of the batch-1 chain [0] and of the batched chain [1] (cmp_decode_grammar)
     DecBudgetCfg budget[2];            // time budget and polyphony cap of the two chains, likewise (cmp_decode_budget)
     DecGuardCfg guard[2];              // copy guard of the two chains, likewise (cmp_decode_copy_guard)
+    void* eval_buf = nullptr;          // evalpass.hip (cmp_eval_dataset): the pass's table, then its partial tables
     int gemm_role = -1;                // profiler class of the GEMMs being enqueued (0 while the forward pass is)
 
     // dropout seed of this replica: the model seed with the data-parallel rank folded in (rank 0: the seed itself)

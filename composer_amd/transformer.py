@@ -11,6 +11,7 @@ import enum
 import logging
 import math
 import os
+import shutil
 import time
 from pathlib import Path
 
@@ -154,6 +155,131 @@ def score_sequences(score_call, sequences, window, keep, max_tokens):
                 dst[start + first:start + length] = src[b, first:length]
         i += B
     return [SequenceScore(s[1:], *r) for s, r in zip(seqs, res)]
+
+
+class EvalReport:
+    """What `Transformer.evaluate_dataset` returns: the table of one validation pass (cmp_eval_dataset) and the figures derived from it.
+    `names`: the event classes in `event_ranges` order; the table's slot len(names) holds every id outside them.  `nll` are float64
+    sums in nats, `count` / `correct` integers, one per slot.  An empty total has NaN figures."""
+
+    def __init__(self, names, nll, count, correct, windows=0):
+        self.names = list(names)
+        k = len(self.names) + 1
+        self.nll = [float(v) for v in list(nll)[:k]]
+        self.count = [int(v) for v in list(count)[:k]]
+        self.correct = [int(v) for v in list(correct)[:k]]
+        if not len(self.nll) == len(self.count) == len(self.correct) == k:
+            raise ValueError('EvalReport: the table needs %d slots (the classes and one for every other id)' % k)
+        self.windows = int(windows)
+
+    @property
+    def events(self):
+        return sum(self.count)
+
+    @property
+    def loss(self):
+        """Mean NLL per event, nats: the slots' sums added in slot order, over the events."""
+        return math.fsum(self.nll) / self.events if self.events else float('nan')
+
+    @property
+    def accuracy(self):
+        return sum(self.correct) / self.events if self.events else float('nan')
+
+    @property
+    def bits_per_event(self):
+        return self.loss / math.log(2.0)
+
+    @property
+    def perplexity(self):
+        nll = self.loss
+        if nll != nll:
+            return float('nan')
+        return math.exp(nll) if nll < 709.0 else float('inf')
+
+    @property
+    def other(self):
+        """(count, mean NLL or NaN, accuracy or NaN) of the ids outside every class."""
+        return self._slot(len(self.names))
+
+    def _slot(self, i):
+        k = self.count[i]
+        return (k, self.nll[i] / k if k else float('nan'), self.correct[i] / k if k else float('nan'))
+
+    @property
+    def by_event_type(self):
+        """{event type: (count, mean NLL or NaN, accuracy or NaN)} in `event_ranges` order."""
+        return collections.OrderedDict((t, self._slot(i)) for i, t in enumerate(self.names))
+
+    def to_dict(self):
+        d = {'events': self.events, 'windows': self.windows, 'loss': self.loss, 'accuracy': self.accuracy,
+             'bits_per_event': self.bits_per_event, 'perplexity': self.perplexity,
+             'by_event_type': {str(t): {'count': c, 'nll_per_event': n, 'accuracy': a} for t, (c, n, a) in self.by_event_type.items()}}
+        if self.count[len(self.names)]:
+            d['other'] = dict(zip(('count', 'nll_per_event', 'accuracy'), self.other))
+        return d
+
+
+class ValidationTracker:
+    """The decision after every validation pass, no GPU: `update(step, loss) -> (is_best, stop)`.  A loss improves when
+    loss < best - min_delta (strictly; the first finite loss always does, a NaN never); `stop` turns true once `patience`
+    consecutive passes have not improved (patience 0: never).  `state()` / `from_state()` carry it through a checkpoint's meta."""
+
+    def __init__(self, patience=0, min_delta=0.0):
+        patience, min_delta = int(patience), float(min_delta)
+        if patience < 0 or not min_delta >= 0.0:
+            raise ValueError('early_stop_patience = %d and min_delta = %g must not be negative' % (patience, min_delta))
+        self.patience, self.min_delta = patience, min_delta
+        self.best, self.best_step, self.bad_passes = None, None, 0
+
+    def update(self, step, loss):
+        loss = float(loss)
+        is_best = loss == loss and (self.best is None or loss < self.best - self.min_delta)
+        if is_best:
+            self.best, self.best_step, self.bad_passes = loss, int(step), 0
+        else:
+            self.bad_passes += 1
+        return is_best, self.patience > 0 and self.bad_passes >= self.patience
+
+    def state(self):
+        return {'best': self.best, 'best_step': self.best_step, 'bad_passes': self.bad_passes}
+
+    def load_state(self, state):
+        """Takes over the counts of an earlier run (patience and min_delta stay this run's)."""
+        if state:
+            best = state.get('best')
+            self.best = None if best is None else float(best)
+            self.best_step = state.get('best_step')
+            self.bad_passes = int(state.get('bad_passes', 0))
+        return self
+
+    @classmethod
+    def from_state(cls, state, patience=0, min_delta=0.0):
+        return cls(patience, min_delta).load_state(state)
+
+
+def exchange_verdict(all_reduce_sum, rank, is_best, stop):
+    """Rank 0's verdict on every rank: a two-element vector through `all_reduce_sum`, to which rank 0 contributes (is_best, stop) and
+    every other rank zeros -- so no rank leaves the train loop alone while its peers wait in a gradient all-reduce.  Collective."""
+    mine = [float(bool(is_best)), float(bool(stop))] if rank == 0 else [0.0, 0.0]
+    got = all_reduce_sum(mine)
+    return bool(got[0] > 0.5), bool(got[1] > 0.5)
+
+
+def check_eval_options(eval_freq=0, eval_max_windows=None, early_stop_patience=0, keep_best=False):
+    """The argument rule of validation during training: eval_freq >= 0 optimiser steps (0 off), eval_max_windows None or >= 1,
+    early_stop_patience >= 0 passes (0 off); patience and keep_best need eval_freq > 0.  Returns them as (int, int | None, int, bool)."""
+    eval_freq, early_stop_patience, keep_best = int(eval_freq), int(early_stop_patience), bool(keep_best)
+    if eval_freq < 0:
+        raise ValueError('eval_freq = %d must not be negative (0: off)' % eval_freq)
+    if eval_max_windows is not None:
+        eval_max_windows = int(eval_max_windows)
+        if eval_max_windows < 1:
+            raise ValueError('eval_max_windows = %d must be at least 1' % eval_max_windows)
+    if early_stop_patience < 0:
+        raise ValueError('early_stop_patience = %d must not be negative (0: off)' % early_stop_patience)
+    if (early_stop_patience or keep_best) and not eval_freq:
+        raise ValueError('early_stop_patience / keep_best need eval_freq > 0: there is no validation pass to act on')
+    return eval_freq, eval_max_windows, early_stop_patience, keep_best
 
 
 def check_sampling(top_k, top_p):
@@ -316,6 +442,7 @@ class Transformer:
         # sized it bigger, which only means smaller calls than possible; with max_seq < window_size a full window exceeds this figure,
         # is sent alone, and the library refuses it by name if its workspace is already sized smaller)
         self._max_tokens = max(1, int(max_batch)) * max(1, min(int(max_seq or window_size), int(window_size)))
+        self._max_batch = max(1, int(max_batch))
         self._specs = self._param_specs()
         self._learning_rate = 1e-3
         self._dp = None          # (rank, nranks) once init_data_parallel() ran
@@ -724,6 +851,47 @@ class Transformer:
             return float('nan'), float('nan')
         return tot / cnt, cor / cnt
 
+    def evaluate_dataset(self, dataset, max_windows=None, batch=None, event_ranges=None):
+        """One validation pass on the device (cmp_eval_dataset): mean NLL and accuracy over the windows of the fixed grid
+        ids[i (W + 1) : (i + 1)(W + 1)], summed per event class.  `dataset`: a DeviceDataset (its stream is uploaded once, through
+        _dataset_handle, with its own window size W) or a plain array of uint16 ids (W = window_size; uploaded for this call).
+        `max_windows`: the first N windows of the grid only, a deterministic subset, so successive passes are comparable.  `batch`:
+        windows per forward pass (default max_batch); the last batch is ragged, no window is dropped.  `event_ranges`: {event type:
+        range of ids} (composer_amd.dataset.event_ranges), at most 8 disjoint classes.  Returns an EvalReport.  Read-only for
+        everything that lasts; two calls on the same inputs return the same bits."""
+        own = None
+        if hasattr(dataset, 'ids') and hasattr(dataset, 'W'):
+            handle, n, W = self._dataset_handle(dataset), len(dataset.ids), int(dataset.W)
+        else:
+            ids = np.asarray(dataset)
+            if ids.ndim != 1 or (ids.size and (ids.min() < 0 or ids.max() > 65535)):
+                raise ValueError('evaluate_dataset: a DeviceDataset or a 1-D array of event ids that fit uint16 is expected')
+            ids = np.ascontiguousarray(ids, dtype=np.uint16)
+            n, W = len(ids), int(self.window_size)
+            own = C.c_void_p()
+            _lib.check(self._lib.cmp_dataset_create(self._ctx, ids.ctypes.data_as(C.c_void_p), n, None, C.byref(own)), 'cmp_dataset_create')
+            handle = own
+        try:
+            windows = n // (W + 1)
+            if max_windows is not None:
+                if int(max_windows) < 1:
+                    raise ValueError('evaluate_dataset: max_windows = %d must be at least 1' % int(max_windows))
+                windows = min(windows, int(max_windows))
+            names, classes = [], _lib.EvalClasses()
+            for t, interval in (event_ranges or {}).items():
+                if len(names) >= 8:
+                    raise ValueError('evaluate_dataset: at most 8 event classes')
+                classes.lo[len(names)], classes.hi[len(names)] = int(interval.start), int(interval.stop)
+                names.append(t)
+            classes.n = len(names)
+            table = _lib.EvalTable()
+            _lib.check(self._lib.cmp_eval_dataset(self._h, handle, 0, windows, W, int(batch or self._max_batch), C.byref(classes),
+                                                  C.byref(table)), 'cmp_eval_dataset')
+        finally:
+            if own is not None:
+                self._lib.cmp_dataset_destroy(own)
+        return EvalReport(names, list(table.nll), list(table.count), list(table.correct), windows=windows)
+
     # ------------------------------------------------------------------ scoring
     def _score_call(self, x, y):
         """cmp_score on one padded batch: (logp, rank, entropy), each [B, T]."""
@@ -1089,12 +1257,28 @@ class Transformer:
     # ------------------------------------------------------------------ train loop (transformer.py:846-960)
     def train(self, dataset, input_shape, logdir, restoredir=None, epochs=None, learning_rate=1e-3,
               save_frequency_mode=ModelSaveFrequencyMode.EPOCH, save_frequency=1, max_checkpoints=1,
-              show_progress_bar=True, max_steps=None, checkpoint_format='npz', clip_norm=0.0, accumulate_steps=1, warmup_steps=0):
+              show_progress_bar=True, max_steps=None, checkpoint_format='npz', clip_norm=0.0, accumulate_steps=1, warmup_steps=0,
+              eval_dataset=None, eval_freq=0, eval_max_windows=None, early_stop_patience=0, keep_best=False, eval_event_ranges=None):
         """clip_norm / accumulate_steps: set_train_options; warmup_steps: warmup_lr.  With accumulate_steps = k > 1 every dataset batch is
         a micro-batch: `step`, max_steps and save_frequency count OPTIMISER steps, the logged loss / accuracy of a step are the means
         over its k micro-batches, a group may span an epoch boundary, checkpoints are written at group boundaries only and a partial
-        group left at the end is discarded."""
+        group left at the end is discarded.
+
+        Validation (eval_dataset with eval_freq > 0; off by default, and then nothing here differs): every eval_freq optimiser steps,
+        where a checkpoint save would drain the pipeline, and once more at the end of the run if its last step was not evaluated,
+        evaluate_dataset runs over eval_dataset (the first eval_max_windows windows) and `val_loss`, `val_accuracy` and one
+        `val_nll/<class>` per event class with events (eval_event_ranges: {class name: range of ids}) are logged at the step.  keep_best:
+        the state with the lowest val_loss so far is kept in <logdir>/best/ (one checkpoint, meta {'step', 'epoch', 'val_loss'}); the
+        rolling checkpoints are untouched.  early_stop_patience = P > 0: after P passes in a row without a lower val_loss the loop
+        ends as max_steps ends it.  The ValidationTracker's state travels in every npz checkpoint's meta ('validation'), so a restored
+        run continues the count.  Data-parallel: every rank runs the pass, rank 0 logs, saves and decides (exchange_verdict)."""
         clip_norm, k, warmup_steps = check_train_options(clip_norm, accumulate_steps, warmup_steps)
+        eval_freq, eval_max_windows, early_stop_patience, keep_best = check_eval_options(eval_freq, eval_max_windows, early_stop_patience,
+                                                                                       keep_best)
+        validate = eval_dataset is not None and eval_freq > 0
+        if (early_stop_patience or keep_best) and not validate:
+            raise ValueError('early_stop_patience / keep_best need an eval_dataset')
+        tracker = ValidationTracker(early_stop_patience) if validate else None
         if clip_norm != 0.0 or k != 1 or hasattr(self._lib, 'cmp_train_options'):   # (an older library as the other arm of an A/B lacks it)
             self.set_train_options(clip_norm, k)
         clip_on = clip_norm > 0.0
@@ -1109,6 +1293,8 @@ class Transformer:
                 sd, meta = ckpt.load(manager.latest_checkpoint)
                 self.load_state_dict(sd)
                 step, epoch = int(meta['step']), int(meta['epoch'])
+                if tracker is not None:
+                    tracker.load_state(meta.get('validation'))
                 logging.info('Model restored from \'{}\'.'.format(manager.latest_checkpoint))
             except Exception:
                 logging.error('Failed to restore model from \'{}\'.'.format(restoredir))
@@ -1121,7 +1307,40 @@ class Transformer:
         def save():
             if rank != 0:
                 return None
-            return manager.save(self.state_dict(), {'step': step, 'epoch': epoch})
+            meta = {'step': step, 'epoch': epoch}
+            if tracker is not None:
+                meta['validation'] = tracker.state()
+            return manager.save(self.state_dict(), meta)
+
+        best_manager = ckpt.CheckpointManager(logdir / 'best', max_to_keep=1, format=checkpoint_format) if keep_best and rank == 0 else None
+        last_eval = None                                                         # the step number of the latest validation pass
+
+        def validation_pass(st):
+            """The pass after optimiser step `st` (the pipeline is drained); True when the run should stop."""
+            nonlocal last_eval
+            last_eval = st
+            report = self.evaluate_dataset(eval_dataset, max_windows=eval_max_windows, event_ranges=eval_event_ranges)
+            is_best, stop = tracker.update(st, report.loss) if rank == 0 else (False, False)
+            if self._dp and self._dp[1] > 1:
+                is_best, stop = exchange_verdict(self.all_reduce_sum, rank, is_best, stop)
+            if rank == 0:
+                summary.scalar('val_loss', report.loss, st)
+                summary.scalar('val_accuracy', report.accuracy, st)
+                for t, (count, nll, _) in report.by_event_type.items():
+                    if count:
+                        summary.scalar('val_nll/{}'.format(t), nll, st)
+                summary.flush()
+                if show_progress_bar:
+                    print('\n- step {}: val_loss {:.4f} - val_accuracy {:.4f}{}'.format(st, report.loss, report.accuracy,
+                                                                                      ' (best)' if is_best else ''))
+                if is_best and best_manager is not None:
+                    best_manager.save(self.state_dict(), {'step': st, 'epoch': epoch, 'val_loss': report.loss})
+                    if (logdir / 'config.yml').exists():                         # a model directory of its own: generate / score / evaluate
+                        shutil.copyfile(logdir / 'config.yml', logdir / 'best' / 'config.yml')
+                if stop:
+                    logging.info('Early stop at step {}: val_loss {:.6f} has not improved on the best {:.6f} at step {} for {} passes.'.format(
+                        st, report.loss, tracker.best if tracker.best is not None else float('nan'), tracker.best_step, tracker.bad_passes))
+            return stop
 
         done = False
         group = []                                                               # (loss, accuracy) of the retired micro-steps of the open group
@@ -1174,19 +1393,25 @@ class Transformer:
                     continue
                 micro = 0
                 ep_n += 1
+                if validate and step % eval_freq == 0:
+                    retire(0)
+                    done = validation_pass(step)
                 if save_frequency_mode == ModelSaveFrequencyMode.GLOBAL_STEP and step % save_frequency == 0:
                     retire(0)
                     path = save()                                                # :941-943
                     if path and show_progress_bar:
                         print('\nSaved checkpoint for step {} at {}.'.format(step, path))
                 step += 1                                                        # :945
-                if max_steps is not None and step - first_step >= max_steps:
+                if done or (max_steps is not None and step - first_step >= max_steps):
                     done = True
                     break
             retire(0)
             if ep_batches == 0:
                 logging.error('The dataset yielded no batches.')
                 break
+            last_epoch = done or (epochs is not None and epoch + 1 >= epochs)
+            if validate and last_epoch and step > first_step and last_eval != step - 1:
+                validation_pass(step - 1)                                        # the end of the run: its last step, if not evaluated yet
             if summary and ep_n:
                 summary.scalar('epoch_loss', ep_loss / ep_n, epoch)              # :949-951
                 summary.scalar('epoch_accuracy', ep_correct / ep_n, epoch)

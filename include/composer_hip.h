@@ -602,6 +602,40 @@ int cmp_k_copy_bans(void* stream, const uint16_t* ids_dev, int64_t n, const uint
                     const cmp_copy_guard_opts* opts, const int32_t* hist_dev, const int32_t* lens_dev, int B, int ld, int V,
                     const uint32_t* static_words_dev, uint32_t* words_out, int64_t* count_out);
 
+/* ---- validation pass: held-out loss of a split in HBM, summed per event class on the device ---------------------------------
+ * When does the model start memorising?  One call evaluates a whole held-out split that a cmp_dataset keeps in HBM and returns one
+ * small table; Transformer.train runs it every eval_freq optimiser steps (Transformer.evaluate_dataset restates the arithmetic).
+ *   Windows: window i of the stream ids[0..n) is ids[i (T + 1) .. (i + 1)(T + 1)), x its first T ids and y its last T -- the fixed
+ *   grid of WindowDataset / DeviceDataset.  The windows first_window .. first_window + n_windows - 1 are evaluated, ALL of them, in
+ *   batches of `batch` rows; the last batch holds the n_windows % batch windows that remain (ragged, not dropped).
+ *   Per row with y inside [0, V), from the fp32 logits row z of the inference forward pass (training = false, the model's dtype):
+ *     nll     = -(z[y] - logsumexp(z)): the fp32 value cmp_k_score_rows yields as -logp (one device function computes both);
+ *     correct = (rank == 0): the greedy argmax, lowest index on ties -- cmp_k_softmax_xent's row_correct.
+ *   A row whose target lies outside [0, V) is counted nowhere.
+ *   Classes: n <= 8 disjoint, non-empty half-open id ranges [lo[c], hi[c]) inside [0, V).  A row belongs to the class whose range
+ *   holds y; slot n collects every other id; slots above n are zero.  The grand total is the sum over the slots.  Null: n = 0.
+ *   Sums: nll in float64, count and correct in int64, in a fixed order -- a wave adds its rows in ascending order, a workgroup its
+ *   four waves in order, one workgroup the per-workgroup partial tables by index (cmp_k_grad_clip's scheme), batches ascending.  No
+ *   float atomics, nothing depends on arrival order: two calls on the same inputs return the same bits.
+ * cmp_eval_dataset: waits for the compute stream's earlier work (a train step may be in flight), enqueues every batch -- the window
+ * cut, the forward pass, the row reduction -- with the table kept on the device, synchronises once and copies back only
+ * sizeof(cmp_eval_table); nothing goes up.  The stream is idle when it returns.  1 <= batch <= max_batch, 1 <= T <= min(window_size,
+ * max_seq), (first_window + n_windows)(T + 1) <= n, n_windows >= 1.  CMP_ERR_INVALID before any device work (reason in
+ * cmp_last_error): ds and m in different contexts, a dataset whose largest id is >= V, windows outside the stream, batch or T out of
+ * range, a class range outside [0, V), empty, or overlapping another, n > 8.
+ * Read-only for everything that lasts: parameters, gradients, Adam state and iterations, a pending accumulation group, the dropout
+ * counters, the metrics and stage slots of train steps in flight or just retired and both decode chains are what they were. */
+typedef struct cmp_eval_classes { int32_t n; int32_t lo[8]; int32_t hi[8]; } cmp_eval_classes;
+typedef struct cmp_eval_table { double nll[9]; int64_t count[9]; int64_t correct[9]; } cmp_eval_table;
+int cmp_eval_dataset(cmp_model* m, cmp_dataset* ds, int64_t first_window, int64_t n_windows, int T, int batch,
+                     const cmp_eval_classes* classes, cmp_eval_table* out);
+/* The kernels alone (dev pointers; classes on the host): logits fp32 [rows, ldz], columns [V, ldz) are padding of any content; y
+ * int32 [rows]; table_dev a cmp_eval_table the sums of these rows are ADDED INTO (all nine slots of the three arrays are rewritten);
+ * ws_dev cmp_k_eval_rows_ws(rows) bytes of workspace; both 8-byte aligned.  One pass over the logits, two launches. */
+int64_t cmp_k_eval_rows_ws(int rows);
+int cmp_k_eval_rows(void* stream, const float* logits, int ldz, const int32_t* y, int rows, int V, const cmp_eval_classes* classes,
+                    void* table_dev, void* ws_dev);
+
 /* ---- live kernel timing (bench.py roofline): HIP events around every launch of ONE kernel class on the
  * stream it is launched on.  cls: 0 gemm forward (A[M,K].B[K,N]), 1 gemm dgrad (B stored [N,K]), 2 gemm wgrad
  * (A stored [K,M]), 3 attention forward, 4 attention dQ, 5 attention dK/dV, 6 layernorm fwd, 7 adam.
