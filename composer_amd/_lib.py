@@ -186,7 +186,6 @@ SIGNATURES = {
     "cmp_k_ln_stats_merge": (_i, [_P, _P, _i, _f, _P, _P, _i]),
     "cmp_k_layernorm_bwd_prescaled": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P, _f, _u64, _u32]),
     "cmp_k_wgrad_ln_fix": (_i, [_P, _P, _i, _i, _P, _P, _P]),
-    "cmp_k_layernorm_bwd_parts": (_i, [_P, _P, _P, _P, _P, _P, _f, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P, _f, _u64, _u32]),
     "cmp_model_path_info": (_i, [_P, C.POINTER(_i), C.POINTER(_i64)]),
     "cmp_k_wgrad_group": (_i, [_P, _i, _P, _P, _P, _P, _P, _P, _P, _P, _i]),
     "cmp_gemm_set_workspace": (_i, [_P, _i64]),
@@ -208,7 +207,7 @@ SIGNATURES = {
 
 # entry points added after round 3: an OLDER build of the library loaded through COMPOSER_HIP_LIB as the other arm of an A/B
 # timing (tools/ab_step.py) may lack them; the package's own library must export every symbol
-_ADDED_LATER = {"cmp_gemm_ln_scale_next", "cmp_attn_bwd_ln_next", "cmp_k_layernorm_bwd_prescaled", "cmp_k_wgrad_ln_fix", "cmp_k_ln_stats_merge", "cmp_dp_rccl_version", "cmp_dp_allreduce_pattern", "cmp_dp_init_exchange", "cmp_train_step_graph_probe", "cmp_train_step_launches", "cmp_k_embed_fwd_stats", "cmp_k_ln_fold_prep", "cmp_gemm_ln_next", "cmp_k_layernorm_bwd_parts", "cmp_model_path_info", "cmp_forward_ex", "cmp_hidden_get_at", "cmp_dp_stats", "cmp_prof_end2", "cmp_prof_pause", "cmp_prof_resume", "cmp_k_wgrad_group", "cmp_k_embed_bwd_v", "cmp_decode_batch_begin", "cmp_decode_batch_steps", "cmp_k_sample_rows", "cmp_decode_logits_get", "cmp_decode_batch_logits_get", "cmp_k_sample_ex", "cmp_k_sample_rows_ex", "cmp_decode_begin_ex", "cmp_decode_batch_begin_ex", "cmp_train_options",
+_ADDED_LATER = {"cmp_gemm_ln_scale_next", "cmp_attn_bwd_ln_next", "cmp_k_layernorm_bwd_prescaled", "cmp_k_wgrad_ln_fix", "cmp_k_ln_stats_merge", "cmp_dp_rccl_version", "cmp_dp_allreduce_pattern", "cmp_dp_init_exchange", "cmp_train_step_graph_probe", "cmp_train_step_launches", "cmp_k_embed_fwd_stats", "cmp_k_ln_fold_prep", "cmp_gemm_ln_next", "cmp_model_path_info", "cmp_forward_ex", "cmp_hidden_get_at", "cmp_dp_stats", "cmp_prof_end2", "cmp_prof_pause", "cmp_prof_resume", "cmp_k_wgrad_group", "cmp_k_embed_bwd_v", "cmp_decode_batch_begin", "cmp_decode_batch_steps", "cmp_k_sample_rows", "cmp_decode_logits_get", "cmp_decode_batch_logits_get", "cmp_k_sample_ex", "cmp_k_sample_rows_ex", "cmp_decode_begin_ex", "cmp_decode_batch_begin_ex", "cmp_train_options",
                 "cmp_train_options_get", "cmp_train_grad_stats", "cmp_train_metrics_wait_ex", "cmp_k_adam_dev", "cmp_k_grad_clip_ws", "cmp_k_grad_clip",
                 "cmp_decode_grammar", "cmp_decode_grammar_state", "cmp_k_sample_banned", "cmp_score", "cmp_k_score_rows", "cmp_gemm_plan",
                 "cmp_attn_plan", "cmp_attn_caps", "cmp_decode_budget", "cmp_decode_budget_state", "cmp_dataset_create", "cmp_dataset_destroy",

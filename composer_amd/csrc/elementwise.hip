@@ -425,18 +425,14 @@ __global__ void layernorm_fwd_kernel(const T* __restrict__ x, const float* __res
 
 // dx = resid + rstd*(g - mean(g) - xhat*mean(g*xhat)), g = dy*gamma;  partial dgamma/dbeta per workgroup
 // into ws[wg][2][E]; ln_param_reduce_kernel folds them into dgamma/dbeta.
-// FUSED (the LayerNorm-fused block path, bf16): the forward pass never ran this LayerNorm as a kernel -- its statistics arrive as
-// the partials the producing GEMM epilogue left (`part`, np segments of 256 columns, merged here), and its OUTPUT, which only
-// the weight-gradient GEMM of the consuming Conv1D needs, is written here (`yout` = xhat * gamma + beta) beside dx.
-// PRE (with mean / rstd arrays, round 6): dy holds rstd o gradient, like LnBwdFused::prescaled of the FUSED form
-template <typename T, int MAXI, bool FUSED = false, bool PRE = false>
+// PRE (round 6, the backward pass of the LayerNorm-fused block path): dy holds rstd o gradient
+template <typename T, int MAXI, bool PRE = false>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                      const float* __restrict__ gamma, const float* __restrict__ mean,
                                      const float* __restrict__ rstd, const T* __restrict__ resid,
                                      T* __restrict__ dx, float* __restrict__ ws, int rows, int E,
                                      T* __restrict__ dmask, int want_colsum, DropCfg drop,
-                                     float* __restrict__ direct_g, float* __restrict__ direct_b, float* __restrict__ direct_cs,
-                                     LnBwdFused fz = LnBwdFused()) {
+                                     float* __restrict__ direct_g, float* __restrict__ direct_b, float* __restrict__ direct_cs) {
     // optional fused consumer prologue: the output dx is the gradient of a residual branch's dropout output
     // (x + dropout(proj(..))): dmask = dx * mask/(1-p) feeds that projection's wgrad/dgrad and its column sums are the
     // projection's bias gradient (third partial, ws[wg][2] -> cs)
@@ -445,7 +441,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wpb = blockDim.x >> 6;
     const int chunks = E / VN;
-    float dg[MAXI][VN], db[MAXI][VN], gm[MAXI][VN], cs[MAXI][VN], be[FUSED ? MAXI : 1][VN];
+    float dg[MAXI][VN], db[MAXI][VN], gm[MAXI][VN], cs[MAXI][VN];
 #pragma unroll
     for (int i = 0; i < MAXI; i++) {
         int c = lane + 64 * i;
@@ -455,10 +451,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
             db[i][j] = 0.f;
             cs[i][j] = 0.f;
             gm[i][j] = (c < chunks) ? gamma[c * VN + j] : 0.f;
-            if (FUSED) be[i][j] = (c < chunks) ? fz.beta[c * VN + j] : 0.f;
         }
     }
-    constexpr int NPMAX = 2 * MAXI;             // segments of 256 columns in a row of at most 64 * MAXI chunks of 8
     // Software pipeline over the rows of this wave: the three input rows (dy, x, residual) and the statistics of the NEXT
     // row are requested before the current row is reduced and written, so ~6 KiB per wave (~96 KiB per CU at 4 waves
     // per SIMD) stay in flight.  (Before: dy/x, two wave reductions, THEN the residual row -- two exposed HBM latencies
@@ -466,17 +460,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
     struct RowIn {
         Vec16<T> dy[MAXI], x[MAXI], r[MAXI];
         float mu, rs;
-        f32x2 pt[FUSED ? NPMAX : 1];           // the row's partial statistics, merged when the row is reduced
     };
     auto fetch = [&](int row, RowIn& in) {
-        if constexpr (FUSED) {
-#pragma unroll
-            for (int sg = 0; sg < NPMAX; sg++)
-                in.pt[sg] = sg < fz.np ? *reinterpret_cast<const f32x2*>(fz.part + ((int64_t)row * fz.np + sg) * 2) : (f32x2){0.f, 0.f};
-        } else {
-            in.mu = mean[row];
-            in.rs = rstd[row];
-        }
+        in.mu = mean[row];
+        in.rs = rstd[row];
 #pragma unroll
         for (int i = 0; i < MAXI; i++) {
             const int c = lane + 64 * i;
@@ -494,24 +481,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
     for (; row < rows; row += stride) {
         const bool more = row + stride < rows;
         if (more) fetch(row + stride, nxt);
-        float mu = cur.mu, rs = cur.rs;
-        if constexpr (FUSED) {
-            float a = 0.f;
-#pragma unroll
-            for (int sg = 0; sg < NPMAX; sg++) a += cur.pt[sg][0];                 // (absent segments hold zeros)
-            mu = a / (float)fz.np;
-            float m2 = 0.f;
-#pragma unroll
-            for (int sg = 0; sg < NPMAX; sg++) {
-                const float d = cur.pt[sg][0] - mu;
-                if (sg < fz.np) m2 += cur.pt[sg][1] + 256.0f * d * d;
-            }
-            rs = __builtin_amdgcn_rsqf(m2 / (256.0f * (float)fz.np) + fz.eps);
-        }
+        const float mu = cur.mu, rs = cur.rs;
         // prescaled: dy holds rstd o gradient (the A operand of the dgrad GEMM in front was stored rstd-scaled, model.hip: backward);
         // the row's 1 / rstd gives the gradient back -- everything below is the formula of the plain form
         float dsc = 1.0f;
-        if constexpr (FUSED) { if (fz.prescaled) dsc = 1.0f / rs; }
         if constexpr (PRE) dsc = 1.0f / rs;
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -537,7 +510,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
         for (int i = 0; i < MAXI; i++) {
             int c = lane + 64 * i;
             if (c < chunks) {
-                Vec16<T> o, om, oy;
+                Vec16<T> o, om;
 #pragma unroll
                 for (int j = 0; j < VN; j++) {
                     float xh = (cur.x[i].get(j) - mu) * rs;
@@ -545,7 +518,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
                     float v = rs * (g - s1 - xh * s2);
                     if (resid) v += cur.r[i].get(j);
                     o.set(j, v);
-                    if (FUSED) oy.set(j, xh * gm[i][j] + be[i][j]);
                     if (want_colsum || dmask) {
                         // the consumer sees the STORED (rounded) value
                         float vm = drop.thr ? apply_drop_rc(drop, rowh, (uint32_t)(c * VN + j), o.get(j)) : o.get(j);
@@ -555,7 +527,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
                 }
                 st16(dx + (int64_t)row * E + c * VN, o);
                 if (dmask) st16(dmask + (int64_t)row * E + c * VN, om);
-                if constexpr (FUSED) { if (fz.yout) st16((T*)fz.yout + (int64_t)row * E + c * VN, oy); }
             }
         }
         if (more) cur = nxt;
@@ -1310,14 +1281,12 @@ extern "C" int cmp_k_layernorm_bwd_fused(void* stream, const void* dy, const voi
                                          void* ws, int rows, int E, int dtype, void* dmask, float* colsum, float p_drop,
                                          uint64_t seed, uint32_t rng_stream) {
     return layernorm_bwd_run(stream, dy, x, gamma, mean, rstd, resid, dx, dgamma, dbeta, ws, rows, E, dtype, dmask, colsum, p_drop,
-                             seed, rng_stream, false, nullptr, false);
+                             seed, rng_stream, false, false);
 }
-// The form the LayerNorm-fused block path uses (bf16, E a multiple of 256): the row statistics come as partials [rows][E/256][2]
-// (mean, M2 per 256-column segment, as the producing GEMM epilogue / embedding kernel leaves them) and the LayerNorm OUTPUT
-// yout = xhat * gamma + beta is written beside dx (null: not wanted).  dmask (null: not wanted) is written whatever p_drop is.
-// Round 6's backward pass: (mean, rstd) of every row from its partial statistics, for any number of LayerNorm sites in ONE launch
-// (grid.y = site): the backward pass of the fused block path merges all 2L sites of a step up front, and every consumer (the
-// LayerNorm backward kernels, the attention backward kernels) reads plain per-row arrays.
+// The LayerNorm-fused block path (bf16, E a multiple of 256) leaves the row statistics as partials [rows][E/256][2] (mean, M2 per
+// 256-column segment, as the producing GEMM epilogue / embedding kernel writes them).  Its backward pass turns them into (mean, rstd)
+// of every row, for any number of LayerNorm sites in ONE launch (grid.y = site): all 2L sites of a step are merged up front, and
+// every consumer (the LayerNorm backward kernels, the attention backward kernels) reads plain per-row arrays.
 struct LnMergeSite { const float* part; float* mean; float* rstd; };
 __global__ void ln_stats_merge_kernel(const LnMergeSite* __restrict__ sites, int np, float eps, int rows) {
     const LnMergeSite st = sites[blockIdx.y];
@@ -1350,19 +1319,10 @@ extern "C" int cmp_k_layernorm_bwd_prescaled(void* stream, const void* dy_scaled
                                              const float* rstd, const void* resid, void* dx, float* dgamma, float* dbeta, void* ws,
                                              int rows, int E, void* dmask, float* colsum, float p_drop, uint64_t seed, uint32_t rng_stream) {
     return layernorm_bwd_run(stream, dy_scaled, x, gamma, mean, rstd, resid, dx, dgamma, dbeta, ws, rows, E, CMP_BF16, dmask, colsum,
-                             p_drop, seed, rng_stream, false, nullptr, true, true);
+                             p_drop, seed, rng_stream, false, true, true);
 }
 extern "C" int cmp_k_wgrad_ln_fix(void* stream, float* G, int rows, int cols, const float* gamma, const float* beta, const float* colsum) {
     return wgrad_ln_fix_run(stream, G, rows, cols, gamma, beta, colsum, nullptr, 0, 0, nullptr, nullptr, nullptr);
-}
-extern "C" int cmp_k_layernorm_bwd_parts(void* stream, const void* dy, const void* x, const float* gamma, const float* beta,
-                                         const float* part, float eps, const void* resid, void* dx, void* yout, float* dgamma,
-                                         float* dbeta, void* ws, int rows, int E, void* dmask, float* colsum, float p_drop,
-                                         uint64_t seed, uint32_t rng_stream) {
-    LnBwdFused fz;
-    fz.part = part; fz.np = E / 256; fz.eps = eps; fz.beta = beta; fz.yout = yout;
-    return layernorm_bwd_run(stream, dy, x, gamma, nullptr, nullptr, resid, dx, dgamma, dbeta, ws, rows, E, CMP_BF16, dmask, colsum, p_drop,
-                             seed, rng_stream, false, &fz, true);
 }
 
 // Round 6 (the fused block path's backward pass): a Conv1D weight gradient n^T . D with n = LayerNorm(r) is accumulated by the
@@ -1415,8 +1375,8 @@ int wgrad_ln_fix_run(void* stream, float* G0, int rows0, int cols0, const float*
 // deterministic: the per-workgroup partials are folded by ONE thread per column in workgroup order (no float atomics)
 int layernorm_bwd_run(void* stream, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                       const void* resid, void* dx, float* dgamma, float* dbeta, void* ws, int rows, int E, int dtype, void* dmask,
-                      float* colsum, float p_drop, uint64_t seed, uint32_t rng_stream, bool deterministic, const LnBwdFused* fz,
-                      bool keep_dmask, bool prescaled) {
+                      float* colsum, float p_drop, uint64_t seed, uint32_t rng_stream, bool deterministic, bool keep_dmask,
+                      bool prescaled) {
     int rc = ln_check(E, dtype);
     if (rc) return rc;
     if (rows == 0) return CMP_OK;
@@ -1426,10 +1386,8 @@ int layernorm_bwd_run(void* stream, const void* dy, const void* x, const float* 
     const int vn = dtype == CMP_BF16 ? 8 : 4;
     const int maxi = cdiv(E / vn, 64);
     DropCfg dcfg = make_drop(p_drop, seed, rng_stream);
-    if (fz) CMP_REQUIRE(dtype == CMP_BF16 && fz->part && fz->beta && E % 256 == 0 && fz->np == E / 256,
-                        "layernorm_bwd: the statistics-from-partials form needs bf16 rows of a multiple of 256 columns (E=%d, np=%d)", E, fz->np);
-    // no mask: the consumer reads dx itself (the fused block path keeps the copy: there dx is overwritten before the weight gradients read it)
-    if (p_drop <= 0.f && !fz && !keep_dmask) dmask = nullptr;
+    // no mask: the consumer reads dx itself (the fused block path keeps the copy: its backward pass reads dmask with and without dropout)
+    if (p_drop <= 0.f && !keep_dmask) dmask = nullptr;
     PROF_START(8, s);
     const int want_cs = colsum != nullptr;
     // up to 256 workgroups (rows <= 2048) the per-workgroup partials go to the gradients by atomics from the kernel itself; beyond
@@ -1441,29 +1399,22 @@ int layernorm_bwd_run(void* stream, const void* dy, const void* x, const float* 
         if (smem > 65536) HIP_CHECK(hipFuncSetAttribute((const void*)layernorm_bwd_kernel<TT, MI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
         layernorm_bwd_kernel<TT, MI><<<grid, 256, smem, s>>>((const TT*)dy, (const TT*)x, gamma, mean, rstd, (const TT*)resid, (TT*)dx, (float*)ws, rows, E, (TT*)dmask, want_cs, dcfg, dg_, dbeta, colsum); \
     } while (0)
-#define LN_BWDF(MI) do { \
-        if (smem > 65536) HIP_CHECK(hipFuncSetAttribute((const void*)layernorm_bwd_kernel<bf16_t, MI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-        layernorm_bwd_kernel<bf16_t, MI, true><<<grid, 256, smem, s>>>((const bf16_t*)dy, (const bf16_t*)x, gamma, mean, rstd, (const bf16_t*)resid, (bf16_t*)dx, (float*)ws, rows, E, (bf16_t*)dmask, want_cs, dcfg, dg_, dbeta, colsum, *fz); \
-    } while (0)
 #define LN_BWDP(MI) do { \
-        if (smem > 65536) HIP_CHECK(hipFuncSetAttribute((const void*)layernorm_bwd_kernel<bf16_t, MI, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-        layernorm_bwd_kernel<bf16_t, MI, false, true><<<grid, 256, smem, s>>>((const bf16_t*)dy, (const bf16_t*)x, gamma, mean, rstd, (const bf16_t*)resid, (bf16_t*)dx, (float*)ws, rows, E, (bf16_t*)dmask, want_cs, dcfg, dg_, dbeta, colsum); \
+        if (smem > 65536) HIP_CHECK(hipFuncSetAttribute((const void*)layernorm_bwd_kernel<bf16_t, MI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
+        layernorm_bwd_kernel<bf16_t, MI, true><<<grid, 256, smem, s>>>((const bf16_t*)dy, (const bf16_t*)x, gamma, mean, rstd, (const bf16_t*)resid, (bf16_t*)dx, (float*)ws, rows, E, (bf16_t*)dmask, want_cs, dcfg, dg_, dbeta, colsum); \
     } while (0)
-    if (prescaled && !fz) {
+    if (prescaled) {
         CMP_REQUIRE(dtype == CMP_BF16 && maxi <= 4, "layernorm_bwd: the prescaled form exists for bf16 rows of at most 2048 columns");
         if (maxi == 1) LN_BWDP(1); else if (maxi == 2) LN_BWDP(2); else LN_BWDP(4);
-    } else
-    if (fz) { if (maxi == 1) LN_BWDF(1); else if (maxi == 2) LN_BWDF(2); else if (maxi <= 4) LN_BWDF(4); else LN_BWDF(8); }
-    else if (dtype == CMP_BF16) { if (maxi == 1) LN_BWD(bf16_t, 1); else if (maxi == 2) LN_BWD(bf16_t, 2); else if (maxi <= 4) LN_BWD(bf16_t, 4); else LN_BWD(bf16_t, 8); }
+    } else if (dtype == CMP_BF16) { if (maxi == 1) LN_BWD(bf16_t, 1); else if (maxi == 2) LN_BWD(bf16_t, 2); else if (maxi <= 4) LN_BWD(bf16_t, 4); else LN_BWD(bf16_t, 8); }
     else { if (maxi == 1) LN_BWD(float, 1); else if (maxi == 2) LN_BWD(float, 2); else if (maxi <= 4) LN_BWD(float, 4); else LN_BWD(float, 8); }
 #undef LN_BWD
-#undef LN_BWDF
 #undef LN_BWDP
     KERNEL_CHECK();
     if (!direct)
         ln_param_reduce_kernel<<<dim3(cdiv(3 * E, 256), deterministic ? 1 : std::min(grid, 32)), 256, 0, s>>>((const float*)ws, dgamma, dbeta, colsum, grid, E);
     {   // class 8: dy, x (+ resid) in, dx (+ the dropout-masked copy) out, mean / rstd
-        const double lb = (double)rows * ((3.0 + (resid ? 1.0 : 0.0) + (dmask ? 1.0 : 0.0) + (fz && fz->yout ? 1.0 : 0.0)) * E * dtype_size(dtype) + 8.0);
+        const double lb = (double)rows * ((3.0 + (resid ? 1.0 : 0.0) + (dmask ? 1.0 : 0.0)) * E * dtype_size(dtype) + 8.0);
         PROF_STOP(8, s, lb, lb);
     }
     KERNEL_CHECK();

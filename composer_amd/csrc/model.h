@@ -148,7 +148,6 @@ struct cmp_model {
     int st_state = 0;                  // what ST holds: 0 nothing, 1 plain transposes, 2 the fused path's set
     int64_t st_version = -1;           // ... of which param_version
     bool fused_last = false;           // the forward pass whose activations are held took the fused path (its backward must too)
-    void* dmask3 = nullptr;            // second MLP-branch masked gradient (fused path: alternates with dmask from block to block)
     // ln_f folded into the tied-logits GEMM (inference passes on the fused path): the gamma-scaled copy of wte, its fold vectors
     // (cs then bias', `lnf_npad` entries each) and the partial statistics of the last block's output rows
     bf16_t* wte_lnf = nullptr;
@@ -232,7 +231,7 @@ struct cmp_model {
     bool last_has_norm = false;        // the last enqueued step computed a norm
     bool stage_has_norm[3] = {false, false, false};
     std::vector<char> reload_seen;     // while poisoned: which parameters cmp_param_set has replaced since (all of them clears the flag)
-    int ln_fused_mode = -1;            // COMPOSER_LN_FUSED as read when the model was created (-1 unset, 0 off, 2 training passes too)
+    int ln_fused_mode = -1;            // COMPOSER_LN_FUSED as read when the model was created (-1 unset, 1 the same, 0 off, 3 training passes too)
     DecodeState* dec = nullptr;
     DecodeBatchState* decb = nullptr;  // batched decode (decode_batch.hip): its own buffers, KV caches and captured chains
     DecGrammarCfg gram[2];             // event grammar of the batch-1 chain [0] and of the batched chain [1] (cmp_decode_grammar)
@@ -285,23 +284,14 @@ int embed_bwd_run(void* stream, const int32_t* ids, const void* dh, float* dwte,
                   int dtype, float p_drop, uint64_t seed, uint32_t rng_stream, int V, float* det_ws, size_t det_ws_bytes,
                   int sort_V = 0, int* sort_ws = nullptr, int64_t sort_ws_words = 0);
 int64_t embed_bwd_sort_ws_words(int64_t ntok, int V);
-struct LnBwdFused {     // layernorm_bwd_kernel<.., FUSED>: statistics from partials, the LayerNorm output written beside dx
-    const float* part = nullptr;   // [rows][np][2]
-    int np = 0;
-    float eps = 0.f;
-    const float* beta = nullptr;
-    void* yout = nullptr;          // xhat * gamma + beta (null: not wanted)
-    int prescaled = 0;             // dy holds rstd o (the gradient): what a dgrad GEMM yields when its A operand was stored rstd-scaled
-                                   // (round 6: the weight gradients of the fused block path run on the raw LayerNorm input rows)
-};
 // G[k, j] = gamma[k] * (G[k, j] - mean_k' G[k', j]) + beta[k] * colsum[j] over one or two [rows, cols] weight gradients that were
 // accumulated as (raw rows)^T . (rstd o D): turns them into LN(raw rows)^T . D (elementwise.hip: wgrad_ln_fix_kernel)
 int wgrad_ln_fix_run(void* stream, float* G0, int rows0, int cols0, const float* gamma0, const float* beta0, const float* colsum0,
                      float* G1, int rows1, int cols1, const float* gamma1, const float* beta1, const float* colsum1);
 int layernorm_bwd_run(void* stream, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                       const void* resid, void* dx, float* dgamma, float* dbeta, void* ws, int rows, int E, int dtype, void* dmask,
-                      float* colsum, float p_drop, uint64_t seed, uint32_t rng_stream, bool deterministic, const LnBwdFused* fz = nullptr,
-                      bool keep_dmask = false, bool prescaled = false);
+                      float* colsum, float p_drop, uint64_t seed, uint32_t rng_stream, bool deterministic, bool keep_dmask = false,
+                      bool prescaled = false);     // prescaled (bf16): dy holds rstd o gradient, what a dgrad GEMM yields from an rstd-scaled A operand
 int ln_stats_merge_run(void* stream, const void* sites_dev, int nsites, int np, float eps, int rows);      // sites: {part, mean, rstd} triples of pointers
 int embed_fwd_stats_run(void* stream, const int32_t* ids, const float* wte, const float* wpe, void* out, float* part, int B, int T,
                         int E, int pos0, float p_drop, uint64_t seed, uint32_t rng_stream);

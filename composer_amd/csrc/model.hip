@@ -298,13 +298,19 @@ extern "C" int cmp_model_create(cmp_ctx* ctx, const cmp_model_cfg* cfg, cmp_mode
     const int D = Dl <= 16 ? 16 : (Dl <= 32 ? 32 : (Dl <= 64 ? 64 : 128));     // the attention kernels' head sizes; Dl < D: zero-padded columns
     CMP_REQUIRE(cfg->dtype == CMP_FP32 || cfg->dtype == CMP_BF16, "model_create: bad dtype %d", cfg->dtype);
     CMP_REQUIRE(L < 64, "model_create: at most 63 layers");
+    // COMPOSER_LN_FUSED is read ONCE per model, here (tests switch it between models): unset or 1 inference passes take the fused block
+    // path, 0 no pass does, 3 training passes take it too.  Nothing else is a mode.
+    int ln_fused_mode = -1;
+    if (const char* e = getenv("COMPOSER_LN_FUSED")) {
+        const bool known = (e[0] == '0' || e[0] == '1' || e[0] == '3') && !e[1];
+        CMP_REQUIRE(known, "model_create: COMPOSER_LN_FUSED=%.32s is not a mode: accepted are unset, 0, 1 and 3 (2, the from-partials "
+                           "training form, was removed: 3 supersedes it)", e);
+        ln_fused_mode = e[0] - '0';
+    }
     HIP_CHECK(hipSetDevice(ctx->device));
     cmp_model* m = new cmp_model();
     m->ctx = ctx;
-    {   // COMPOSER_LN_FUSED is read ONCE per model, here (tests switch it between models): 0 off, 2 / 3 training passes too
-        const char* e = getenv("COMPOSER_LN_FUSED");
-        m->ln_fused_mode = e ? atoi(e) : -1;
-    }
+    m->ln_fused_mode = ln_fused_mode;
     // a failure part-way (an allocation, an event) must not leave the buffers allocated so far behind
     const int rc = model_create_fill(m, ctx, cfg, V, E, W, L, H, D, Dl);
     if (rc != CMP_OK) { cmp_model_destroy(m); return rc; }
@@ -626,7 +632,6 @@ static int ensure_workspace_fill(cmp_model* m, int B, int T) {
     CHECK_RC(dev_alloc(m, &m->tmpE, (size_t)M * m->Ea * es));          // [M, E] gradients and the [M, Ea] attention-output gradient
     CHECK_RC(dev_alloc(m, &m->dmask, (size_t)M * E * es));
     CHECK_RC(dev_alloc(m, &m->dmask2, (size_t)M * E * es));
-    CHECK_RC(dev_alloc(m, &m->dmask3, (size_t)M * E * es));
     CHECK_RC(dev_alloc(m, &m->dfc, (size_t)M * 4 * E * es));
     CHECK_RC(dev_alloc(m, &m->dqkv, (size_t)M * 3 * m->Ea * es));
     {   // COMPOSER_DETERMINISTIC=1: no float atomics anywhere in the step -- split-K wgrads write per-split slabs and fold them
@@ -712,14 +717,13 @@ static int refresh_transposed_weights(cmp_model* m, bool fold) {
 // written by it.  Taken when every GEMM of a block reaches the persistent 256x256 kernel with whole tiles (bf16, E = 2 or 3
 // segments of 256 columns, no head padding, tokens a multiple of 256 and enough of them) and the call is a plain forward /
 // pass (no past, none of cmp_forward_ex's optional inputs).  COMPOSER_LN_FUSED=0 switches it off (A/B timing, tests).
-// Measured (profiles/r5_01_ln_fused.txt): the inference forward of C2 7.87 -> 7.65 ms; a TRAIN step loses 1.5-2 % (the two LayerNorm
-// backward kernels of a block write u / n instead of the forward kernels, and the fold GEMMs read a colder A operand than the
-// one a LayerNorm kernel has just written), so training passes take it only when COMPOSER_LN_FUSED=2 asks for it (tests), or =3: round 6's
-// form of the backward pass (weight gradients on the raw LayerNorm input rows, no u / n written at all) -- measured a tie with the
-// unfused train step (profiles/r6_02_ln_raw_training.txt).
+// Measured (profiles/r5_01_ln_fused.txt): the inference forward of C2 7.87 -> 7.65 ms.  A TRAIN step gains nothing: with the weight
+// gradients on the raw LayerNorm input rows, so that no u / n is written at all (backward(), round 6), it ties with the unfused
+// step (profiles/r6_02_ln_raw_training.txt), so training passes take the path only when COMPOSER_LN_FUSED=3 asks for it
+// (DESIGN.md §4).
 static bool ln_fused_ok(const cmp_model* m, int M, int past_len, bool training) {
     if (m->ln_fused_mode == 0) return false;
-    if (training && m->ln_fused_mode != 2 && m->ln_fused_mode != 3) return false;
+    if (training && m->ln_fused_mode != 3) return false;
     if (!m->cfg.use_layer_norm || m->dtype != CMP_BF16 || m->slab || past_len) return false;
     if (m->Ea != m->E || m->E % 256 || m->E < 512 || m->E > 768 || !m->act[0].ln1_part) return false;   // 2 or 3 segments (the fold images' LDS)
     if (M % 256 || (int64_t)(M / 256) * (m->E / 256) < GEMM_BIG_MIN_TILES) return false;      // gemm_plan's `big`: the N = E GEMMs too
@@ -740,10 +744,10 @@ static int colsum_any(cmp_model* m, const void* X, int ldx, float* out, int rows
 }
 static int ln_bwd(cmp_model* m, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                   const void* resid, void* dx, float* dgamma, float* dbeta, int rows, void* dmask, float* colsum, float p_drop,
-                  uint32_t rng_stream, const LnBwdFused* fz = nullptr, bool prescaled = false) {
-    // (fused block path: every masked copy is written, dropout or not -- dx does not live until the weight gradients there)
+                  uint32_t rng_stream, bool prescaled = false) {
+    // (fused block path: every masked copy is written, dropout or not -- there backward() takes dmo / dao from dmask / dmask2, never from dx / dr)
     return layernorm_bwd_run(m->ctx->stream, dy, x, gamma, mean, rstd, resid, dx, dgamma, dbeta, m->ln_ws, rows, m->E, m->dtype,
-                             dmask, colsum, p_drop, m->drop_seed(), rng_stream, m->slab != nullptr, fz, m->fused_last, prescaled);
+                             dmask, colsum, p_drop, m->drop_seed(), rng_stream, m->slab != nullptr, m->fused_last, prescaled);
 }
 
 // The GEMM launches of the model as launch records (gemm_plan.h: GemmDesc); the dtype and the dropout seed are the model's.
@@ -1030,76 +1034,73 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
                     m->G + m->off_lnf_g, m->G + m->off_lnf_b, M, m->dmask, m->G + m->lo[m->L - 1].pr_b, pr,
                     drop_stream(step, m->L - 1, 3)));
     bool dmo_ready = true;      // dmask / pr_b of the current layer already produced
-    // The LayerNorm-fused block path (model_forward): the forward pass wrote neither u = ln_1(x) nor n = ln_2(r) and kept their
-    // statistics as partials.  The two LayerNorm backward kernels of a block merge the partials and write u / n beside dx -- only
-    // the block's weight-gradient launch reads them, so that launch moves behind ln_1's backward; by then ln_1's backward has
-    // produced the NEXT block's MLP masked gradient, hence two alternating buffers for it.
-    const bool fused = m->fused_last;
-    // Round 6 (COMPOSER_LN_FUSED=3): the weight gradients of c_fc / c_attn run on the RAW LayerNorm input rows (r / x) --
+    // A block's backward pass runs in one of two orders.
+    // The default order: the forward pass wrote u = ln_1(x) and n = ln_2(r) with their per-row statistics, and the weight gradients of
+    // c_attn / c_fc contract over u / n (grouped into one launch per block, or one launch each where `grouped` below is false).
+    // The raw-row order (`raw`: the forward pass took the LayerNorm-fused block path of model_forward, which a training pass does only
+    // with COMPOSER_LN_FUSED=3): the forward pass wrote neither u nor n and kept their statistics as partials, and the backward pass
+    // writes no LayerNorm output either.  The weight gradients of c_fc / c_attn run on the RAW LayerNorm input rows (r / x) --
     //   n^T . D = gamma o (r^T . D' - 1 (x) (mean^T . D')) + beta (x) colsum(D),   D' = rstd o D,   mean^T . D' = column means of r^T . D'
-    // -- so the backward pass writes no LayerNorm output either: the GELU' dgrad epilogue stores D' = rstd o dfc,
-    // the attention backward kernels store rstd o [dQ | dK | dV], the dgrads that consume them yield rstd o dn / rstd o du (the residual
-    // term of du gets its rstd in the epilogue), which the LayerNorm backward kernels take as they are (LnBwdFused::prescaled), and one
-    // small pass per block applies gamma / beta and the mean term to the two accumulated gradients (wgrad_ln_fix_kernel).
-    const bool raw = fused && m->ln_fused_mode == 3;
-    // (the statistics of all 2L sites, merged from their partials in one launch: the plain LayerNorm backward kernel and the attention
-    //  backward kernels read per-row arrays; the statistics-from-partials form of the LayerNorm backward runs one wave per SIMD less)
+    // -- the GELU' dgrad epilogue stores D' = rstd o dfc, the attention backward kernels store rstd o [dQ | dK | dV], the dgrads that
+    // consume them yield rstd o dn / rstd o du (the residual term of du gets its rstd in the epilogue), which the LayerNorm backward
+    // kernels take as they are (ln_bwd: prescaled), and one small pass per block applies gamma / beta and the mean term to the two
+    // accumulated gradients (wgrad_ln_fix_kernel).  The launches keep the places they have in the default grouped order.
+    const bool raw = m->fused_last;
+    // (the statistics of all 2L sites, merged from their partials in one launch: the LayerNorm backward kernels and the attention
+    //  backward kernels read per-row arrays)
     if (raw) CHECK_RC(ln_stats_merge_run(s, m->ln_sites, 2 * m->L, E / 256, m->cfg.ln_eps, M));
-    void* const dmk[2] = {m->dmask, m->dmask3};
-    int cur = 0;
     if (allreduce) CHECK_RC(bucket_ready(m, m->L, m->off_lnf_g, m->total, lr, update));
     // The four Conv1D weight gradients of a block contract over the same M tokens: with LayerNorm, bf16 and the atomic
     // (non-deterministic) split-K form they go out as ONE grouped launch behind the block's attention backward (gemm.hip:
     // gemm_wgrad_group_kernel) -- a quarter of the f32-atomic traffic of four split-K launches, equal k-steps per workgroup.
     // Until then both masked gradient copies of the block stay live: the MLP branch's in dmask, the attention branch's in dmask2.
+    // ONE dmask serves every block, in both grouped orders: block i's MLP mask is read by the GELU' dgrad and by the grouped launch of
+    // block i and by nothing else, its only writer is ln_1's backward of block i + 1 (ln_f's for the last block), and ln_1's backward
+    // of block i -- which overwrites it with block i - 1's -- is enqueued behind block i's grouped launch on the one compute stream.
     // (COMPOSER_DETERMINISTIC=1 takes the grouped launch too since round 6, in its last-arriver form: partial tiles summed in the
     //  order of the K ranges, no float atomics -- the deterministic step runs the launch order of the default one)
     const bool grouped = ln && dt == CMP_BF16;
-    CMP_REQUIRE(!fused || grouped, "backward: the fused block path needs the grouped weight-gradient order");
+    CMP_REQUIRE(!raw || grouped, "backward: the fused block path needs the grouped weight-gradient order");
     if (grouped && (int)m->wgrad_groups.size() != m->L) m->wgrad_groups.resize(m->L);
     for (int i = m->L - 1; i >= 0; i--) {
         const LayerOff& o = m->lo[i];
         LayerAct& a = m->act[i];
-        bool group_now = grouped;
         // ---- MLP: x_out = r + dropout(gelu(n.Wfc+b).Wpr+b)
         const void* dmo = m->dx;
-        if (fused) {
-            dmo = dmk[cur];             // (also without dropout: dx is overwritten before the weight gradients read it)
+        if (raw) {
+            dmo = m->dmask;             // (also without dropout: ln_bwd keeps every masked copy on the fused block path)
         } else if (pr > 0.f) {
             if (!dmo_ready) CHECK_RC(drop_apply(m, m->dx, m->dmask, (int64_t)M * E, pr, drop_stream(step, i, 3)));
             dmo = m->dmask;
         }
-        LnBwdFused fz;
-        fz.np = E / 256; fz.eps = m->cfg.ln_eps;
         auto wgrad = [&](int Mw, int Nw, const void* A, int lda, const void* Bm, int ldb, float* Cw) {
             return gemm(m, wgrad_desc(Mw, Nw, M, A, lda, Bm, ldb, Cw, std::max(2, wgrad_splits(M, Mw, Nw))));
         };
-        if (!group_now) CHECK_RC(wgrad(4 * E, E, a.g, 4 * E, dmo, E, m->G + o.pr_w));
+        if (!grouped) CHECK_RC(wgrad(4 * E, E, a.g, 4 * E, dmo, E, m->G + o.pr_w));
         if (!dmo_ready) CHECK_RC(colsum_any(m, dmo, E, m->G + o.pr_b, M, E));
         LnEpi ls;
         ls.np = E / 256; ls.eps = m->cfg.ln_eps; ls.scale = 1;
         ls.in_part = a.ln2_part;
         CHECK_RC(gemm(m, with_gelu_grad(xw(1, M, 4 * E, E, dmo, m->w(o.pr_w), m->dfc), a.fc), m->G + o.fc_b,
                       raw ? &ls : nullptr));                                // dfc = (dmo.Wpr^T) * gelu'(fc) [raw: rstd_2 o that]; b_fc grad = column sums of dfc
-        if (!group_now) CHECK_RC(wgrad(E, 4 * E, a.n, E, m->dfc, 4 * E, m->G + o.fc_w));
-        void* const dao_mask = group_now ? m->dmask2 : m->dmask;
+        if (!grouped) CHECK_RC(wgrad(E, 4 * E, a.n, E, m->dfc, 4 * E, m->G + o.fc_w));
+        void* const dao_mask = grouped ? m->dmask2 : m->dmask;
         if (ln) {
             CHECK_RC(gemm(m, xw(1, M, E, 4 * E, m->dfc, m->w(o.fc_w), m->tmpE)));   // dn
-            fz.part = a.ln2_part; fz.beta = m->P + o.ln2_b; fz.yout = a.n;
             CHECK_RC(ln_bwd(m, m->tmpE, a.r, m->P + o.ln2_g, a.ln2_mean, a.ln2_rstd, m->dx, m->dr, m->G + o.ln2_g, m->G + o.ln2_b, M,
-                            dao_mask, m->G + o.proj_b, pr, drop_stream(step, i, 2), (fused && !raw) ? &fz : nullptr, raw));   // dr = dx + LN2'(dn); dao, b_proj grad
+                            dao_mask, m->G + o.proj_b, pr, drop_stream(step, i, 2), raw));   // dr = dx + LN2'(dn); dao, b_proj grad
         } else {
             CHECK_RC(gemm(m, with_resid(xw(1, M, E, 4 * E, m->dfc, m->w(o.fc_w), m->dr), m->dx)));   // dr = dx + dn
         }
         // ---- attention: r = u + dropout(att.Wproj+b)
         const void* dao = m->dr;
-        if (fused) {
+        if (raw) {
             dao = dao_mask;
         } else if (pr > 0.f) {
             if (!ln) CHECK_RC(drop_apply(m, m->dr, m->dmask, (int64_t)M * E, pr, drop_stream(step, i, 2)));
             dao = dao_mask;
         }
-        if (!group_now) CHECK_RC(wgrad(Ea, E, a.att, Ea, dao, E, m->G + o.proj_w));
+        if (!grouped) CHECK_RC(wgrad(Ea, E, a.att, Ea, dao, E, m->G + o.proj_w));
         if (!ln) CHECK_RC(colsum_any(m, dao, E, m->G + o.proj_b, M, E));
         CHECK_RC(gemm(m, xw(1, M, Ea, E, dao, m->w(o.proj_w), m->tmpE)));          // datt
         const bool det = m->slab != nullptr;     // the fused bias sums are float atomics: a separate fixed-order pass instead
@@ -1109,7 +1110,7 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
         if (raw) ad.ln.rstd = a.ln1_rstd;
         CHECK_RC(attn_bwd_run(s, ad));
         if (det) CHECK_RC(colsum_det(m, m->dqkv, 3 * Ea, m->G + o.attn_b, M, 3 * Ea));
-        auto group_launch = [&]() -> int {
+        if (grouped) {
             const WgradProblem wp[4] = {
                 {a.g, 4 * E, dmo, E, m->G + o.pr_w, E, 4 * E, E},                  // dWpr   = g^T . dmo
                 {raw ? a.r : a.n, E, m->dfc, 4 * E, m->G + o.fc_w, 4 * E, E, 4 * E},           // dWfc   = n^T . dfc        [raw: r^T . (rstd_2 o dfc)]
@@ -1133,11 +1134,7 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
                 CHECK_RC(wgrad_ln_fix_run(s, m->G + o.fc_w, E, 4 * E, m->P + o.ln2_g, m->P + o.ln2_b, m->G + o.fc_b,
                                           m->G + o.attn_w, E, 3 * E, m->P + o.ln1_g, m->P + o.ln1_b, m->G + o.attn_b));
             }
-            return CMP_OK;
-        };
-        if (group_now && (!fused || raw)) {
-            CHECK_RC(group_launch());
-        } else if (!group_now) {
+        } else {
             CHECK_RC(wgrad(E, 3 * Ea, a.u, E, m->dqkv, 3 * Ea, m->G + o.attn_w));
         }
         if (ln) {
@@ -1145,15 +1142,9 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
             CHECK_RC(gemm(m, with_resid(xw(1, M, E, 3 * Ea, m->dqkv, m->w(o.attn_w), m->tmpE), m->dr), nullptr,
                           raw ? &ls : nullptr));                                   // du = dr + dqkv.Wattn^T  [raw: rstd_1 o du]
             // dx_in = LN1'(du): no skip connection around LN1; feeds layer i-1's MLP branch (or the embedding for i = 0)
-            fz.part = a.ln1_part; fz.beta = m->P + o.ln1_b; fz.yout = a.u;
-            void* const next_mask = fused ? dmk[cur ^ 1] : m->dmask;
             CHECK_RC(ln_bwd(m, m->tmpE, m->xs[i], m->P + o.ln1_g, a.ln1_mean, a.ln1_rstd, nullptr, m->dx, m->G + o.ln1_g,
-                            m->G + o.ln1_b, M, i > 0 ? next_mask : nullptr, i > 0 ? m->G + m->lo[i - 1].pr_b : nullptr, pr,
-                            drop_stream(step, i > 0 ? i - 1 : 0, 3), (fused && !raw) ? &fz : nullptr, raw));
-            if (fused) {
-                if (!raw) CHECK_RC(group_launch());          // g^T.dmo, n^T.dfc, att^T.dao, u^T.dqkv -- u and n as just written
-                cur ^= 1;
-            }
+                            m->G + o.ln1_b, M, i > 0 ? m->dmask : nullptr, i > 0 ? m->G + m->lo[i - 1].pr_b : nullptr, pr,
+                            drop_stream(step, i > 0 ? i - 1 : 0, 3), raw));
             dmo_ready = true;
         } else {
             dmo_ready = false;

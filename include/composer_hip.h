@@ -718,10 +718,7 @@ int cmp_k_wgrad_group(void* stream, int nprob, const void* const* A, const int* 
  *     the OUTPUT rows are written (residual epilogues).  bf16, ta=0, tb=1, M and N multiples of 256, and a shape that reaches the
  *     persistent 256x256 kernel (CMP_GEMM_TILE256 forces it); anything else fails with CMP_ERR_INVALID.  With out_fp32 the fold also
  *     takes a ragged N (ln_f folded into the tied-logits matmul, transformer.py:811, 818: N = vocabulary size; cs and bias must then
- *     hold N rounded up to 256 entries, zero beyond N).
- *   cmp_k_layernorm_bwd_parts: cmp_k_layernorm_bwd_fused (bf16) with the statistics taken from partials and the LayerNorm OUTPUT
- *     yout = xhat*gamma + beta written beside dx (the weight-gradient GEMM of the consuming Conv1D is its only reader); dmask
- *     (when given) is written whatever p_drop is. */
+ *     hold N rounded up to 256 entries, zero beyond N). */
 int cmp_k_embed_fwd_stats(void* stream, const int32_t* ids, const float* wte, const float* wpe, void* out, float* part,
                           int B, int T, int E, int pos0, float p_drop, uint64_t seed, uint32_t rng_stream);
 int cmp_k_ln_fold_prep(void* stream, const float* W, const float* bias, const float* gamma, const float* beta, void* WT,
@@ -735,7 +732,8 @@ int cmp_gemm_ln_next(const float* in_part, int np, float eps, const float* cs, c
  *     a residual operand it stores C = acc + rstd o resid.
  *   cmp_k_ln_stats_merge: (mean, rstd) per row from the rows' partial statistics [rows][np][2] (the model merges all its sites in one launch).
  *   cmp_attn_bwd_ln_next: cmp_k_attn_bwd stores rstd[token] o [dQ | dK | dV].
- *   cmp_k_layernorm_bwd_prescaled: the LayerNorm backward (mean / rstd arrays) on a dy that holds rstd o (the gradient).
+ *   cmp_k_layernorm_bwd_prescaled: the LayerNorm backward (mean / rstd arrays) on a dy that holds rstd o (the gradient); bf16;
+ *     dmask (when given) is written whatever p_drop is.
  *   cmp_k_wgrad_ln_fix: G[k, j] = gamma[k] * (G[k, j] - mean over k' of G[k', j]) + beta[k] * colsum[j] -- turns R = (raw rows)^T .
  *     (rstd o D) into LN(raw rows)^T . D: the mean term mean^T . (rstd o D) IS the column mean of R, a row's mean being the mean of
  *     that row as stored. */
@@ -746,10 +744,6 @@ int cmp_k_layernorm_bwd_prescaled(void* stream, const void* dy_scaled, const voi
                                   const float* rstd, const void* resid, void* dx, float* dgamma, float* dbeta, void* ws,
                                   int rows, int E, void* dmask, float* colsum, float p_drop, uint64_t seed, uint32_t rng_stream);
 int cmp_k_wgrad_ln_fix(void* stream, float* G, int rows, int cols, const float* gamma, const float* beta, const float* colsum);
-int cmp_k_layernorm_bwd_parts(void* stream, const void* dy, const void* x, const float* gamma, const float* beta,
-                              const float* part, float eps, const void* resid, void* dx, void* yout, float* dgamma,
-                              float* dbeta, void* ws, int rows, int E, void* dmask, float* colsum, float p_drop,
-                              uint64_t seed, uint32_t rng_stream);
 /* Diagnostics of the model's last passes: fused = 1 when the last forward pass took the LayerNorm-fused block path;
  * wgrad_table_builds = item tables of the grouped weight-gradient launches built so far (a steady train loop builds one per
  * decoder block, once). */

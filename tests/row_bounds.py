@@ -1,5 +1,5 @@
 """Per-element error bounds for the row kernels of composer_amd/csrc/elementwise.hip: the LayerNorm family (forward, backward with its
-fused prologue, the statistics-from-partials and prescaled forms, ln_stats_merge, wgrad_ln_fix) and the fused softmax cross-entropy.
+fused prologue, the prescaled form, ln_stats_merge, wgrad_ln_fix) and the fused softmax cross-entropy.
 float64 references written out, float32 emulations that round where the kernels round, the bounds the two give, planted inputs, and
 `ln_check` / `xent_check`, which hold the arrays of one launch to all of it.  numpy and torch on the CPU; no GPU, no library.
 
@@ -13,7 +13,7 @@ Bound, per element, in the idiom of tests/attention_bounds.py:
 
 S is the size on which an fp32 evaluation of the element is resolved:
 
-    y, yout      |gamma_e| rstd_r (|x_re| + |mu_r|) + |beta_e| + |y_re|                 (|mu|: the cancellation in x - mu)
+    y            |gamma_e| rstd_r (|x_re| + |mu_r|) + |beta_e| + |y_re|                 (|mu|: the cancellation in x - mu)
     dx           rstd (|g| + A1 + |xhat| A2 + rstd (|x| + |mu|) |s2|) + |resid| + |dx|,   g = dy gamma, A1 = mean_e |g|,
                  A2 = mean_e |g| rstd (|x| + |mu|): s1 and s2 are sums of E terms of those sizes, and xhat carries the cancellation of
                  x - mu both where it multiplies s2 and inside s2.  (The issue's starting form rstd (|g| + |s1| + |xhat s2|) + |resid|
@@ -104,10 +104,9 @@ def parts_of(x):
     return np.stack([mu, ((seg - mu[..., None]) ** 2).sum(-1)], -1)
 
 
-def ln_bwd_ref(dy, x, gamma, mean, rstd, resid=None, prescaled=False, beta=None):
-    """dx = resid + rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma, on the statistics GIVEN (the arrays the kernel reads; for the
-    `_parts` form the float64 merge of the partials it reads); prescaled: dy holds rstd o gradient.  Also the summands of dgamma
-    (dy xhat) and dbeta (dy), and yout = xhat gamma + beta when beta is given."""
+def ln_bwd_ref(dy, x, gamma, mean, rstd, resid=None, prescaled=False):
+    """dx = resid + rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma, on the statistics GIVEN (the arrays the kernel reads);
+    prescaled: dy holds rstd o gradient.  Also the summands of dgamma (dy xhat) and dbeta (dy)."""
     dy, x, gamma, mu, rs = A64(dy), A64(x), A64(gamma), A64(mean)[:, None], A64(rstd)[:, None]
     if prescaled:
         dy = dy / rs
@@ -119,13 +118,8 @@ def ln_bwd_ref(dy, x, gamma, mean, rstd, resid=None, prescaled=False, beta=None)
     A1 = np.abs(g).mean(-1, keepdims=True)
     cx = rs * (np.abs(x) + np.abs(mu))
     A2 = (np.abs(g) * cx).mean(-1, keepdims=True)
-    out = dict(dx=dx + r, tg=dy * xh, tb=dy, xh=xh,
-               S_dx=rs * (np.abs(g) + A1 + np.abs(xh) * A2 + cx * np.abs(s2)) + np.abs(r) + np.abs(dx + r))
-    if beta is not None:
-        b = A64(beta)
-        out["yout"] = xh * gamma + b
-        out["S_yout"] = np.abs(gamma) * cx + np.abs(b) + np.abs(out["yout"])
-    return out
+    return dict(dx=dx + r, tg=dy * xh, tb=dy, xh=xh,
+                S_dx=rs * (np.abs(g) + A1 + np.abs(xh) * A2 + cx * np.abs(s2)) + np.abs(r) + np.abs(dx + r))
 
 
 def y_S(x, gamma, beta, ref):
@@ -171,7 +165,7 @@ def ln_fwd_emulation(x, gamma, beta, eps=EPS):
 
 
 def merge_emulation(part, eps=EPS):
-    """The in-kernel merge (layernorm_bwd_kernel FUSED; common.h: ln_merge_parts) with its fp32 roundings."""
+    """The in-kernel merge (ln_stats_merge_kernel; common.h: ln_merge_parts) with its fp32 roundings."""
     part = np.asarray(part, dtype=f32)
     npart = part.shape[1]
     mu = seq_sum32(part[:, :, 0]) / f32(npart)
@@ -182,8 +176,8 @@ def merge_emulation(part, eps=EPS):
     return dict(mean=mu, rstd=f32(1.0) / np.sqrt(m2 / (f32(256.0) * f32(npart)) + f32(eps)))
 
 
-def ln_bwd_emulation(dy, x, gamma, mean, rstd, resid=None, prescaled=False, beta=None):
-    """layernorm_bwd_kernel in float32 with sequential row sums -> dx (in front of the store), the fp32 summands tg, tb, yout."""
+def ln_bwd_emulation(dy, x, gamma, mean, rstd, resid=None, prescaled=False):
+    """layernorm_bwd_kernel in float32 with sequential row sums -> dx (in front of the store), the fp32 summands tg, tb."""
     dy, x, gamma = (np.asarray(a, dtype=f32) for a in (dy, x, gamma))
     mu, rs = np.asarray(mean, dtype=f32)[:, None], np.asarray(rstd, dtype=f32)[:, None]
     E = f32(x.shape[1])
@@ -194,10 +188,7 @@ def ln_bwd_emulation(dy, x, gamma, mean, rstd, resid=None, prescaled=False, beta
     v = rs * (g - s1 - xh * s2)
     if resid is not None:
         v = v + np.asarray(resid, dtype=f32)
-    out = dict(dx=v, tg=d * xh, tb=d)
-    if beta is not None:
-        out["yout"] = xh * gamma + np.asarray(beta, dtype=f32)
-    return out
+    return dict(dx=v, tg=d * xh, tb=d)
 
 
 def ln_bwd_grid(rows):
@@ -324,14 +315,14 @@ def figures(what, res):
                                                      " ".join("%s %.1f" % (k, v / U) for k, v in res["q"].items()))
 
 
-def ln_check(dtype, x, gamma, beta=None, eps=EPS, y=None, mean=None, rstd=None, dy=None, stats=None, part=None, resid=None,
-             prescaled=False, dx=None, yout=None, dgamma=None, dbeta=None, start_g=None, start_b=None, grid=None, dmask=None,
+def ln_check(dtype, x, gamma, beta=None, eps=EPS, y=None, mean=None, rstd=None, dy=None, stats=None, resid=None,
+             prescaled=False, dx=None, dgamma=None, dbeta=None, start_g=None, start_b=None, grid=None, dmask=None,
              keep=None, p=0.0, colsum=None, start_cs=None, what="layernorm", raise_on_fail=True):
     """The arrays of one launch against the bounds.  Operands as stored (numpy or torch; bf16 values widened).
 
     forward   y, mean, rstd given: against ln_fwd_ref of x.
     backward  dx (+ dgamma, dbeta and their start values; + dmask with keep / p, + colsum with its start) given: the statistics the
-              kernel read are `stats` = (mean, rstd) arrays, or `part`, the partials of the `_parts` form (then yout is checked too);
+              kernel read are `stats` = (mean, rstd) arrays;
               prescaled: dy holds rstd o gradient.  The masked copy and the column sums come from the dx that was STORED.
     -> dict(worst = {output: error / limit}, q = {output: q}, fails = {output: message}); raises the first failure unless told not to."""
     worst, q, fails = {}, {}, {}
@@ -345,19 +336,11 @@ def ln_check(dtype, x, gamma, beta=None, eps=EPS, y=None, mean=None, rstd=None, 
             lim, q[n] = f32_limits(emu[n], ref[n], size)
             worst[n] = within(what, n, {"mean": mean, "rstd": rstd}[n], ref[n], lim, fails)
     if dx is not None:
-        if part is not None:
-            st64, st32 = merge_ref(part, eps), merge_emulation(part, eps)
-        else:
-            st64 = dict(mean=A64(stats[0]), rstd=A64(stats[1]))
-            st32 = st64
-        ref = ln_bwd_ref(dy, x64, gamma, st64["mean"], st64["rstd"], resid, prescaled, beta if part is not None else None)
-        emu = ln_bwd_emulation(A64(dy), x64, gamma, st32["mean"], st32["rstd"], None if resid is None else A64(resid), prescaled,
-                               beta if part is not None else None)
+        mu, rs = A64(stats[0]), A64(stats[1])
+        ref = ln_bwd_ref(dy, x64, gamma, mu, rs, resid, prescaled)
+        emu = ln_bwd_emulation(A64(dy), x64, gamma, mu, rs, None if resid is None else A64(resid), prescaled)
         q["dx"] = _q(emu["dx"], ref["dx"], ref["S_dx"])
         worst["dx"] = within(what, "dx", dx, ref["dx"], limit_of(q["dx"], ref["S_dx"], ref["dx"], dtype), fails)
-        if yout is not None:
-            q["yout"] = _q(emu["yout"], ref["yout"], ref["S_yout"])
-            worst["yout"] = within(what, "yout", yout, ref["yout"], limit_of(q["yout"], ref["S_yout"], ref["yout"], dtype), fails)
         for n, got, t64, t32, st in (("dgamma", dgamma, ref["tg"], emu["tg"], start_g), ("dbeta", dbeta, ref["tb"], emu["tb"], start_b)):
             if got is None:
                 continue

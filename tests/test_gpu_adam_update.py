@@ -256,20 +256,22 @@ HISTORIES = {   # name: (dtype, E, H, L, T, B of the fixed batch, COMPOSER_LN_FU
     # ln_fused_ok (model.hip): bf16, E a multiple of 256 in [512, 768], tokens a multiple of 256 with (tokens / 256) * (E / 256) >= 192
     # -- at E = 512, T = 256 the smallest batch is B = 96.  The train step takes the plain ST, the inference pass the folded set.
     "bf16-fused": ("bf16", 512, 8, 2, 256, 96, None, 1),
-    "bf16-fused-train": ("bf16", 512, 8, 2, 256, 96, "2", 1),       # the train step itself takes the folded set
+    "bf16-fused-train": ("bf16", 512, 8, 2, 256, 96, "3", 1),       # the train step itself takes the folded set
 }
 
 
 @pytest.mark.parametrize("name", list(HISTORIES))
 def test_derived_copies_follow_the_weights(name, monkeypatch):
     """Model A lives through: forward; train step; two forwards; set_parameter of one ln_1/gamma and of ln_f/beta; loss_and_grads;
-    an evaluate on a small batch; load_state_dict of a perturbed state; an accumulated step of two micro-steps.  Wherever the weights
+    an evaluate on a small batch; load_state_dict of a perturbed state; an accumulated step of two micro-steps (COMPOSER_LN_FUSED=3
+    refuses accumulation, by name: there the refusal is asserted and one plain step follows).  Wherever the weights
     changed, A's inference logits on a fixed batch are BITWISE those of a fresh model F, created for that comparison, that received
     A.get_weights() and nothing else; wherever they did not, A's logits are bitwise the previous pass's.  Covers the bf16 shadow S,
     the transposed shadow ST in both of its states (plain / folded: asserted through cmp_model_path_info, fused on the fixed batch and
     not on the small one), the fold vectors and wte_lnf.  A stale copy moves logits by the relative size of an update (1e-3), a stale
     gamma by far more.
     Measured: all four histories repeat bitwise (two passes of F differ by 0); no tolerance is used."""
+    from composer_amd import _lib
     from composer_amd.transformer import Transformer
     dtype, E_, H_, L_, T_, B_, mode, fused = HISTORIES[name]
     if mode is None:
@@ -335,14 +337,19 @@ def test_derived_copies_follow_the_weights(name, monkeypatch):
                 sd[key] = (sd[key] * (1 + 0.02 * rng.standard_normal(sd[key].shape))).astype(np.float32)
         A.load_state_dict(sd)
         z = compare("load_state_dict of a perturbed state")
-        A.set_train_options(accumulate_steps=2)                       # 8.
-        it = A.iterations
-        A.train_step(x, y, LR)
-        assert A.iterations == it
-        forward_A(z)
+        it = A.iterations                                             # 8.
+        if mode == "3":
+            with pytest.raises(_lib.HipLibraryError, match="COMPOSER_LN_FUSED=3"):
+                A.set_train_options(accumulate_steps=2)
+            assert A.train_options()["accumulate_steps"] == 1
+        else:
+            A.set_train_options(accumulate_steps=2)
+            A.train_step(x, y, LR)
+            assert A.iterations == it
+            forward_A(z)
         A.train_step(x, y, LR)
         assert A.iterations == it + 1
-        compare("an accumulated train step")
+        compare("an accumulated train step" if mode != "3" else "a plain train step after the refused accumulation")
         assert state["compares"] == 5
     finally:
         A.close()

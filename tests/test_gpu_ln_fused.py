@@ -4,7 +4,8 @@ For large bf16 batches no LayerNorm kernel runs inside the decoder blocks' forwa
 transformer.py:574-597; LayerNormalization layers :551,563): the row statistics travel as partials (mean, M2 per 256-column
 segment) written by the producing epilogue, ln_1 / ln_2 are folded into the c_attn / c_fc GEMMs
 (LN(x).W + b = rstd*(x.(gamma o W)) - rstd*mean*colsum(gamma o W) + (beta.W + b)), the attention c_proj epilogue rebuilds
-ln_1(x) for its residual operand, and the LayerNorm backward kernels write u = ln_1(x) / n = ln_2(r) for the weight gradients.
+ln_1(x) for its residual operand.  A training pass takes the path only with COMPOSER_LN_FUSED=3 (round 6): its backward pass runs the
+weight gradients of c_attn / c_fc on the raw LayerNorm input rows and writes no u = ln_1(x) / n = ln_2(r) at all.
 
 Every new kernel form against float64 (the oracle's formulas: O.layernorm_fwd / O.gelu / O.dropout_keep_rows), then the model:
 the fused path against the unfused one and against the bf16-rounding oracle at a batch both paths can run.
@@ -222,48 +223,6 @@ def test_a_launch_that_cannot_carry_the_epilogue_fails_loudly(lib):
     torch.cuda.synchronize()
 
 
-# --------------------------------------------------------------------------------------------- LayerNorm backward from partials
-@pytest.mark.parametrize("E", [512, 768, 1024])
-@pytest.mark.parametrize("p", [0.0, 0.1])
-def test_layernorm_backward_from_partials_writes_the_forward_output(lib, E, p):
-    rows = 1500
-    rng = np.random.default_rng(E + int(10 * p))
-    x = bf(rng.normal(1.0, 2.0, (rows, E)) + seg_offsets(E))
-    dy = bf(rng.normal(0, 1.0, (rows, E)))
-    res = bf(rng.normal(0, 1.0, (rows, E)))
-    g = (1 + 0.3 * rng.normal(size=E)).astype(np.float32)
-    be = rng.normal(0, 0.2, E).astype(np.float32)
-    x64, dy64 = x.double().cpu().numpy(), dy.double().cpu().numpy()
-    part = f32(parts_of(x64))
-    ws = torch.zeros(lib.cmp_k_layernorm_bwd_ws(rows, E) // 4, device="cuda")
-    dx, yout, dmask = (torch.zeros(rows, E, dtype=torch.bfloat16, device="cuda") for _ in range(3))
-    dg, db, csum = torch.zeros(E, device="cuda"), torch.zeros(E, device="cuda"), torch.zeros(E, device="cuda")
-    ck(lib, lib.cmp_k_layernorm_bwd_parts(stream(), P(dy), P(x), P(f32(g)), P(f32(be)), P(part), EPS, P(res), P(dx), P(yout), P(dg), P(db),
-                                          P(ws), rows, E, P(dmask), P(csum), p, 5, 2))
-    torch.cuda.synchronize()
-    g64 = g.astype(np.float64)
-    mu, var = x64.mean(-1, keepdims=True), x64.var(-1, keepdims=True)
-    rs = 1 / np.sqrt(var + EPS)
-    xh = (x64 - mu) * rs
-    gg = dy64 * g64
-    want_dx = res.double().cpu().numpy() + rs * (gg - gg.mean(-1, keepdims=True) - xh * (gg * xh).mean(-1, keepdims=True))
-    assert rel(dx.double().cpu().numpy(), want_dx) < 6e-3
-    assert rel(yout.double().cpu().numpy(), xh * g64 + be) < 6e-3
-    assert rel(dg.cpu().numpy(), (dy64 * xh).sum(0)) < 1e-4
-    assert rel(db.cpu().numpy(), dy64.sum(0)) < 1e-4
-    stored = dx.double().cpu().numpy()
-    keep = O.dropout_keep_rows(5, 2, rows, E, p) if p > 0 else np.ones((rows, E), bool)
-    want_mask = np.where(keep, stored / (1 - p), 0.0)
-    assert rel(dmask.double().cpu().numpy(), want_mask) < 5e-3          # written also with p = 0: the fused path's masked copy
-    assert rel(csum.cpu().numpy(), dmask.double().cpu().numpy().sum(0)) < 1e-4
-    # ... and every element inside its own bound (tests/row_bounds.py)
-    part_h, zero = part.cpu().numpy(), np.zeros(E, np.float32)
-    assert RB.merge_ref(part_h)["share"].min() >= RB.SEG_SHARE_MIN
-    print(RB.figures("ln_bwd_parts rows %d E %d p %g" % (rows, E, p), RB.ln_check(
-        BF16, x64, g, dy=dy64, part=part_h, beta=be, eps=EPS, resid=res, dx=dx, yout=yout, dgamma=dg, dbeta=db, start_g=zero, start_b=zero,
-        dmask=dmask, keep=keep if p > 0 else None, p=p, colsum=csum, start_cs=zero)))
-
-
 # --------------------------------------------------------------------------------------------- round 6: the backward pass without u / n
 def _gelu_grad64(x):
     c, k = np.sqrt(2 / np.pi), 0.044715
@@ -421,7 +380,7 @@ def _fused(m):
     return f.value, n.value
 
 
-@pytest.mark.parametrize("form", ["2", "3"])          # 2: the LayerNorm backward kernels write u / n; 3 (round 6): weight gradients on the raw rows
+@pytest.mark.parametrize("form", ["3"])               # 3 (round 6): weight gradients on the raw rows -- the one training form of the path
 @pytest.mark.parametrize("E,H,L,T,B,p", [(512, 8, 2, 256, 96, 0.1), (768, 12, 2, 512, 32, 0.0)])
 def test_fused_path_matches_the_unfused_path_and_the_oracle(E, H, L, T, B, p, form):
     """Same weights, same batch, same dropout masks: loss and EVERY parameter gradient of the fused path against (a) the unfused
@@ -438,7 +397,7 @@ def test_fused_path_matches_the_unfused_path_and_the_oracle(E, H, L, T, B, p, fo
     x, y = O.synthetic_batch(rng, V, B, T)
     res = {}
     for mode in ("1", "0"):
-        os.environ["COMPOSER_LN_FUSED"] = form if mode == "1" else "0"         # 2 / 3: training passes take the fused path too
+        os.environ["COMPOSER_LN_FUSED"] = form if mode == "1" else "0"         # 3: training passes take the fused path too
         try:
             m = _model(E, H, L, T, B, p)
             m.set_weights(params)
@@ -617,3 +576,26 @@ def test_fused_forward_whose_logits_launch_has_fewer_tiles_than_its_block_launch
             os.environ.pop("COMPOSER_LN_FUSED", None)
     assert np.abs(out["1"][0] - out["0"][0]).max() <= 3e-2 * np.abs(out["0"][0]).max()
     assert abs(out["1"][1][0] - out["0"][1][0]) <= 2e-3 * abs(out["0"][1][0])
+
+
+def test_the_fused_path_switch_is_read_strictly():
+    """COMPOSER_LN_FUSED is read when a model is created and takes 0, 1 and 3 only: 2 (the from-partials training form, removed) and
+    anything that is no mode are refused by name, before a model exists."""
+    from composer_amd import _lib
+    from composer_amd.transformer import Transformer
+
+    def create():
+        return Transformer(V, 64, 32, 1, 2, dtype="bf16", seed=1, max_batch=1, max_seq=32)
+    try:
+        for bad in ("2", "x"):
+            os.environ["COMPOSER_LN_FUSED"] = bad
+            with pytest.raises(_lib.HipLibraryError) as e:
+                create().close()
+            assert "COMPOSER_LN_FUSED" in str(e.value) and "COMPOSER_LN_FUSED=%s " % bad in str(e.value), str(e.value)
+        for good in ("0", "1", "3", None):
+            os.environ.pop("COMPOSER_LN_FUSED", None)
+            if good is not None:
+                os.environ["COMPOSER_LN_FUSED"] = good
+            create().close()
+    finally:
+        os.environ.pop("COMPOSER_LN_FUSED", None)

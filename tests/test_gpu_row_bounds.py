@@ -39,26 +39,18 @@ construction: round-to-nearest alone uses up to 2^-8 |ref|, the BF16_OUT term.
                                        err/limit: dx 0.30 / 0.96, dgamma 0.50 / 0.36, dbeta 0.26 / 0.26, colsum 0.24 / 0.24
     ln_bwd rows 3 E 64                 q/u: dx 0.6 / 0.6, dgamma 1.2 / 0.8, dbeta 0.8 / 0.5, colsum 1.0 / 0.5
                                        err/limit: dx 0.21 / 0.85, dgamma 0.50 / 0.41, dbeta 0.38 / 0.26, colsum 0.50 / 0.26
-    ln_bwd_parts rows 2049 E 512       q/u: dx - / 3.8, yout - / 2.2, dgamma - / 5.6, dbeta - / 3.0, colsum - / 5.4
-                                       err/limit: dx - / 1.00, yout - / 1.00, dgamma - / 0.37, dbeta - / 0.23, colsum - / 0.33
     ln_stats_merge rows 2049 E 512     q/u: mean 0.4 / -, rstd 1.9 / -
                                        err/limit: mean 0.02 / -, rstd 0.08 / -
     ln_bwd_prescaled rows 2049 E 512   q/u: dx - / 2.5, dgamma - / 6.8, dbeta - / 5.6, colsum - / 4.6
                                        err/limit: dx - / 1.00, dgamma - / 0.34, dbeta - / 0.38, colsum - / 0.56
-    ln_bwd_parts rows 66 E 256         q/u: dx - / 1.4, yout - / 1.4, dgamma - / 4.0, dbeta - / 1.2, colsum - / 1.4
-                                       err/limit: dx - / 0.99, yout - / 0.99, dgamma - / 0.50, dbeta - / 0.50, colsum - / 0.34
     ln_stats_merge rows 66 E 256       q/u: mean 0.0 / -, rstd 1.4 / -
                                        err/limit: mean 0.00 / -, rstd 0.06 / -
     ln_bwd_prescaled rows 66 E 256     q/u: dx - / 1.3, dgamma - / 3.1, dbeta - / 3.4, colsum - / 1.2
                                        err/limit: dx - / 0.99, dgamma - / 0.46, dbeta - / 0.38, colsum - / 0.46
-    ln_bwd_parts rows 66 E 1024        q/u: dx - / 2.4, yout - / 1.6, dgamma - / 3.8, dbeta - / 1.3, colsum - / 1.7
-                                       err/limit: dx - / 1.00, yout - / 0.99, dgamma - / 0.43, dbeta - / 0.38, colsum - / 0.36
     ln_stats_merge rows 66 E 1024      q/u: mean 0.4 / -, rstd 1.8 / -
                                        err/limit: mean 0.02 / -, rstd 0.05 / -
     ln_bwd_prescaled rows 66 E 1024    q/u: dx - / 1.6, dgamma - / 4.0, dbeta - / 4.4, colsum - / 1.4
                                        err/limit: dx - / 0.99, dgamma - / 0.36, dbeta - / 0.35, colsum - / 0.47
-    ln_bwd_parts rows 66 E 2048        q/u: dx - / 1.4, yout - / 2.2, dgamma - / 4.9, dbeta - / 1.6, colsum - / 1.9
-                                       err/limit: dx - / 1.00, yout - / 0.99, dgamma - / 0.32, dbeta - / 0.41, colsum - / 0.38
     ln_stats_merge rows 66 E 2048      q/u: mean 0.7 / -, rstd 2.0 / -
                                        err/limit: mean 0.03 / -, rstd 0.05 / -
     ln_bwd_prescaled rows 66 E 2048    q/u: dx - / 1.4, dgamma - / 3.7, dbeta - / 3.7, colsum - / 1.8
@@ -123,7 +115,7 @@ LN_BWD = [(2048, 64, (FP32, BF16), 256, True, 2, 0, False),       # the last dir
           (1, 64, (FP32, BF16), 1, True, 1, 0, False),            # waves with no row
           (3, 64, (FP32, BF16), 1, True, 1, 0, False)]
 TWICE = (2049, 8200)                                      # launched twice on the same inputs: atomics may reorder
-PARTS = [(2049, 512), (66, 256), (66, 1024), (66, 2048)]  # `_parts`, `_prescaled`, ln_stats_merge: bf16, per-segment offsets planted
+PARTS = [(2049, 512), (66, 256), (66, 1024), (66, 2048)]  # `_prescaled`, ln_stats_merge: bf16, per-segment offsets planted
 FIX = [(512, 1536), (130, 33), (768, 40)]
 # cross-entropy: (rows, V, ldz, logits pointer offset in floats, kernel)
 XENT = [(65539, 50, 56, 0, "xent8"), (520, 390, 448, 0, "xent8"), (520, 512, 512, 0, "xent8"), (520, 8, 8, 0, "xent8"), (520, 1, 8, 0, "xent8"),
@@ -225,8 +217,8 @@ def test_layernorm_forward_within_bounds(lib, dtype, rows, E):
 
 
 # ---------------------------------------------------------------------------------------------------------------- LayerNorm backward
-def run_ln_bwd(lib, inp, dtype, rows, E, fused, form="plain", part=None, st=None):
-    """One launch in a fresh arena -> the result of ln_check.  form: plain (cmp_k_layernorm_bwd / _fused), parts, prescaled."""
+def run_ln_bwd(lib, inp, dtype, rows, E, fused, form="plain", st=None):
+    """One launch in a fresh arena -> the result of ln_check.  form: plain (cmp_k_layernorm_bwd / _fused), prescaled."""
     dt = tdt(dtype)
     ar = Arena("cuda", 8 * rows * E * 4 + (2 << 20))
     mat = lambda a, name: ar.operand(T(a), dt, rows, E, E, name=name)
@@ -241,35 +233,25 @@ def run_ln_bwd(lib, inp, dtype, rows, E, fused, form="plain", part=None, st=None
     dg, db = ar.vector(T(s_g), F32, name="dgamma", kind="acc"), ar.vector(T(s_b), F32, name="dbeta", kind="acc")
     ws = ar.scratch(int(lib.cmp_k_layernorm_bwd_ws(rows, E)), name="ws")
     p = P_FUSED if fused else 0.0
-    kw = {}
-    if form == "parts":
-        beta, pt = ar.vector(T(inp["beta"]), F32, name="beta"), ar.operand(T(part.reshape(rows, -1)), F32, rows, part[0].size, part[0].size, name="part")
-        yout, dmask = ar.output(dt, rows, E, E, name="yout"), ar.output(dt, rows, E, E, name="dmask")
+    mean, rstd = ar.vector(T(st[0]), F32, name="mean"), ar.vector(T(st[1]), F32, name="rstd")
+    kw = dict(stats=st)
+    if form == "prescaled":
+        dmask = ar.output(dt, rows, E, E, name="dmask")
         cs = ar.vector(T(s_c), F32, name="colsum", kind="acc")
         ar.arm()
-        ck(lib, lib.cmp_k_layernorm_bwd_parts(stream(), P(dy), P(x), P(gamma), P(beta), P(pt), EPS, P(resid), P(dx), P(yout), P(dg), P(db), P(ws),
-                                              rows, E, P(dmask), P(cs), p, SEED, STREAM))
-        kw = dict(part=part, beta=inp["beta"], yout=yout.host(), dmask=dmask.host(), colsum=cs.host().reshape(-1), start_cs=s_c)
+        ck(lib, lib.cmp_k_layernorm_bwd_prescaled(stream(), P(dy), P(x), P(gamma), P(mean), P(rstd), P(resid), P(dx), P(dg), P(db), P(ws),
+                                                  rows, E, P(dmask), P(cs), p, SEED, STREAM))
+        kw.update(prescaled=True, dmask=dmask.host(), colsum=cs.host().reshape(-1), start_cs=s_c)
+    elif fused:
+        dmask = ar.output(dt, rows, E, E, name="dmask")
+        cs = ar.vector(T(s_c), F32, name="colsum", kind="acc")
+        ar.arm()
+        ck(lib, lib.cmp_k_layernorm_bwd_fused(stream(), P(dy), P(x), P(gamma), P(mean), P(rstd), P(resid), P(dx), P(dg), P(db), P(ws),
+                                              rows, E, dtype, P(dmask), P(cs), p, SEED, STREAM))
+        kw.update(dmask=dmask.host(), colsum=cs.host().reshape(-1), start_cs=s_c)
     else:
-        mean, rstd = ar.vector(T(st[0]), F32, name="mean"), ar.vector(T(st[1]), F32, name="rstd")
-        kw = dict(stats=st)
-        if form == "prescaled":
-            dmask = ar.output(dt, rows, E, E, name="dmask")
-            cs = ar.vector(T(s_c), F32, name="colsum", kind="acc")
-            ar.arm()
-            ck(lib, lib.cmp_k_layernorm_bwd_prescaled(stream(), P(dy), P(x), P(gamma), P(mean), P(rstd), P(resid), P(dx), P(dg), P(db), P(ws),
-                                                      rows, E, P(dmask), P(cs), p, SEED, STREAM))
-            kw.update(prescaled=True, dmask=dmask.host(), colsum=cs.host().reshape(-1), start_cs=s_c)
-        elif fused:
-            dmask = ar.output(dt, rows, E, E, name="dmask")
-            cs = ar.vector(T(s_c), F32, name="colsum", kind="acc")
-            ar.arm()
-            ck(lib, lib.cmp_k_layernorm_bwd_fused(stream(), P(dy), P(x), P(gamma), P(mean), P(rstd), P(resid), P(dx), P(dg), P(db), P(ws),
-                                                  rows, E, dtype, P(dmask), P(cs), p, SEED, STREAM))
-            kw.update(dmask=dmask.host(), colsum=cs.host().reshape(-1), start_cs=s_c)
-        else:
-            ar.arm()
-            ck(lib, lib.cmp_k_layernorm_bwd(stream(), P(dy), P(x), P(gamma), P(mean), P(rstd), P(resid), P(dx), P(dg), P(db), P(ws), rows, E, dtype))
+        ar.arm()
+        ck(lib, lib.cmp_k_layernorm_bwd(stream(), P(dy), P(x), P(gamma), P(mean), P(rstd), P(resid), P(dx), P(dg), P(db), P(ws), rows, E, dtype))
     ar.check()
     return RB.ln_check(dtype, inp["x"], inp["gamma"], dy=dy_h, resid=inp["resid"], dx=dx.host(), dgamma=dg.host().reshape(-1),
                        dbeta=db.host().reshape(-1), start_g=s_g, start_b=s_b, keep=keep_of(rows, E, p), p=p, raise_on_fail=False, **kw)
@@ -285,23 +267,21 @@ def test_layernorm_backward_within_bounds(lib, dtype, rows, E, fused):
                run_ln_bwd(lib, inp, dtype, rows, E, fused, st=st))
 
 
-@pytest.mark.parametrize("form", ["parts", "prescaled"])
+@pytest.mark.parametrize("form", ["prescaled"])
 @pytest.mark.parametrize("rows,E", PARTS)
 def test_layernorm_backward_from_partials_and_prescaled_within_bounds(lib, rows, E, form):
     inp = RB.ln_inputs(rows, E, BF16, seed=rows + E + 2, segments=True)
     part = RB.parts_of(inp["x"]).astype(np.float32)
-    st = None
-    if form == "prescaled":
-        ar = Arena("cuda", 1 << 20)
-        npart = E // 256
-        pt = ar.operand(T(part.reshape(rows, -1)), F32, rows, 2 * npart, 2 * npart, name="part")
-        mean, rstd = ar.output(F32, 1, rows, rows, name="mean"), ar.output(F32, 1, rows, rows, name="rstd")
-        ar.arm()
-        ck(lib, lib.cmp_k_ln_stats_merge(stream(), P(pt), npart, EPS, P(mean), P(rstd), rows))
-        ar.check()
-        st = (mean.host().reshape(-1).numpy(), rstd.host().reshape(-1).numpy())
-        report("ln_stats_merge rows %d E %d" % (rows, E), RB.merge_check(part, st[0], st[1], EPS, raise_on_fail=False))
-    report("ln_bwd_%s rows %d E %d" % (form, rows, E), run_ln_bwd(lib, inp, BF16, rows, E, True, form=form, part=part, st=st))
+    ar = Arena("cuda", 1 << 20)
+    npart = E // 256
+    pt = ar.operand(T(part.reshape(rows, -1)), F32, rows, 2 * npart, 2 * npart, name="part")
+    mean, rstd = ar.output(F32, 1, rows, rows, name="mean"), ar.output(F32, 1, rows, rows, name="rstd")
+    ar.arm()
+    ck(lib, lib.cmp_k_ln_stats_merge(stream(), P(pt), npart, EPS, P(mean), P(rstd), rows))
+    ar.check()
+    st = (mean.host().reshape(-1).numpy(), rstd.host().reshape(-1).numpy())
+    report("ln_stats_merge rows %d E %d" % (rows, E), RB.merge_check(part, st[0], st[1], EPS, raise_on_fail=False))
+    report("ln_bwd_%s rows %d E %d" % (form, rows, E), run_ln_bwd(lib, inp, BF16, rows, E, True, form=form, st=st))
 
 
 @pytest.mark.parametrize("rows,cols", FIX)

@@ -1,6 +1,6 @@
 """The assertions of tests/row_bounds.py can fail (CPU; the pattern of tests/test_attention_checks_host.py).
 
-`fake_ln_fwd`, `fake_ln_bwd` and `fake_xent` are chunk- and wave-structured numpy statements of the row kernels of elementwise.hip: a
+`fake_ln_fwd`, `fake_ln_bwd`, `fake_merge` and `fake_xent` are chunk- and wave-structured numpy statements of the row kernels of elementwise.hip: a
 lane owns the 16-byte chunks lane + 64 i of a row (eight consecutive columns in the cross-entropy kernel) and the lanes are folded by
 the xor butterfly; a wave strides over the rows w, w + stride, ... with the next row prefetched; the parameter-gradient partials go
 through the 4-wave fold and then the atomics or the 32-slice reduce with its 8-way unrolled loop and tail.  Each is correct, and wrong
@@ -32,7 +32,7 @@ BUGS = {
     "s2_last_chunk": ("bwd", "dx", (FP32, BF16)), "ragged_row_dropped": ("bwd", "dgamma", (FP32, BF16)),
     "fold_three_waves": ("bwd", "dbeta", (FP32, BF16)), "reduce_tail_dropped": ("bwd", "dgamma", (FP32, BF16)),
     "resid_before_rstd": ("bwd", "dx", (FP32, BF16)), "mask_unrounded": ("bwd", "dmask", (BF16,)),       # (an fp32 store rounds nothing)
-    "colsum_unmasked": ("bwd", "colsum", (FP32, BF16)), "no_prescale": ("prescaled", "dx", (BF16,)), "merge_no_between": ("parts", "dx", (BF16,)),
+    "colsum_unmasked": ("bwd", "colsum", (FP32, BF16)), "no_prescale": ("prescaled", "dx", (BF16,)), "merge_no_between": ("merge", "rstd", (BF16,)),
     "last_col": ("xent", "dlogits", (FP32, BF16)), "lane_col7": ("xent", "dlogits", (FP32, BF16)), "pad_included": ("xent", "dlogits", (FP32, BF16)),
     "tie_high": ("xent", "row_correct", (FP32, BF16)), "next_label": ("xent", "row_loss", (FP32, BF16)), "no_max": ("xent", "row_loss", (FP32, BF16)),
     "label_no_inv_n": ("xent", "dlogits", (FP32, BF16)),
@@ -115,23 +115,24 @@ def fake_param_grads(t, start, rows, grid, bug, ragged_bug):
     return acc
 
 
-def fake_ln_bwd(dy, x, gamma, dtype, grid, start, stats=None, part=None, beta=None, resid=None, prescaled=False, keep=None, p=0.0, bug=None):
-    """layernorm_bwd_kernel (plain / fused prologue / statistics from partials / prescaled) -> dict of the arrays as stored."""
+def fake_merge(part, bug=None):
+    """ln_stats_merge_kernel (common.h: ln_merge_parts) -> mean, rstd of every row from its partials."""
+    pt = np.asarray(part, dtype=f32)
+    npart = pt.shape[1]
+    mu = RB.seq_sum32(pt[:, :, 0]) / f32(npart)
+    m2 = np.zeros(pt.shape[0], dtype=f32)
+    for s in range(npart):
+        dd = pt[:, s, 0] - mu
+        m2 = m2 + (pt[:, s, 1] if bug == "merge_no_between" else pt[:, s, 1] + f32(256.0) * dd * dd)
+    return mu, f32(1.0) / np.sqrt(m2 / (f32(256.0) * f32(npart)) + f32(EPS))
+
+
+def fake_ln_bwd(dy, x, gamma, dtype, grid, start, stats, resid=None, prescaled=False, keep=None, p=0.0, bug=None):
+    """layernorm_bwd_kernel (plain / fused prologue / prescaled) -> dict of the arrays as stored."""
     dy, x, gamma = (np.asarray(a, dtype=f32) for a in (dy, x, gamma))
     rows, E = x.shape
     VN = 8 if dtype == BF16 else 4
-    if part is not None:
-        pt = np.asarray(part, dtype=f32)
-        npart = pt.shape[1]
-        mu = RB.seq_sum32(pt[:, :, 0]) / f32(npart)
-        m2 = np.zeros(rows, dtype=f32)
-        for s in range(npart):
-            dd = pt[:, s, 0] - mu
-            m2 = m2 + (pt[:, s, 1] if bug == "merge_no_between" else pt[:, s, 1] + f32(256.0) * dd * dd)
-        rs = f32(1.0) / np.sqrt(m2 / (f32(256.0) * f32(npart)) + f32(EPS))
-    else:
-        mu, rs = np.asarray(stats[0], dtype=f32), np.asarray(stats[1], dtype=f32)
-    mu, rs = mu[:, None], rs[:, None]
+    mu, rs = np.asarray(stats[0], dtype=f32)[:, None], np.asarray(stats[1], dtype=f32)[:, None]
     d = dy * (f32(1.0) / rs) if (prescaled and bug != "no_prescale") else dy
     xh = (x - mu) * rs
     g = d * gamma
@@ -142,8 +143,6 @@ def fake_ln_bwd(dy, x, gamma, dtype, grid, start, stats=None, part=None, beta=No
     dx = RB.store(v, dtype)
     dmask = RB.dmask_of(v if bug == "mask_unrounded" else dx, keep, p, dtype)
     out = dict(dx=dx, dmask=dmask)
-    if part is not None:
-        out["yout"] = RB.store(xh * gamma + np.asarray(beta, dtype=f32), dtype)
     for n, t in (("dgamma", d * xh), ("dbeta", d), ("colsum", dx if bug == "colsum_unmasked" else dmask)):
         out[n] = fake_param_grads(t, start[n], rows, grid, bug, bug == "ragged_row_dropped" and n == "dgamma")
     return out
@@ -212,21 +211,20 @@ def check_fwd(dtype, rows, E, grid, bug=None):
 def check_bwd(dtype, rows, E, grid, form="bwd", bug=None, p=0.25):
     inp = RB.ln_inputs(rows, E, dtype, seed=rows + E + 1, segments=form != "bwd")
     st, keep = starts(E), keep_of(rows, E, p)
-    kw, fk = {}, {}
-    dy = inp["dy"]
-    if form == "parts":
-        part = RB.parts_of(inp["x"]).astype(f32)
-        fk, kw = dict(part=part, beta=inp["beta"]), dict(part=part, beta=inp["beta"])
-    else:
-        s = stats32(inp)
-        fk, kw = dict(stats=s), dict(stats=s)
-        if form == "prescaled":
-            dy = RB.store(inp["dy"].astype(np.float64) * s[1][:, None].astype(np.float64), dtype)
-            fk["prescaled"] = kw["prescaled"] = True
-    out = fake_ln_bwd(dy, inp["x"], inp["gamma"], dtype, grid, st, resid=inp["resid"], keep=keep, p=p, bug=bug, **fk)
-    return RB.ln_check(dtype, inp["x"], inp["gamma"], dy=dy, resid=inp["resid"], dx=out["dx"], yout=out.get("yout"), dgamma=out["dgamma"],
+    dy, s, pre = inp["dy"], stats32(inp), form == "prescaled"
+    if pre:
+        dy = RB.store(inp["dy"].astype(np.float64) * s[1][:, None].astype(np.float64), dtype)
+    out = fake_ln_bwd(dy, inp["x"], inp["gamma"], dtype, grid, st, s, resid=inp["resid"], prescaled=pre, keep=keep, p=p, bug=bug)
+    return RB.ln_check(dtype, inp["x"], inp["gamma"], dy=dy, stats=s, prescaled=pre, resid=inp["resid"], dx=out["dx"], dgamma=out["dgamma"],
                        dbeta=out["dbeta"], start_g=st["dgamma"], start_b=st["dbeta"], grid=grid, dmask=out["dmask"], keep=keep, p=p,
-                       colsum=out["colsum"], start_cs=st["colsum"], raise_on_fail=False, **kw)
+                       colsum=out["colsum"], start_cs=st["colsum"], raise_on_fail=False)
+
+
+def check_merge(rows, E, grid=None, bug=None):
+    """The merge of the partial statistics on the planted per-segment offsets (the geometry's grid plays no part in it)."""
+    part = RB.parts_of(RB.ln_inputs(rows, E, BF16, seed=rows + E + 1, segments=True)["x"]).astype(f32)
+    mu, rs = fake_merge(part, bug)
+    return RB.merge_check(part, mu, rs, raise_on_fail=False)
 
 
 def check_xent(dtype, rows, V, ldz, grid, bug=None):
@@ -247,8 +245,10 @@ def run_bug(kernel, dtype, bug):
         return [check_fwd(dtype, *g, bug=bug) for g in FWD_GEO[:1]]
     if kernel == "bwd":
         return [check_bwd(dtype, *g, bug=bug) for g in BWD_GEO[:2]]
-    if kernel in ("parts", "prescaled"):
+    if kernel == "prescaled":
         return [check_bwd(dtype, *g, form=kernel, bug=bug) for g in PARTS_GEO]
+    if kernel == "merge":
+        return [check_merge(*g, bug=bug) for g in PARTS_GEO]
     return [check_xent(dtype, *g, bug=bug) for g in XENT_GEO]
 
 
@@ -256,7 +256,7 @@ def run_bug(kernel, dtype, bug):
 def test_the_correct_fakes_sit_inside_every_limit(dtype):
     res = [check_fwd(dtype, *g) for g in FWD_GEO] + [check_bwd(dtype, *g) for g in BWD_GEO] + [check_xent(dtype, *g) for g in XENT_GEO]
     if dtype == BF16:
-        res += [check_bwd(dtype, *g, form=f) for g in PARTS_GEO for f in ("parts", "prescaled")]
+        res += [check_bwd(dtype, *g, form="prescaled") for g in PARTS_GEO] + [check_merge(*g) for g in PARTS_GEO]
     for r in res:
         assert not r["fails"], r["fails"]
         assert max(r["worst"].values()) <= 1.0
@@ -278,7 +278,7 @@ def test_every_bug_has_a_test_and_every_issue_bug_is_listed():
             "merge_no_between", "last_col", "lane_col7", "pad_included", "tie_high", "next_label", "no_max", "label_no_inv_n"}
     assert want <= set(BUGS)
     import inspect
-    src = "".join(inspect.getsource(f) for f in (fake_ln_fwd, fake_ln_bwd, fake_param_grads, fake_xent))
+    src = "".join(inspect.getsource(f) for f in (fake_ln_fwd, fake_merge, fake_ln_bwd, fake_param_grads, fake_xent))
     for bug in BUGS:
         assert '"%s"' % bug in src, "%s is in BUGS but no fake implements it" % bug
 
@@ -296,25 +296,17 @@ def stored_reference_bwd(dtype, rows, E, form, p):
     """The float64 reference, rounded where an output is stored, in the place of a kernel -> the arguments of ln_check."""
     inp = RB.ln_inputs(rows, E, dtype, seed=rows + E + (1 if form == "bwd" else 2), segments=form != "bwd")
     keep, st = keep_of(rows, E, p), starts(E)
-    dy, kw = inp["dy"], {}
-    if form == "parts":
-        part = RB.parts_of(inp["x"]).astype(f32)
-        m = RB.merge_ref(part)
-        s, kw = (m["mean"], m["rstd"]), dict(part=part, beta=inp["beta"])
-    else:
-        s = stats32(inp)
-        kw = dict(stats=s)
-        if form == "prescaled":
-            dy = RB.store(inp["dy"].astype(np.float64) * s[1][:, None].astype(np.float64), dtype)
-            kw["prescaled"] = True
-    ref = RB.ln_bwd_ref(dy, inp["x"], inp["gamma"], s[0], s[1], inp["resid"], form == "prescaled", inp["beta"] if form == "parts" else None)
+    dy, s = inp["dy"], stats32(inp)
+    kw = dict(stats=s)
+    if form == "prescaled":
+        dy = RB.store(inp["dy"].astype(np.float64) * s[1][:, None].astype(np.float64), dtype)
+        kw["prescaled"] = True
+    ref = RB.ln_bwd_ref(dy, inp["x"], inp["gamma"], s[0], s[1], inp["resid"], form == "prescaled")
     dx = RB.store(ref["dx"], dtype)
     dmask = RB.dmask_of(dx, keep, p, dtype)
     args = dict(dy=dy, resid=inp["resid"], dx=dx, dgamma=st["dgamma"] + ref["tg"].sum(0), dbeta=st["dbeta"] + ref["tb"].sum(0),
                 start_g=st["dgamma"], start_b=st["dbeta"], dmask=dmask, keep=keep, p=p, colsum=st["colsum"] + dmask.astype(np.float64).sum(0),
                 start_cs=st["colsum"], **kw)
-    if form == "parts":
-        args["yout"] = RB.store(ref["yout"], dtype)
     return inp, ref, args
 
 
@@ -368,7 +360,7 @@ def test_backward_geometry_reference_and_a_removed_row(dtype, rows, E, p):
 
 
 @pytest.mark.parametrize("rows,E", GB.PARTS)
-@pytest.mark.parametrize("form", ["parts", "prescaled"])
+@pytest.mark.parametrize("form", ["prescaled"])
 def test_partials_geometry_reference_and_the_between_segment_share(rows, E, form):
     inp, ref, args = stored_reference_bwd(BF16, rows, E, form, GB.P_FUSED)
     res = RB.ln_check(BF16, inp["x"], inp["gamma"], **args)
@@ -482,10 +474,13 @@ def test_the_whole_tensor_metric_passed_a_merge_without_its_between_segment_term
     for name, inp in (("old", old), ("new", new)):
         part = RB.parts_of(inp["x"]).astype(f32)
         m = RB.merge_ref(part)
-        ref = RB.ln_bwd_ref(inp["dy"], inp["x"], inp["gamma"], m["mean"], m["rstd"], inp["resid"], beta=inp["beta"])
-        out = fake_ln_bwd(inp["dy"], inp["x"], inp["gamma"], BF16, 2, starts(E), part=part, beta=inp["beta"], resid=inp["resid"], bug="merge_no_between")
-        res = RB.ln_check(BF16, inp["x"], inp["gamma"], dy=inp["dy"], part=part, beta=inp["beta"], resid=inp["resid"], dx=out["dx"], yout=out["yout"],
-                          raise_on_fail=False)
-        seen[name] = (max(rel_err(out["dx"], ref["dx"]), rel_err(out["yout"], ref["yout"])), res["fails"])
+        good = (m["mean"], m["rstd"])
+        ref = RB.ln_bwd_ref(inp["dy"], inp["x"], inp["gamma"], good[0], good[1], inp["resid"])
+        bad = fake_merge(part, bug="merge_no_between")               # the flawed merge, and the LayerNorm backward on what it wrote
+        out = fake_ln_bwd(inp["dy"], inp["x"], inp["gamma"], BF16, 2, starts(E), bad, resid=inp["resid"])
+        fails = dict(RB.merge_check(part, bad[0], bad[1], raise_on_fail=False)["fails"])
+        fails.update(RB.ln_check(BF16, inp["x"], inp["gamma"], dy=inp["dy"], stats=good, resid=inp["resid"], dx=out["dx"], raise_on_fail=False)["fails"])
+        seen[name] = (rel_err(out["dx"], ref["dx"]), np.abs(bad[1] / good[1] - 1.0), fails)
     assert seen["old"][0] < 6e-3                                      # the tolerance of test_gpu_ln_fused on its i.i.d. N(1, 2) rows
-    assert "dx" in seen["new"][1] and "yout" in seen["new"][1] and seen["new"][0] > 6e-3
+    rnd = np.isin(new["kinds"], ("off0.5", "off24", "off300"))        # planted: the rstd of EVERY random row is off by more than that
+    assert "rstd" in seen["new"][2] and "dx" in seen["new"][2] and seen["new"][1][rnd].min() > 6e-3

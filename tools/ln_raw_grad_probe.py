@@ -13,7 +13,7 @@ E, H, L, T, B = {"c2": (512, 8, 6, 1024, 128), "c2b32": (512, 8, 6, 1024, 32), "
 rng = np.random.default_rng(0)
 x = rng.integers(0, 390, (B, T), dtype=np.int32); y = rng.integers(0, 390, (B, T), dtype=np.int32)
 res = {}
-for mode in ("0", "3", "2"):
+for mode in ("0", "3"):
     os.environ["COMPOSER_LN_FUSED"] = mode
     m = Transformer(390, E, T, L, H, attention_dropout_rate=p, residual_dropout_rate=p, dtype="bf16", seed=7, max_batch=B, max_seq=T)
     m.initialize_parameters(0)
@@ -22,6 +22,6 @@ for mode in ("0", "3", "2"):
     m.close()
 print(name, "dropout", p, "losses", {k: v[0] for k, v in res.items()})
 ref = res["0"][1]
-for mode in ("3", "2"):
+for mode in ("3",):
     worst = sorted(((np.abs(res[mode][1][n] - ref[n]).max() / (np.abs(ref[n]).max() + 1e-30), n) for n in ref), reverse=True)
     print("mode", mode, "worst:", ["%s %.3g" % (n, w) for w, n in worst[:6]])

@@ -25,7 +25,7 @@ opt = m.get_optimizer_state() if hasattr(m, "get_optimizer_state") else None
 m.close()
 print("gamma range", float(min(W[n].min() for n in W if n.endswith("gamma"))), float(max(W[n].max() for n in W if n.endswith("gamma"))))
 res = {}
-for mode in ("0", "3", "2"):
+for mode in ("0", "3"):
     m = make(mode)
     m.set_weights(W)
     loss, acc = m.loss_and_grads(xs[0], ys[0])
@@ -35,6 +35,6 @@ for mode in ("0", "3", "2"):
     m.close()
 for mode in res: print("mode", mode, "loss %.5f" % res[mode][0], "traj", ["%.4f" % t for t in res[mode][2]])
 ref = res["0"][1]
-for mode in ("3", "2"):
+for mode in ("3",):
     worst = sorted(((np.abs(res[mode][1][n] - ref[n]).max() / (np.abs(ref[n]).max() + 1e-30), n) for n in ref), reverse=True)
     print("mode", mode, "worst:", ["%s %.3g" % (n, w) for w, n in worst[:8]])

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """N train steps of C2 / C2 at B=32 / C4 for a profiler run:  python3 tools/train_only.py [c2|c2b32|c4] [steps]
-(`rocprofv3 --kernel-trace --stats -- python3 tools/train_only.py c2 12`; COMPOSER_LN_FUSED=2 sends training passes down the
+(`rocprofv3 --kernel-trace --stats -- python3 tools/train_only.py c2 12`; COMPOSER_LN_FUSED=3 sends training passes down the
 LayerNorm-fused block path, =0 keeps every pass off it)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
