@@ -173,6 +173,11 @@ SIGNATURES = {
     "cmp_k_embed_fwd": (_i, [_P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _f, _u64, _u32]),
     "cmp_k_embed_bwd": (_i, [_P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _f, _u64, _u32]),
     "cmp_k_embed_bwd_v": (_i, [_P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _f, _u64, _u32, _i]),
+    "cmp_k_embed_fwd_ex": (_i, [_P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _f, _u64, _u32, _P, _P]),
+    "cmp_k_embed_bwd_det_ws": (_i64, [_i, _i]),
+    "cmp_k_embed_bwd_det": (_i, [_P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _f, _u64, _u32, _i, _P, _i64]),
+    "cmp_embed_bwd_form": (_i, [_i, _i, _i, _i, _i, _i64, _i]),
+    "cmp_embed_bwd_sort_ws_words": (_i64, [_i64, _i]),
     "cmp_k_layernorm_fwd": (_i, [_P, _P, _P, _P, _P, _P, _P, _i, _i, _f, _i]),
     "cmp_k_layernorm_bwd": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i]),
     "cmp_k_layernorm_bwd_ws": (_i64, [_i, _i]),
@@ -193,6 +198,8 @@ SIGNATURES = {
     "cmp_gemm_set_stamps": (_i, [_P]),
     "cmp_gemm_plan": (_i, [_i, _i, _i, _i, _i, _i, _P, _i, _P, _i, _P, _i, _P, _i, _P, _i, _P, _i, _i, _i, _f, _u64, _u32, _i, C.POINTER(GemmPlanInfo)]),
     "cmp_k_colsum": (_i, [_P, _P, _i, _P, _i, _i, _i]),
+    "cmp_k_colsum_det_ws": (_i64, [_i, _i, _i]),
+    "cmp_k_colsum_det": (_i, [_P, _P, _i, _P, _i, _i, _i, _P, _i64]),
     "cmp_k_attn_fwd": (_i, [_P, _P, _P, _P, _i, _i, _i, _i, _i, _i, _f, _u64, _u32]),
     "cmp_attn_bwd_bias_next": (_i, [_P]),
     "cmp_k_attn_bwd": (_i, [_P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _i, _f, _u64, _u32]),
@@ -213,7 +220,8 @@ _ADDED_LATER = {"cmp_gemm_ln_scale_next", "cmp_attn_bwd_ln_next", "cmp_k_layerno
                 "cmp_attn_plan", "cmp_attn_caps", "cmp_decode_budget", "cmp_decode_budget_state", "cmp_dataset_create", "cmp_dataset_destroy",
                 "cmp_k_batch_rows", "cmp_dataset_batch", "cmp_train_step_dataset", "cmp_dataset_set_pieces", "cmp_novelty", "cmp_k_novelty",
                 "cmp_decode_copy_guard", "cmp_decode_copy_guard_state", "cmp_k_copy_bans", "cmp_eval_dataset",
-                "cmp_k_eval_rows_ws", "cmp_k_eval_rows"}
+                "cmp_k_eval_rows_ws", "cmp_k_eval_rows", "cmp_k_embed_fwd_ex", "cmp_k_embed_bwd_det_ws", "cmp_k_embed_bwd_det",
+                "cmp_embed_bwd_form", "cmp_embed_bwd_sort_ws_words", "cmp_k_colsum_det_ws", "cmp_k_colsum_det"}
 
 _lib = None
 

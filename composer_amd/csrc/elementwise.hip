@@ -990,6 +990,12 @@ extern "C" int cmp_k_embed_fwd(void* stream, const int32_t* ids, const float* wt
                                uint32_t rng_stream) {
     return embed_fwd_run(stream, ids, wte, wpe, out, B, T, E, pos0, dtype, p_drop, seed, rng_stream, nullptr, nullptr);
 }
+// ... with the two optional per-token arrays of a forward pass (kernel-level tests; either may be null)
+extern "C" int cmp_k_embed_fwd_ex(void* stream, const int32_t* ids, const float* wte, const float* wpe, void* out,
+                                  int B, int T, int E, int pos0, int dtype, float p_drop, uint64_t seed,
+                                  uint32_t rng_stream, const int32_t* pos_ids, const int32_t* type_ids) {
+    return embed_fwd_run(stream, ids, wte, wpe, out, B, T, E, pos0, dtype, p_drop, seed, rng_stream, pos_ids, type_ids);
+}
 
 int embed_fwd_run(void* stream, const int32_t* ids, const float* wte, const float* wpe, void* out, int B, int T, int E, int pos0,
                   int dtype, float p_drop, uint64_t seed, uint32_t rng_stream, const int32_t* pos_ids, const int32_t* type_ids) {
@@ -1155,6 +1161,32 @@ int64_t embed_bwd_sort_ws_words(int64_t ntok, int V) {
     return 16 + 2ll * EMB_NB * V + V + 2ll * (V + 1) + (ntok / EMB_CH + V + 1) + ntok + 16;
 }
 
+extern "C" int64_t cmp_embed_bwd_sort_ws_words(int64_t ntok, int V) { return embed_bwd_sort_ws_words(ntok, V); }
+
+// The form embed_bwd_run takes -- 0: one f32 atomic per gradient element, 1: sorted, 2: atomic-free -- from what it is given (the
+// workspaces as "there or not").  The ONLY statement of the dispatch condition: embed_bwd_run and cmp_embed_bwd_form both ask it.
+static int embed_bwd_form(int64_t ntok, int E, int dtype, int det_V, bool det_ws, int sort_V, bool sort_ws, int64_t sort_ws_words) {
+    if (det_V > 0 && det_ws) return 2;
+    const int vn = dtype == CMP_BF16 ? 8 : 4;
+    if (sort_V > 0 && sort_ws && embed_bwd_sort_ws_words(ntok, sort_V) > 0 && sort_ws_words >= embed_bwd_sort_ws_words(ntok, sort_V) &&
+        ntok >= 4096 && E % vn == 0 && ntok < (1ll << 31)) return 1;
+    return 0;
+}
+extern "C" int cmp_embed_bwd_form(int B, int T, int E, int dtype, int V, int64_t sort_ws_words, int det) {
+    return embed_bwd_form((int64_t)B * T, E, dtype, det ? V : 0, det != 0, det ? 0 : V, sort_ws_words > 0, sort_ws_words);
+}
+
+extern "C" int64_t cmp_k_embed_bwd_det_ws(int V, int E) { return V > 0 && E > 0 ? (int64_t)V * EMB_SEG * E * 4 : 0; }
+// the atomic-free form on a workspace of the caller's (kernel-level tests; the model passes its slab)
+extern "C" int cmp_k_embed_bwd_det(void* stream, const int32_t* ids, const void* dh, float* dwte, float* dwpe,
+                                   int B, int T, int E, int pos0, int dtype, float p_drop, uint64_t seed,
+                                   uint32_t rng_stream, int V, float* ws, int64_t ws_bytes) {
+    CMP_REQUIRE(V > 0 && E > 0 && ws, "embed_bwd_det: V=%d E=%d and a workspace are required", V, E);
+    CMP_REQUIRE(ws_bytes >= cmp_k_embed_bwd_det_ws(V, E), "embed_bwd_det: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+                (long long)cmp_k_embed_bwd_det_ws(V, E));
+    return embed_bwd_run(stream, ids, dh, dwte, dwpe, B, T, E, pos0, dtype, p_drop, seed, rng_stream, V, ws, (size_t)ws_bytes, 0, nullptr, 0);
+}
+
 extern "C" int cmp_k_embed_bwd_v(void* stream, const int32_t* ids, const void* dh, float* dwte, float* dwpe,
                                  int B, int T, int E, int pos0, int dtype, float p_drop, uint64_t seed,
                                  uint32_t rng_stream, int V) {
@@ -1180,7 +1212,9 @@ int embed_bwd_run(void* stream, const int32_t* ids, const void* dh, float* dwte,
     hipStream_t s = (hipStream_t)stream;
     DropCfg d = make_drop(p_drop, seed, rng_stream);
     if (B * T == 0) return CMP_OK;
-    if (V > 0 && det_ws) {
+    const int64_t ntok = (int64_t)B * T;
+    const int form = embed_bwd_form(ntok, E, dtype, V, det_ws != nullptr, sort_V, sort_ws != nullptr, sort_ws_words);
+    if (form == 2) {
         CMP_REQUIRE((size_t)V * EMB_SEG * E * 4 <= det_ws_bytes, "embed_bwd: deterministic workspace too small");
         dim3 g1(V, EMB_SEG);
         const int g2 = (int)cdiv64((int64_t)V * E, 256), g3 = (int)cdiv64((int64_t)T * E, 256);
@@ -1195,10 +1229,7 @@ int embed_bwd_run(void* stream, const int32_t* ids, const void* dh, float* dwte,
         KERNEL_CHECK();
         return CMP_OK;
     }
-    const int64_t ntok = (int64_t)B * T;
-    const int vn = dtype == CMP_BF16 ? 8 : 4;
-    if (sort_V > 0 && sort_ws && embed_bwd_sort_ws_words(ntok, sort_V) > 0 && sort_ws_words >= embed_bwd_sort_ws_words(ntok, sort_V) &&
-        ntok >= 4096 && E % vn == 0 && ntok < (1ll << 31)) {
+    if (form == 1) {
         const int Vv = sort_V, NB = EMB_NB;
         int* nchunks = sort_ws;
         int* hist = sort_ws + 16;                       // 16-byte aligned rows of EMB_NB counts
@@ -1519,6 +1550,22 @@ extern "C" int cmp_k_colsum(void* stream, const void* X, int ldx, float* out, in
     return colsum_run(stream, X, ldx, out, rows, cols, dtype, nullptr, 0);
 }
 
+// row splits of a column-sum launch (grid.y): 64 rows or more each, at most 128, about 1024 workgroups in all
+static int colsum_splits(int rows, int cols, int vn) {
+    const int gx = cdiv(cols, 64 * vn);
+    return std::max(1, std::min(std::min(rows / 64, 128), std::max(1, 1024 / gx)));
+}
+extern "C" int64_t cmp_k_colsum_det_ws(int rows, int cols, int dtype) {
+    if (rows <= 0 || cols <= 0) return 0;
+    return (int64_t)colsum_splits(rows, cols, dtype == CMP_BF16 ? 8 : 4) * cols * 4;
+}
+// the partial-and-fold form on a workspace of the caller's (kernel-level tests; the model passes its slab)
+extern "C" int cmp_k_colsum_det(void* stream, const void* X, int ldx, float* out, int rows, int cols, int dtype, float* ws, int64_t ws_bytes) {
+    CMP_REQUIRE(ws && ws_bytes >= cmp_k_colsum_det_ws(rows, cols, dtype), "colsum_det: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+                (long long)cmp_k_colsum_det_ws(rows, cols, dtype));
+    return colsum_run(stream, X, ldx, out, rows, cols, dtype, ws, (size_t)ws_bytes);
+}
+
 // det_ws (>= 128 * cols floats): per-split partial sums + a fixed-order fold instead of float atomics
 int colsum_run(void* stream, const void* X, int ldx, float* out, int rows, int cols, int dtype, float* det_ws, size_t det_ws_bytes) {
     if (rows == 0 || cols == 0) return CMP_OK;
@@ -1526,7 +1573,7 @@ int colsum_run(void* stream, const void* X, int ldx, float* out, int rows, int c
     const int vn = dtype == CMP_BF16 ? 8 : 4;
     CMP_REQUIRE(cols % vn == 0 && ldx % vn == 0, "colsum: cols=%d and ldx=%d must be multiples of %d", cols, ldx, vn);
     const int gx = cdiv(cols, 64 * vn);
-    int splits = std::max(1, std::min(std::min(rows / 64, 128), std::max(1, 1024 / gx)));
+    const int splits = colsum_splits(rows, cols, vn);
     dim3 grid(gx, splits);
     if (det_ws) CMP_REQUIRE((size_t)splits * cols * 4 <= det_ws_bytes, "colsum: deterministic workspace too small");
     if (dtype == CMP_BF16)

@@ -657,10 +657,32 @@ int cmp_k_embed_fwd(void* stream, const int32_t* ids, const float* wte, const fl
                     int B, int T, int E, int pos0, int dtype, float p_drop, uint64_t seed, uint32_t rng_stream);
 int cmp_k_embed_bwd(void* stream, const int32_t* ids, const void* dh, float* dwte, float* dwpe,
                     int B, int T, int E, int pos0, int dtype, float p_drop, uint64_t seed, uint32_t rng_stream);
-/* the same through the sorted form the model uses for batches of 4096 tokens or more (tokens counting-sorted by id, rows of one id
- * summed before they are added: E f32 atomics per 32 rows instead of one per element); V = vocabulary size (<= 8192) */
+/* cmp_k_embed_fwd with the two optional per-token arrays of a forward pass (int32 [B*T], either may be NULL): pos_ids replaces
+ * pos0 + t as the row of wpe; type_ids names a second row of wte that is added LAST: out = ((wte[id] + wpe[pos]) + wte[type]) in
+ * fp32, then dropout, then one rounding to the output dtype.  Both NULL: exactly cmp_k_embed_fwd. */
+int cmp_k_embed_fwd_ex(void* stream, const int32_t* ids, const float* wte, const float* wpe, void* out,
+                       int B, int T, int E, int pos0, int dtype, float p_drop, uint64_t seed, uint32_t rng_stream,
+                       const int32_t* pos_ids, const int32_t* type_ids);
+/* the same through the sorted form the model uses for batches of 4096 tokens or more (tokens counting-sorted by id, up to 128 rows of
+ * one id summed by a workgroup before they are added: E f32 atomics per 128 rows instead of one per element); V = vocabulary size
+ * (<= 8192).  Below 4096 tokens, above 8192 ids or with E no multiple of 8 (bf16) / 4 (fp32) this is cmp_k_embed_bwd: see
+ * cmp_embed_bwd_form. */
 int cmp_k_embed_bwd_v(void* stream, const int32_t* ids, const void* dh, float* dwte, float* dwpe,
                       int B, int T, int E, int pos0, int dtype, float p_drop, uint64_t seed, uint32_t rng_stream, int V);
+/* the same through the atomic-free form of the deterministic mode: 64 token segments summed in order per id into ws, folded in
+ * segment order, then dwte += ; dwpe += the batch sum in batch order.  Bitwise reproducible.  ws: cmp_k_embed_bwd_det_ws(V, E) bytes
+ * (= V * 64 * E * 4), contents of no meaning before or after; fewer bytes, a NULL ws or V <= 0: CMP_ERR_INVALID and nothing is
+ * written. */
+int64_t cmp_k_embed_bwd_det_ws(int V, int E);
+int cmp_k_embed_bwd_det(void* stream, const int32_t* ids, const void* dh, float* dwte, float* dwpe,
+                        int B, int T, int E, int pos0, int dtype, float p_drop, uint64_t seed, uint32_t rng_stream, int V,
+                        float* ws, int64_t ws_bytes);
+/* Host only, no device work: the form the embedding backward takes for these arguments -- 0: one f32 atomic per gradient element,
+ * 1: sorted, 2: atomic-free.  det != 0: the deterministic mode with a workspace for V ids; otherwise V ids and a sort workspace of
+ * sort_ws_words int32 words (0: none; cmp_embed_bwd_sort_ws_words(B * T, V) is what the sorted form needs, 0 when V is outside
+ * 1..8192).  The launcher itself decides through the same function. */
+int cmp_embed_bwd_form(int B, int T, int E, int dtype, int V, int64_t sort_ws_words, int det);
+int64_t cmp_embed_bwd_sort_ws_words(int64_t ntok, int V);
 int cmp_k_layernorm_fwd(void* stream, const void* x, const float* gamma, const float* beta, void* y,
                         float* mean, float* rstd, int rows, int E, float eps, int dtype);
 /* dx = resid(optional) + LN_bwd(dy); dgamma/dbeta fp32 [E] are ACCUMULATED into; ws >= cmp_k_layernorm_bwd_ws bytes */
@@ -794,6 +816,11 @@ int cmp_gemm_plan(int dtype, int ta, int tb, int M, int N, int K, const void* A,
                   int ldc, const float* bias, int act, void* aux, int ldaux, const void* resid, int ldr, int out_fp32, int splitk,
                   float p_drop, uint64_t seed, uint32_t rng_stream, int flags, cmp_gemm_plan_info* out);
 int cmp_k_colsum(void* stream, const void* X, int ldx, float* out, int rows, int cols, int dtype);
+/* the same without float atomics, as the deterministic mode runs it: every row split writes its partial sums to ws, one fold adds
+ * them in split order, then out += .  Bitwise reproducible.  ws: cmp_k_colsum_det_ws(rows, cols, dtype) bytes (splits * cols * 4);
+ * fewer bytes or a NULL ws: CMP_ERR_INVALID and nothing is written. */
+int64_t cmp_k_colsum_det_ws(int rows, int cols, int dtype);
+int cmp_k_colsum_det(void* stream, const void* X, int ldx, float* out, int rows, int cols, int dtype, float* ws, int64_t ws_bytes);
 /* causal attention on qkv [B,T,3E] (head-merged, transformer.py:417): o [B,T,E], lse fp32 [B,H,T] */
 int cmp_k_attn_fwd(void* stream, const void* qkv, void* o, float* lse, int B, int T, int H, int D,
                    int scale, int dtype, float p_drop, uint64_t seed, uint32_t rng_stream);

@@ -609,16 +609,21 @@ def test_embedding_guarded(lib, dtype, B, T, E, V):
     dwte0, dwpe0 = torch.randn(V, E, generator=g), torch.randn(W, E, generator=g)
     rw = dwte0.double().clone(); rw.index_add_(0, ids.reshape(-1).long(), d)
     rp = dwpe0.double().clone(); rp[pos0:pos0 + T] += d.reshape(B, T, E).sum(0)
-    for sorted_form in (False, True):
-        dwte = ar.accumulator(dwte0, F32, V, E, E, name="dwte%d" % sorted_form)
-        dwpe = ar.accumulator(dwpe0, F32, W, E, E, name="dwpe%d" % sorted_form)
+    # the form each launch takes (cmp_embed_bwd_form: 0 atomic, 1 sorted): cmp_k_embed_bwd_v brings a sort workspace, but below 4096
+    # tokens -- the (3, 17, ...) case -- its launch is the atomic form a second time
+    for entry, want in (("bwd", "atomic"), ("bwd_v", "sorted" if B * T >= 4096 else "atomic")):
+        words = lib.cmp_embed_bwd_sort_ws_words(B * T, V) if entry == "bwd_v" else 0
+        form = ("atomic", "sorted", "atomic-free")[lib.cmp_embed_bwd_form(B, T, E, dtype, V, words, 0)]
+        assert form == want, (entry, form)
+        dwte = ar.accumulator(dwte0, F32, V, E, E, name="dwte_%s_%s" % (entry, form))
+        dwpe = ar.accumulator(dwpe0, F32, W, E, E, name="dwpe_%s_%s" % (entry, form))
         ar.arm()
-        if sorted_form:
+        if entry == "bwd_v":
             ck(lib, lib.cmp_k_embed_bwd_v(stream(), P(ids_s), P(dh), P(dwte), P(dwpe), B, T, E, pos0, dtype, p, 5, 2, V))
         else:
             ck(lib, lib.cmp_k_embed_bwd(stream(), P(ids_s), P(dh), P(dwte), P(dwpe), B, T, E, pos0, dtype, p, 5, 2))
         ar.check()
-        assert TK.rel_err(dwte.host(), rw) < 2e-5 and TK.rel_err(dwpe.host(), rp) < 2e-5, sorted_form
+        assert TK.rel_err(dwte.host(), rw) < 2e-5 and TK.rel_err(dwpe.host(), rp) < 2e-5, (entry, form)
         assert torch.equal(dwpe.host()[:pos0], dwpe0[:pos0])
         ar.freeze(dwte, dwpe)
 

@@ -707,7 +707,7 @@ def test_embedding_fwd_bwd(lib, dtype):
 @pytest.mark.parametrize("B,T,E,V,p", [(8, 512, 512, 390, 0.3), (5, 1000, 768, 1384, 0.0), (33, 128, 64, 3, 0.1), (2, 2048, 1024, 8000, 0.2),
                                        (16, 256, 2048, 390, 0.0)])
 def test_embedding_bwd_sorted_form(lib, dtype, B, T, E, V, p):
-    """cmp_k_embed_bwd_v: the form the model's backward pass uses from 4096 tokens on -- tokens counting-sorted by id, up to 32 rows
+    """cmp_k_embed_bwd_v: the form the model's backward pass uses from 4096 tokens on -- tokens counting-sorted by id, up to 128 rows
     of one id summed by a workgroup before E atomics, position gradient as a per-position batch sum -- against float64 index_add /
     batch sums with the oracle's dropout masks; ids skewed (half the tokens share three ids), ids that never occur, and the
     gradients ACCUMULATE into what the buffers hold (the tied logits gradient is already in dwte when the model gets here)."""
