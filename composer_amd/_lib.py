@@ -78,6 +78,11 @@ class AttnPlanInfo(C.Structure):
                 ("bias_pass", C.c_int32), ("cls", C.c_int32 * 2), ("work", C.c_double * 2), ("bytes", C.c_double * 2), ("empty", C.c_int32)]
 
 
+class WgradPlanInfo(C.Structure):
+    """cmp_wgrad_plan_info: the grouped weight-gradient launch's plan for one problem list (host only; tests/test_wgrad_group_plan_host.py)."""
+    _fields_ = [(n, C.c_int32) for n in ("fits", "taken", "refusal", "wgs", "tiles", "nk", "nitems", "grid", "max_split", "longest", "nslots")]
+
+
 _P = C.c_void_p
 _i, _f, _i64, _u64, _u32 = C.c_int, C.c_float, C.c_int64, C.c_uint64, C.c_uint32
 
@@ -193,6 +198,9 @@ SIGNATURES = {
     "cmp_k_wgrad_ln_fix": (_i, [_P, _P, _i, _i, _P, _P, _P]),
     "cmp_model_path_info": (_i, [_P, C.POINTER(_i), C.POINTER(_i64)]),
     "cmp_k_wgrad_group": (_i, [_P, _i, _P, _P, _P, _P, _P, _P, _P, _P, _i]),
+    "cmp_k_wgrad_group_bias": (_i, [_P, _i, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P]),
+    "cmp_wgrad_group_plan": (_i, [_i, _P, _P, _P, _P, _P, _P, _i, _i, _i, C.POINTER(WgradPlanInfo), _P, _i]),
+    "cmp_model_bias_path": (_i, [_P, C.POINTER(_i)]),
     "cmp_gemm_set_workspace": (_i, [_P, _i64]),
     "cmp_gemm_colsum_next": (_i, [_P]),
     "cmp_gemm_set_stamps": (_i, [_P]),
@@ -221,7 +229,8 @@ _ADDED_LATER = {"cmp_gemm_ln_scale_next", "cmp_attn_bwd_ln_next", "cmp_k_layerno
                 "cmp_k_batch_rows", "cmp_dataset_batch", "cmp_train_step_dataset", "cmp_dataset_set_pieces", "cmp_novelty", "cmp_k_novelty",
                 "cmp_decode_copy_guard", "cmp_decode_copy_guard_state", "cmp_k_copy_bans", "cmp_eval_dataset",
                 "cmp_k_eval_rows_ws", "cmp_k_eval_rows", "cmp_k_embed_fwd_ex", "cmp_k_embed_bwd_det_ws", "cmp_k_embed_bwd_det",
-                "cmp_embed_bwd_form", "cmp_embed_bwd_sort_ws_words", "cmp_k_colsum_det_ws", "cmp_k_colsum_det"}
+                "cmp_embed_bwd_form", "cmp_embed_bwd_sort_ws_words", "cmp_k_colsum_det_ws", "cmp_k_colsum_det",
+                "cmp_k_wgrad_group_bias", "cmp_wgrad_group_plan", "cmp_model_bias_path"}
 
 _lib = None
 

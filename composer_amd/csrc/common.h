@@ -84,9 +84,7 @@ struct WgradWs {
     size_t bytes = 0;
 };
 void wgrad_ws_free(WgradWs* w);
-// One launch for several split-K weight gradients that contract over the same K rows (gemm.hip: gemm_wgrad_group_kernel):
-// problem i is C_i[M_i, N_i] (fp32, accumulated into) += A_i^T . B_i with A_i stored [K, M_i] and B_i stored [K, N_i], bf16.
-struct WgradProblem { const void* A; int lda; const void* B; int ldb; float* C; int ldc; int M, N; };
+#include "wgrad_plan.h"     // WgradProblem and the grouped weight-gradient launch's plan (fits / taken / item table): host-only, no HIP
 struct WgradGroup {              // owned by the caller, one per call site whose problems keep their pointers (a decoder block)
     void* dev = nullptr;         // device copy of the problem descriptors + the item table
     size_t dev_bytes = 0;

@@ -1501,9 +1501,15 @@ __device__ __forceinline__ bf16x8 p_frag(const char* img, int t16, int lane) {
 // depth.  Grouped, the block's 48 output tiles (C2) are cut stream-K fashion into one contiguous (tile, k-range) segment per
 // workgroup -- a segment that crosses a tile boundary becomes two items -- so the block pays for ~300 partial tiles once instead of
 // 4 x 256, every workgroup contracts the same number of k-steps, and the workgroups of an XCD are given segments of the same K
-// octant (its L2 fetches each operand panel once).  The host builds the item table (gemm_wgrad_group_run).
-#define WG_MAXP 8
-struct WgProb { const bf16_t* A; const bf16_t* B; float* C; int M, N, lda, ldb, ldc, pad; };      // 48 bytes, in device memory
+// octant (its L2 fetches each operand panel once).  The host builds the item table (wgrad_plan.h, wgrad_group_run).
+//
+// Bias gradients ride on the launch (WgProb::bias, the float-atomic form only): the bias gradient of a Conv1D is the column sum,
+// over the tokens, of the B operand of its weight gradient, and the k-loop holds every B fragment in registers -- colsum(B) =
+// 1^T . B is one more MFMA per B fragment with a constant all-ones A fragment (cs[j] = mfma(ones, fb[j], cs[j])): no LDS read, no
+// global read, no pass of its own.  Only the wm == 0 waves of the items of tile row 0 (m0 == 0) of a problem with a bias pointer
+// do it (every (column tile, k-step) of B exactly once: wgrad_plan.h), in a second instantiation of the stage loop chosen outside
+// the k-loop; all 16 rows of cs[j] are equal, lanes 0-15 add row 0 to bias[] with the float atomics the tile itself uses.
+struct WgProb { const bf16_t* A; const bf16_t* B; float* C; int M, N, lda, ldb, ldc, pad; float* bias; };      // 56 bytes, in device memory
 // item table entry: {meta, m0 | n0 << 16, first k-step, end k-step}; first == end: nothing to do.
 // meta = problem | index of this K range among the tile's << 4 | K ranges of the tile << 12 | tile << 20
 //
@@ -1549,11 +1555,14 @@ __device__ __forceinline__ void p4_body(int M, int N, int K, const bf16_t* __res
 
     int cur_split = 0;
     int cur_meta = 0;                                     // grouped: the item's meta word (tile, K range index and count)
+    float* cur_bias = nullptr;                            // grouped, float-atomic form: the item's problem also sums B's columns into it
+    constexpr bool CSUM = GROUPED && !WGLA;
     auto item_coords = [&](int item, int& m0, int& n0, int& kt0, int& kt1) {
         if constexpr (GROUPED) {
             const int4 d = gitems[item];                  // wave-uniform index: scalar loads
             const WgProb pr = gprobs[d.x & 15];
             cur_meta = d.x;
+            if constexpr (CSUM) cur_bias = pr.bias;
             A = pr.A; B = pr.B; C = pr.C; M = pr.M; N = pr.N; lda = pr.lda; ldb = pr.ldb; ldc = pr.ldc;
             m0 = d.y & 0xFFFF;
             n0 = (int)((unsigned)d.y >> 16);
@@ -1580,6 +1589,14 @@ __device__ __forceinline__ void p4_body(int M, int N, int K, const bf16_t* __res
         return make_srd(base, bytes);
     };
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_char*)smem;     // LDS byte address of the staging area
+    // Grouped kernels, cold per-item sites only (the bias atomics, the scheduler's peek / steal): the lane number through an opaque
+    // move, so that what is derived from it is computed where it is used -- hoisted out of the item loop, those per-lane addresses
+    // were live across the k-loops, beyond the 256 registers, and got spilled.
+    auto cold_lane = [&]() {
+        int l = lane;
+        if constexpr (GROUPED) asm volatile("" : "+v"(l));
+        return l;
+    };
 
     int item = blockIdx.x;
     if (item >= nitems) return;
@@ -1657,6 +1674,8 @@ __device__ __forceinline__ void p4_body(int M, int N, int K, const bf16_t* __res
 #pragma unroll
             for (int j = 0; j < 4; j++) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
         const int n = run ? kt1 - kt0 : 0;
+        // the column sums of B that ride on this item (see WgProb): wave-uniform, decided per item, outside the k-loop
+        const bool cs_on = CSUM && cur_bias != nullptr && m0 == 0 && wm == 0;
         // Software pipeline ACROSS the barrier: the wait+barrier that publishes stage t+1 sits inside stage t's 32
         // MFMAs and stage t+1's B fragments + first A fragment are read right after it, under the remaining MFMAs.
         bf16x8 fb[4], fa0;
@@ -1678,8 +1697,9 @@ __device__ __forceinline__ void p4_body(int M, int N, int K, const bf16_t* __res
         // Stagger (8-wave tile only): waves w and w+4 share a SIMD; waves 0-3 take the stage barrier after MFMA group
         // 3, waves 4-7 before group 0 (same barrier count) so the partners run half a stage apart.  With NWM == 1 the
         // SIMD partner belongs to the other, independent workgroup.
-        auto run_stage = [&](int t, auto BAR) {
+        auto run_stage = [&](int t, auto BAR, auto CSF, f32x4* cs) {
             constexpr int bar_at = decltype(BAR)::value;     // barrier after this MFMA group (-1: before group 0)
+            constexpr bool CS = decltype(CSF)::value;        // this item also sums B's columns: four MFMAs more in group 0
             const char* ia = smem + (t % NST) * STAGE;
             const char* nia = smem + ((t + 1) % NST) * STAGE;
             bf16x8 fa[8], fbn[4], fa0n;
@@ -1722,6 +1742,15 @@ __device__ __forceinline__ void p4_body(int M, int N, int K, const bf16_t* __res
                     if (SWAP) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
                     else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
                 }
+                if constexpr (CS) {
+                    if (i == 0) {            // 1^T . B: every row of cs[j] becomes the column sums of this stage's B fragment
+                        bf16x8 ones;
+#pragma unroll
+                        for (int e = 0; e < 8; e++) ones[e] = (bf16_t)1.0f;
+#pragma unroll
+                        for (int j = 0; j < 4; j++) cs[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, fb[j], cs[j], 0, 0, 0);
+                    }
+                }
             }
             if (t + 1 < n) {
 #pragma unroll
@@ -1729,10 +1758,27 @@ __device__ __forceinline__ void p4_body(int M, int N, int K, const bf16_t* __res
                 fa0 = fa0n;
             }
         };
-        if (NWM == 1 || wave < 4) {
-            for (int t = 0; t < n; t++) run_stage(t, std::integral_constant<int, 3>());
+        if (CSUM && cs_on) {          // (wm == 0: waves 0-3 of the 8-wave tile)
+            if constexpr (CSUM) {
+                // the sums live in this branch only (the other instantiations keep their register budget): out they go right
+                // behind the k-loop, ahead of the next item's stage DMAs, drained with the tile's own atomics at the item's end
+                f32x4 cs[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) cs[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                for (int t = 0; t < n; t++) run_stage(t, std::integral_constant<int, 3>(), std::true_type(), cs);
+                if (n > 0) {                   // all 16 rows of cs[j] are equal: lanes 0-15 hold row 0 in element 0
+                    const int cl = cold_lane();
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const int col = n0 + wn * 64 + j * 16 + (cl & 15);
+                        if (cl < 16 && col < N) atomicAdd(cur_bias + col, cs[j][0]);
+                    }
+                }
+            }
+        } else if (NWM == 1 || wave < 4) {
+            for (int t = 0; t < n; t++) run_stage(t, std::integral_constant<int, 3>(), std::false_type(), nullptr);
         } else {
-            for (int t = 0; t < n; t++) run_stage(t, std::integral_constant<int, -1>());
+            for (int t = 0; t < n; t++) run_stage(t, std::integral_constant<int, -1>(), std::false_type(), nullptr);
         }
         stamp(20);
         if (pl.ctr && tid == 0) *slot = pl.claimed(slot);
@@ -1760,7 +1806,7 @@ __device__ __forceinline__ void p4_body(int M, int N, int K, const bf16_t* __res
         }
         stamp(22);
         uint32_t seen = 0;
-        if (!has_next && pl.ctr && wave == 0) seen = pl.peek(lane);
+        if (!has_next && pl.ctr && wave == 0) seen = pl.peek(cold_lane());
         if (!run) {
         } else if (SWAP) {
             // per wave [16 rows][64 floats] = 4 KiB, 16-byte chunks xor-swizzled by the row
@@ -1808,7 +1854,8 @@ __device__ __forceinline__ void p4_body(int M, int N, int K, const bf16_t* __res
             if (nsp > 1) {
                 typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));
                 const int s0 = la.slot0[tile];
-                const int voff = ((wave * 32) * 64 + lane) * 16;
+                const int el = cold_lane();
+                const int voff = ((wave * 32) * 64 + el) * 16;
                 {
                     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(la.ws + (int64_t)(s0 + spi) * 65536), 0, 262144, 0x00020000);
 #pragma unroll
@@ -1831,12 +1878,12 @@ __device__ __forceinline__ void p4_body(int M, int N, int K, const bf16_t* __res
                     for (int q = 0; q < nsp; q++) {
                         const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)(la.ws + (int64_t)(s0 + q) * 65536), 0, 262144, 0x00020000);
 #pragma unroll
-                        for (int h = 0; h < 2; h++) {             // sixteen 16-byte loads in flight per lane
-                            u32x4_ t[16];
+                        for (int h = 0; h < 4; h++) {             // eight 16-byte loads in flight per lane (sixteen: 32 registers more than the
+                            u32x4_ t[8];                          //  kernel has beside its accumulators -- they went to scratch)
 #pragma unroll
-                            for (int e = 0; e < 16; e++) t[e] = __builtin_amdgcn_raw_buffer_load_b128(rr, voff + (h * 16 + e) * 1024, 0, 16);
+                            for (int e = 0; e < 8; e++) t[e] = __builtin_amdgcn_raw_buffer_load_b128(rr, voff + (h * 8 + e) * 1024, 0, 16);
 #pragma unroll
-                            for (int e = 0; e < 16; e++) acc[h * 4 + e / 4][e % 4] += __builtin_bit_cast(f32x4, t[e]);
+                            for (int e = 0; e < 8; e++) acc[h * 2 + e / 4][e % 4] += __builtin_bit_cast(f32x4, t[e]);
                         }
                     }
                     if (tid == 0) __hip_atomic_store(la.cnt + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // for the next launch
@@ -1844,12 +1891,13 @@ __device__ __forceinline__ void p4_body(int M, int N, int K, const bf16_t* __res
             }
             if (mine) {
                 float* Cf = (float*)Ccur;
+                const int el = cold_lane();
 #pragma unroll
                 for (int i = 0; i < 8; i++)
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
-                        const int col = cn0 + wn * 64 + j * 16 + (lane & 15);
-                        const int row0 = cm0 + wm * 128 + i * 16 + (lane >> 4) * 4;
+                        const int col = cn0 + wn * 64 + j * 16 + (el & 15);
+                        const int row0 = cm0 + wm * 128 + i * 16 + (el >> 4) * 4;
                         if (col < Ncur) {
 #pragma unroll
                             for (int r = 0; r < 4; r++)
@@ -1859,12 +1907,13 @@ __device__ __forceinline__ void p4_body(int M, int N, int K, const bf16_t* __res
             }
         } else {
             float* Cf = (float*)Ccur;
+            const int el = cold_lane();
 #pragma unroll
             for (int i = 0; i < 8; i++)
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    const int col = cn0 + wn * 64 + j * 16 + (lane & 15);
-                    const int row0 = cm0 + wm * 128 + i * 16 + (lane >> 4) * 4;
+                    const int col = cn0 + wn * 64 + j * 16 + (el & 15);
+                    const int row0 = cm0 + wm * 128 + i * 16 + (el >> 4) * 4;
                     if (col < Ncur) {
                         if (row0 + 0 < Mcur) atomicAdd(Cf + (int64_t)(row0 + 0) * ldccur + col, acc[i][j][0]);
                         if (row0 + 1 < Mcur) atomicAdd(Cf + (int64_t)(row0 + 1) * ldccur + col, acc[i][j][1]);
@@ -1880,8 +1929,9 @@ __device__ __forceinline__ void p4_body(int M, int N, int K, const bf16_t* __res
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             if (wave == 0) {
-                const int got = pl.steal(lane, seen, slot);
-                if (lane == 0) *slot = got;
+                const int sl = cold_lane();
+                const int got = pl.steal(sl, seen, slot);
+                if (sl == 0) *slot = got;
             }
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
@@ -2196,15 +2246,7 @@ void sched_ws_free(SchedWs* w) {
     if (w && w->dev) { (void)hipFree(w->dev); w->dev = nullptr; }
 }
 
-// ---- grouped weight gradients: the item table ---------------------------------------------------------------------------
-// All T output tiles (of all problems) are cut into the SAME s = floor(G / T) K ranges; item lin = range * T + tile, dealt to the
-// XCD groups in consecutive runs like every persistent launch here: the workgroups of an XCD contract the same rows of
-// different tiles in step, so its L2 fetches each operand panel once.  (A stream-K cut -- one contiguous range of exactly
-// T * nk / G k-steps per workgroup -- was built first and measured: every workgroup equally long, but the ranges of an XCD start
-// at unrelated rows, nothing is shared through L2, and the launch took 890 us at K = 131072 where this form is predicted at
-// ~800 and four split-K launches take 902-954; at C4's 108 tiles it lost 3.6 % of the step.)
-// Cost model in k-steps of 32 (tools/kbench.py wgradgroup: 0.91 us per k-step, 54 us = 59 k-steps of atomic epilogue per launch):
-// grouped = ceil(nk / s) * rounds + 59 against the sum over problems of nk / split_p + 59 -- the grouped launch is used when it wins.
+// ---- grouped weight gradients: the launch (the item table and the decision whether to take it are wgrad_plan.h's) --------------
 void wgrad_group_free(WgradGroup* g) {
     if (g && g->dev) { (void)hipFree(g->dev); g->dev = nullptr; g->dev_bytes = 0; g->key.clear(); }
 }
@@ -2216,30 +2258,34 @@ void wgrad_ws_free(WgradWs* w) {
 int wgrad_group_run(void* stream, WgradGroup* g, const WgradProblem* probs, int nprob, int K, const GemmExtra& ex, bool* handled) {
     *handled = false;
     hipStream_t s = (hipStream_t)stream;
+    static_assert(WG_BK == P_BK, "wgrad_plan.h cuts K in the kernel's k-steps");
     const int G = (ex.max_wgs > 0 ? std::min(ex.max_wgs, 256) : 256) & ~7;
-    if (nprob < 1 || nprob > WG_MAXP || K < P_BK || K % P_BK != 0 || G < 8 || ex.slab_ws) return CMP_OK;
-    for (int i = 0; i < nprob; i++) {
-        const WgradProblem& q = probs[i];
-        if (q.M <= 0 || q.N <= 0 || q.M >= 65536 - 256 || q.N >= 65536 - 256 || q.lda % 8 || q.ldb % 8 || ((uintptr_t)q.A & 15) || ((uintptr_t)q.B & 15) ||
-            (int64_t)K * q.lda * 2 >= 0x7FFFFFF0ll || (int64_t)K * q.ldb * 2 >= 0x7FFFFFF0ll)
-            return CMP_OK;
-    }
+    if (nprob < 1 || nprob > WG_MAXP || ex.slab_ws) return CMP_OK;             // (wgrad_plan.h refuses these too; everything else it looks at is in the key)
+    const bool la = ex.wws != nullptr;
+    for (int i = 0; i < nprob; i++)
+        CMP_REQUIRE(!(la && probs[i].bias), "grouped weight gradients: the last-arriver form (deterministic mode) carries no bias sums");
     // the key is built field by field: WgradProblem has padding holes whose bytes are whatever the caller's stack held (a raw
     // byte copy made every step look like new shapes: a rebuild, two stream syncs and an upload per block per step)
     std::string key;
-    key.reserve((size_t)nprob * 48 + 8);
+    key.reserve((size_t)nprob * 56 + 8);
     auto put = [&key](const void* p, size_t n) { key.append((const char*)p, n); };
     for (int i = 0; i < nprob; i++) {
         const WgradProblem& q = probs[i];
-        put(&q.A, sizeof(q.A)); put(&q.B, sizeof(q.B)); put(&q.C, sizeof(q.C));
+        put(&q.A, sizeof(q.A)); put(&q.B, sizeof(q.B)); put(&q.C, sizeof(q.C)); put(&q.bias, sizeof(q.bias));
         const int v[5] = {q.lda, q.ldb, q.ldc, q.M, q.N};
         put(v, sizeof(v));
     }
     put(&K, sizeof(K));
     put(&G, sizeof(G));
-    const bool la = ex.wws != nullptr;
     put(&la, sizeof(la));
     if (key != g->key) {
+        const WgPlan plan = wgrad_group_plan(probs, nprob, K, ex.max_wgs, false, g->force);
+        if (plan.refusal != WG_FITS) return CMP_OK;
+        if (!plan.taken) {                              // remembered: the next call with these shapes returns at once
+            g->key = key;
+            g->nitems = 0;
+            return CMP_OK;
+        }
         {   // building a table synchronises the stream: not inside a capture (cmp_train_step_launches on a model that has not stepped yet)
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
             if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
@@ -2248,92 +2294,22 @@ int wgrad_group_run(void* stream, WgradGroup* g, const WgradProblem* probs, int 
                 return CMP_ERR_STATE;
             }
         }
-        struct Seg { int prob, m0, n0; };
-        std::vector<Seg> tiles;
-        for (int i = 0; i < nprob; i++)
-            for (int tm = 0; tm < cdiv(probs[i].M, 256); tm++)
-                for (int tn = 0; tn < cdiv(probs[i].N, 256); tn++) tiles.push_back({i, tm * 256, tn * 256});
-        const int T = (int)tiles.size(), nk = K / P_BK;
-        // Split count: every split of every tile is one more partial 256x256 f32 tile through the float-atomic unit (~1.3 TB/s),
-        // every split less is a longer k-loop per workgroup.  With few tokens the atomics win: the reference's default configuration
-        // (1 024 tokens, 12 tiles) ran 21 splits = 64 MB of atomics for 32 k-steps of work, 44 us per block; the minimum of
-        //   ceil(nk / s) * 0.91 us + T * s * 256 KiB / 1.3 TB/s          (tools/kbench.py wgradgroup, same constants as below)
-        // over s <= G / T is 4 splits there (~17 us) and stays at G / T for the benchmark shapes (K = 32 768 ... 131 072 tokens).
-        // (the last-arriver form takes the same cut: K ranges finer than one item per workgroup -- 7 ranges in 3 rounds at C4's 108
-        //  tiles -- measured 917 us without its reduction reads and 967 with them against 934 for the float-atomic form's 2 ranges)
-        int sp = 1;
-        {
-            const int smax = std::max(1, std::min(G / T, nk));
-            double best = 1e30;
-            for (int c = 1; c <= smax; c++) {
-                const double t = (double)cdiv(nk, c) * 0.91 + (double)T * c * 262144.0 / 1.3e6;
-                if (t < best * 0.999) { best = t; sp = c; }
-            }
-        }
-        // Workgroups left over by the common split count (C2: 256 - 48 * 5 = 16) go to whole PROBLEMS, smallest first, as one
-        // more split each (tiles that share operand panels keep the same K ranges): their items are shorter, finish early and
-        // put their share of the atomic traffic out before the final burst; the longest item is unchanged.
-        std::vector<int> tiles_of(nprob, 0), split_of(nprob, sp);
-        for (const Seg& t : tiles) tiles_of[t.prob]++;
-        {
-            int spare = G - T * sp;
-            std::vector<int> byt(nprob);
-            for (int i = 0; i < nprob; i++) byt[i] = i;
-            std::stable_sort(byt.begin(), byt.end(), [&](int a, int b) { return tiles_of[a] < tiles_of[b]; });
-            for (int i : byt)
-                if (T * sp <= G && sp + 1 <= nk && tiles_of[i] <= spare) { split_of[i] = sp + 1; spare -= tiles_of[i]; }
-        }
-        // items in K-range-major order (range j of every problem that has one, tile by tile): consecutive items = one XCD's group
-        struct Item { int tile, kt0, kt1, idx; };
-        std::vector<Item> order;
-        std::vector<int> ranges_of(T, 0);              // K ranges a tile really has (a chunk that starts behind nk does not exist)
-        int max_split = 0, longest = 0;
-        for (int i = 0; i < nprob; i++) max_split = std::max(max_split, split_of[i]);
-        for (int j = 0; j < max_split; j++)
-            for (int t = 0; t < T; t++) {
-                const int spt = split_of[tiles[t].prob], chunk = cdiv(nk, spt);
-                if (j * chunk >= nk) continue;
-                order.push_back({t, j * chunk, std::min(nk, (j + 1) * chunk), ranges_of[t]});
-                ranges_of[t] += 1;
-                longest = std::max(longest, std::min(nk, (j + 1) * chunk) - j * chunk);
-            }
-        const int nitems = (int)order.size();
-        if (max_split > 255 || T > 4095) return CMP_OK;       // (the meta word's fields; far outside any model shape)
-        std::vector<int> slot0(T, 0);                   // first workspace slot of a tile; single-range tiles need none
-        int nslots = 0;
-        for (int t = 0; t < T; t++) { slot0[t] = nslots; if (ranges_of[t] > 1) nslots += ranges_of[t]; }
-        {   // is one grouped launch cheaper than one split-K launch per problem?  (model above; K-independent overhead in k-steps)
-            const double ov = 59.0;
-            const double grouped = (double)longest * cdiv(nitems, G) + ov;
-            double separate = 0.0;
-            for (int i = 0; i < nprob; i++) {
-                const int t = cdiv(probs[i].M, 256) * cdiv(probs[i].N, 256);
-                const int si = std::max(1, std::min(G / std::max(1, t), nk));
-                separate += (double)cdiv(nk, si) * cdiv(t * si, G) + ov;
-            }
-            if (grouped >= separate && !g->force) {      // remembered: the next call with these shapes returns at once
-                g->key = key;
-                g->nitems = 0;
-                return CMP_OK;
-            }
-        }
+        const int T = plan.T, nitems = plan.nitems, nslots = plan.nslots;
         const size_t la_off = (WG_MAXP * sizeof(WgProb) + (size_t)nitems * sizeof(int4) + 127) / 128 * 128;      // counters on lines of their own
         const int Tpad = (T + 3) / 4 * 4;
         std::string host(la_off + (size_t)(Tpad + T) * sizeof(int), '\0');
         WgProb* hp = (WgProb*)&host[0];
         for (int i = 0; i < nprob; i++)
             hp[i] = WgProb{(const bf16_t*)probs[i].A, (const bf16_t*)probs[i].B, probs[i].C, probs[i].M, probs[i].N, probs[i].lda, probs[i].ldb,
-                           probs[i].ldc, 0};
+                           probs[i].ldc, 0, probs[i].bias};
         int4* hi = (int4*)&host[WG_MAXP * sizeof(WgProb)];
-        const int q = nitems >> 3, r = nitems & 7;
         for (int item = 0; item < nitems; item++) {
-            const int x = item & 7;                                        // the XCD group of the item (ItemPuller): consecutive lin per group
-            const int lin = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (item >> 3);
-            const Item& it = order[lin];
-            const int meta = tiles[it.tile].prob | (it.idx << 4) | (ranges_of[it.tile] << 12) | (it.tile << 20);
-            hi[item] = make_int4(meta, tiles[it.tile].m0 | (tiles[it.tile].n0 << 16), it.kt0, it.kt1);
+            const WgPlanItem& it = plan.order[plan.lin_of(item)];          // the XCD group of the item (ItemPuller): consecutive lin per group
+            const WgPlanTile& tl = plan.tiles[it.tile];
+            const int meta = tl.prob | (it.idx << 4) | (tl.ranges << 12) | (it.tile << 20);
+            hi[item] = make_int4(meta, tl.m0 | (tl.n0 << 16), it.kt0, it.kt1);
         }
-        memcpy(&host[la_off + (size_t)Tpad * sizeof(int)], slot0.data(), (size_t)T * sizeof(int));      // (the counters in front stay zero)
+        memcpy(&host[la_off + (size_t)Tpad * sizeof(int)], plan.slot0.data(), (size_t)T * sizeof(int));     // (the counters in front stay zero)
         HIP_CHECK(hipStreamSynchronize(s));            // the previous table of this group may still be in use / in flight (a rebuild is rare)
         if (g->dev_bytes < host.size()) {
             wgrad_group_free(g);
@@ -2414,20 +2390,46 @@ int wgrad_group_run(void* stream, WgradGroup* g, const WgradProblem* probs, int 
     *handled = true;
     return CMP_OK;
 }
-// kernel-level entry point of the grouped launch (tests, micro-benchmarks): nprob problems given as parallel arrays
-extern "C" int cmp_k_wgrad_group(void* stream, int nprob, const void* const* A, const int* lda, const void* const* B, const int* ldb,
-                                 float* const* C, const int* ldc, const int* M, const int* N, int K) {
+// kernel-level entry point of the grouped launch (tests, micro-benchmarks): nprob problems given as parallel arrays; bias (null: no
+// problem has one) holds per problem a vector that also receives the column sums of B_i, or null
+extern "C" int cmp_k_wgrad_group_bias(void* stream, int nprob, const void* const* A, const int* lda, const void* const* B, const int* ldb,
+                                      float* const* C, const int* ldc, const int* M, const int* N, int K, float* const* bias) {
     CMP_REQUIRE(nprob >= 1 && nprob <= WG_MAXP && A && B && C && lda && ldb && ldc && M && N, "wgrad_group: bad arguments");
     static thread_local WgradGroup grp;           // rebuilt whenever the problems change
     static thread_local WgradWs wws;              // (kept for the life of the thread, like the item table)
     grp.force = true;                             // this entry point IS the grouped launch, whatever the cost model says
     WgradProblem pr[WG_MAXP];
-    for (int i = 0; i < nprob; i++) pr[i] = WgradProblem{A[i], lda[i], B[i], ldb[i], C[i], ldc[i], M[i], N[i]};
+    for (int i = 0; i < nprob; i++) pr[i] = WgradProblem{A[i], lda[i], B[i], ldb[i], C[i], ldc[i], M[i], N[i], bias ? bias[i] : nullptr};
     GemmExtra ex;
     if (const char* e = getenv("COMPOSER_WGRAD_TAIL")) if (e[0] == 'l') ex.wws = &wws;
     bool handled = false;
     CHECK_SCHED(wgrad_group_run(stream, &grp, pr, nprob, K, ex, &handled));
     CMP_REQUIRE(handled, "wgrad_group: these shapes do not fit the grouped kernel (K %% 32, leading dimensions %% 8, 16-byte alignment, < 2 GiB operands)");
+    return CMP_OK;
+}
+extern "C" int cmp_k_wgrad_group(void* stream, int nprob, const void* const* A, const int* lda, const void* const* B, const int* ldb,
+                                 float* const* C, const int* ldc, const int* M, const int* N, int K) {
+    return cmp_k_wgrad_group_bias(stream, nprob, A, lda, B, ldb, C, ldc, M, N, K, nullptr);
+}
+// The plan of the grouped launch the same arguments would get (wgrad_plan.h), without a device: pointers are looked at for
+// alignment only (A / B null: aligned).  flags: 1 = slab split-K asked for, 2 = force (as cmp_k_wgrad_group does).  items (null:
+// not wanted) receives up to max_items rows {problem, m0, n0, first k-step, end k-step, index of the K range among the tile's,
+// K ranges of the tile, tile} in item-table order.
+extern "C" int cmp_wgrad_group_plan(int nprob, const void* const* A, const int* lda, const void* const* B, const int* ldb, const int* M,
+                                    const int* N, int K, int max_wgs, int flags, cmp_wgrad_plan_info* out, int32_t* items, int max_items) {
+    CMP_REQUIRE(out && lda && ldb && M && N && nprob >= 0 && nprob <= 64, "wgrad_group_plan: bad arguments");
+    std::vector<WgradProblem> pr((size_t)nprob);
+    for (int i = 0; i < nprob; i++) pr[i] = WgradProblem{A ? A[i] : nullptr, lda[i], B ? B[i] : nullptr, ldb[i], nullptr, N[i], M[i], N[i], nullptr};
+    const WgPlan p = wgrad_group_plan(pr.data(), nprob, K, max_wgs, (flags & 1) != 0, (flags & 2) != 0);
+    *out = cmp_wgrad_plan_info{p.refusal == WG_FITS, p.taken, p.refusal, p.G, p.T, p.nk, p.nitems, p.grid, p.max_split, p.longest, p.nslots};
+    if (items && p.refusal == WG_FITS) {
+        for (int item = 0; item < p.nitems && item < max_items; item++) {
+            const WgPlanItem& it = p.order[p.lin_of(item)];
+            const WgPlanTile& tl = p.tiles[it.tile];
+            const int32_t row[8] = {tl.prob, tl.m0, tl.n0, it.kt0, it.kt1, it.idx, tl.ranges, it.tile};
+            memcpy(items + (size_t)item * 8, row, sizeof(row));
+        }
+    }
     return CMP_OK;
 }
 

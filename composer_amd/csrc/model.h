@@ -232,6 +232,12 @@ struct cmp_model {
     bool stage_has_norm[3] = {false, false, false};
     std::vector<char> reload_seen;     // while poisoned: which parameters cmp_param_set has replaced since (all of them clears the flag)
     int ln_fused_mode = -1;            // COMPOSER_LN_FUSED as read when the model was created (-1 unset, 1 the same, 0 off, 3 training passes too)
+    int bias_wgrad = 10;               // COMPOSER_BIAS_WGRAD as read when the model was created: which bias gradients of a block ride on its grouped
+                                       // weight-gradient launch where backward() can carry them -- bits 1 pr_b, 2 fc_b, 4 proj_b, 8 attn_b; 0: none.
+                                       // Default fc_b + attn_b: their producers (GELU' dgrad epilogue, attention backward) lose 39 / 31 us per block
+                                       // without the sums; the LayerNorm backward kernel loses nothing (profiles/bias_from_wgrad.txt), so pr_b /
+                                       // proj_b stay with it and spare the grouped launch four of its eighteen summing tiles
+    bool bias_carried_last = false;    // the last backward pass did so (cmp_model_bias_path)
     DecodeState* dec = nullptr;
     DecodeBatchState* decb = nullptr;  // batched decode (decode_batch.hip): its own buffers, KV caches and captured chains
     DecGrammarCfg gram[2];             // event grammar of the batch-1 chain [0] and of the batched chain [1] (cmp_decode_grammar)

@@ -311,6 +311,7 @@ extern "C" int cmp_model_create(cmp_ctx* ctx, const cmp_model_cfg* cfg, cmp_mode
     cmp_model* m = new cmp_model();
     m->ctx = ctx;
     m->ln_fused_mode = ln_fused_mode;
+    if (const char* e = getenv("COMPOSER_BIAS_WGRAD")) m->bias_wgrad = atoi(e) & 15;      // read ONCE per model, like COMPOSER_LN_FUSED
     // a failure part-way (an allocation, an event) must not leave the buffers allocated so far behind
     const int rc = model_create_fill(m, ctx, cfg, V, E, W, L, H, D, Dl);
     if (rc != CMP_OK) { cmp_model_destroy(m); return rc; }
@@ -1028,10 +1029,46 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
     GemmDesc dhf = with_flags(xw(0, M, E, V, m->dlogits, m->w(m->off_wte), m->tmpE), CMP_GEMM_KPAD_ZERO);
     dhf.lda = m->ldz;                                 // dlogits rows are zero-padded to ldz (softmax_xent kernel)
     CHECK_RC(gemm(m, dhf));
+    // Bias gradients carried by the grouped weight-gradient launches.  Every bias gradient of a block is the column sum, over the
+    // tokens, of a B operand of the block's grouped launch (dmo -> pr_b, dfc -> fc_b, dao -> proj_b, dqkv -> attn_b), and that launch
+    // holds every B fragment in registers: the sums ride on it as one more MFMA per fragment (gemm.hip: WgProb::bias) and their
+    // producers -- the LayerNorm backward kernels, the GELU' dgrad epilogue, the attention backward kernels -- run without their
+    // column sums.  Decided per block BEFORE anything of it is enqueued (the ln_f site below produces the last block's dmo): the
+    // default grouped order only (the raw-row order stores rstd-scaled operands, the deterministic mode takes no float atomics),
+    // where the plan takes the grouped launch (wgrad_plan.h), and for the biases COMPOSER_BIAS_WGRAD named when the model was created
+    // (a mask, model.h: bias_wgrad; default fc_b + attn_b, 0 = none, 15 = all four).
+    // All of block i's bias gradients are then complete behind block i's grouped launch, ahead of bucket_ready(i); they are
+    // accumulated into G like the sums they replace (gradient accumulation, clipping: nothing else changes).
+    const bool raw = m->fused_last;
+    const bool grouped = ln && dt == CMP_BF16;
+    const int wg_max_wgs = m->ctx->dp_on() ? m->ctx->gemm_max_wgs : 0;
+    // dmo / dao of a block as backward() below hands them to the launches (the same buffers for every block)
+    const void* const dmo_buf = (raw || pr > 0.f) ? (const void*)m->dmask : (const void*)m->dx;
+    const void* const dao_buf = (raw || pr > 0.f) ? (const void*)(grouped ? m->dmask2 : m->dmask) : (const void*)m->dr;
+    auto block_probs = [&](int i, WgradProblem* wp) {
+        const LayerOff& o = m->lo[i];
+        const LayerAct& a = m->act[i];
+        wp[0] = WgradProblem{a.g, 4 * E, dmo_buf, E, m->G + o.pr_w, E, 4 * E, E};                  // dWpr   = g^T . dmo
+        wp[1] = WgradProblem{raw ? a.r : a.n, E, m->dfc, 4 * E, m->G + o.fc_w, 4 * E, E, 4 * E};   // dWfc   = n^T . dfc        [raw: r^T . (rstd_2 o dfc)]
+        wp[2] = WgradProblem{a.att, Ea, dao_buf, E, m->G + o.proj_w, E, Ea, E};                    // dWproj = att^T . dao
+        wp[3] = WgradProblem{raw ? m->xs[i] : a.u, E, m->dqkv, 3 * Ea, m->G + o.attn_w, 3 * Ea, E, 3 * Ea};    // dWattn = u^T . dqkv  [raw: x^T . (rstd_1 o dqkv)]
+    };
+    std::vector<char> carry((size_t)m->L, 0);           // per block: the bits of bias_wgrad its launch carries
+    enum { CB_PR = 1, CB_FC = 2, CB_PROJ = 4, CB_ATTN = 8 };
+    if (grouped && !raw && !m->slab && m->bias_wgrad) {
+        for (int i = 0; i < m->L; i++) {
+            WgradProblem wp[4];
+            block_probs(i, wp);
+            const WgPlan plan = wgrad_group_plan(wp, 4, M, wg_max_wgs, false, false);
+            if (plan.refusal == WG_FITS && plan.taken) carry[i] = (char)m->bias_wgrad;
+        }
+    }
+    m->bias_carried_last = m->L > 0 && carry[m->L - 1] != 0;
     // dx of every LayerNorm backward below is the gradient of the previous residual branch's dropout output, so the
-    // kernel also emits that branch's masked gradient (dmask) and bias gradient (column sums)
+    // kernel also emits that branch's masked gradient (dmask) and, unless the branch's grouped launch carries it, its bias
+    // gradient (column sums)
     CHECK_RC(ln_bwd(m, m->tmpE, m->xs[m->L], m->P + m->off_lnf_g, m->lnf_mean, m->lnf_rstd, nullptr, m->dx,
-                    m->G + m->off_lnf_g, m->G + m->off_lnf_b, M, m->dmask, m->G + m->lo[m->L - 1].pr_b, pr,
+                    m->G + m->off_lnf_g, m->G + m->off_lnf_b, M, m->dmask, (carry[m->L - 1] & CB_PR) ? nullptr : m->G + m->lo[m->L - 1].pr_b, pr,
                     drop_stream(step, m->L - 1, 3)));
     bool dmo_ready = true;      // dmask / pr_b of the current layer already produced
     // A block's backward pass runs in one of two orders.
@@ -1045,7 +1082,6 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
     // consume them yield rstd o dn / rstd o du (the residual term of du gets its rstd in the epilogue), which the LayerNorm backward
     // kernels take as they are (ln_bwd: prescaled), and one small pass per block applies gamma / beta and the mean term to the two
     // accumulated gradients (wgrad_ln_fix_kernel).  The launches keep the places they have in the default grouped order.
-    const bool raw = m->fused_last;
     // (the statistics of all 2L sites, merged from their partials in one launch: the LayerNorm backward kernels and the attention
     //  backward kernels read per-row arrays)
     if (raw) CHECK_RC(ln_stats_merge_run(s, m->ln_sites, 2 * m->L, E / 256, m->cfg.ln_eps, M));
@@ -1059,7 +1095,6 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
     // of block i -- which overwrites it with block i - 1's -- is enqueued behind block i's grouped launch on the one compute stream.
     // (COMPOSER_DETERMINISTIC=1 takes the grouped launch too since round 6, in its last-arriver form: partial tiles summed in the
     //  order of the K ranges, no float atomics -- the deterministic step runs the launch order of the default one)
-    const bool grouped = ln && dt == CMP_BF16;
     CMP_REQUIRE(!raw || grouped, "backward: the fused block path needs the grouped weight-gradient order");
     if (grouped && (int)m->wgrad_groups.size() != m->L) m->wgrad_groups.resize(m->L);
     for (int i = m->L - 1; i >= 0; i--) {
@@ -1081,14 +1116,15 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
         LnEpi ls;
         ls.np = E / 256; ls.eps = m->cfg.ln_eps; ls.scale = 1;
         ls.in_part = a.ln2_part;
-        CHECK_RC(gemm(m, with_gelu_grad(xw(1, M, 4 * E, E, dmo, m->w(o.pr_w), m->dfc), a.fc), m->G + o.fc_b,
+        const int cb = carry[i];                 // the bias gradients of this block that ride on its grouped launch
+        CHECK_RC(gemm(m, with_gelu_grad(xw(1, M, 4 * E, E, dmo, m->w(o.pr_w), m->dfc), a.fc), (cb & CB_FC) ? nullptr : m->G + o.fc_b,
                       raw ? &ls : nullptr));                                // dfc = (dmo.Wpr^T) * gelu'(fc) [raw: rstd_2 o that]; b_fc grad = column sums of dfc
         if (!grouped) CHECK_RC(wgrad(E, 4 * E, a.n, E, m->dfc, 4 * E, m->G + o.fc_w));
         void* const dao_mask = grouped ? m->dmask2 : m->dmask;
         if (ln) {
             CHECK_RC(gemm(m, xw(1, M, E, 4 * E, m->dfc, m->w(o.fc_w), m->tmpE)));   // dn
             CHECK_RC(ln_bwd(m, m->tmpE, a.r, m->P + o.ln2_g, a.ln2_mean, a.ln2_rstd, m->dx, m->dr, m->G + o.ln2_g, m->G + o.ln2_b, M,
-                            dao_mask, m->G + o.proj_b, pr, drop_stream(step, i, 2), raw));   // dr = dx + LN2'(dn); dao, b_proj grad
+                            dao_mask, (cb & CB_PROJ) ? nullptr : m->G + o.proj_b, pr, drop_stream(step, i, 2), raw));   // dr = dx + LN2'(dn); dao, b_proj grad
         } else {
             CHECK_RC(gemm(m, with_resid(xw(1, M, E, 4 * E, m->dfc, m->w(o.fc_w), m->dr), m->dx)));   // dr = dx + dn
         }
@@ -1106,19 +1142,20 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
         const bool det = m->slab != nullptr;     // the fused bias sums are float atomics: a separate fixed-order pass instead
         AttnDesc ad = attn_desc(m, i, B, T, step, pa);
         ad.d_o = m->tmpE; ad.delta = m->delta; ad.dqkv = m->dqkv;
-        ad.bias_grad = det ? nullptr : m->G + o.attn_b;                            // b_attn grad = column sums of dqkv
+        ad.bias_grad = det || (cb & CB_ATTN) ? nullptr : m->G + o.attn_b;                            // b_attn grad = column sums of dqkv
         if (raw) ad.ln.rstd = a.ln1_rstd;
         CHECK_RC(attn_bwd_run(s, ad));
         if (det) CHECK_RC(colsum_det(m, m->dqkv, 3 * Ea, m->G + o.attn_b, M, 3 * Ea));
         if (grouped) {
-            const WgradProblem wp[4] = {
-                {a.g, 4 * E, dmo, E, m->G + o.pr_w, E, 4 * E, E},                  // dWpr   = g^T . dmo
-                {raw ? a.r : a.n, E, m->dfc, 4 * E, m->G + o.fc_w, 4 * E, E, 4 * E},           // dWfc   = n^T . dfc        [raw: r^T . (rstd_2 o dfc)]
-                {a.att, Ea, dao, E, m->G + o.proj_w, E, Ea, E},                    // dWproj = att^T . dao
-                {raw ? m->xs[i] : a.u, E, m->dqkv, 3 * Ea, m->G + o.attn_w, 3 * Ea, E, 3 * Ea}};    // dWattn = u^T . dqkv  [raw: x^T . (rstd_1 o dqkv)]
+            WgradProblem wp[4];
+            block_probs(i, wp);
+            CMP_REQUIRE(wp[0].B == dmo && wp[2].B == dao, "backward: the grouped launch's operands moved");
+            float* const bias_of[4] = {m->G + o.pr_b, m->G + o.fc_b, m->G + o.proj_b, m->G + o.attn_b};
+            for (int k = 0; k < 4; k++)                  // (wp[] is in the order of the CB_* bits)
+                if (cb & (1 << k)) wp[k].bias = bias_of[k];
             GemmExtra ex;
             ex.role = 2;
-            ex.max_wgs = m->ctx->dp_on() ? m->ctx->gemm_max_wgs : 0;
+            ex.max_wgs = wg_max_wgs;
             ex.dp = m->ctx->dp_on();
             ex.sched = &m->ctx->gemm_sched;
             if (m->slab) ex.wws = &m->wgrad_ws;        // deterministic mode: partial tiles through workspace slots, summed by each tile's last arriver (gemm.hip: WgLa)
@@ -1129,6 +1166,8 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
                 CHECK_RC(wgrad(E, 4 * E, wp[1].A, E, m->dfc, 4 * E, m->G + o.fc_w));
                 CHECK_RC(wgrad(Ea, E, a.att, Ea, dao, E, m->G + o.proj_w));
                 CHECK_RC(wgrad(E, 3 * Ea, wp[3].A, E, m->dqkv, 3 * Ea, m->G + o.attn_w));
+                for (int k = 0; k < 4; k++)          // (the plan said the launch would run: not reached; the sums nobody else made, as passes)
+                    if (cb & (1 << k)) CHECK_RC(colsum_any(m, wp[k].B, wp[k].ldb, bias_of[k], M, wp[k].N));
             }
             if (raw) {               // gamma / beta and the mean term on the two gradients that were accumulated on raw rows
                 CHECK_RC(wgrad_ln_fix_run(s, m->G + o.fc_w, E, 4 * E, m->P + o.ln2_g, m->P + o.ln2_b, m->G + o.fc_b,
@@ -1143,7 +1182,7 @@ static int backward(cmp_model* m, const int32_t* x_dev, int B, int T, int64_t st
                           raw ? &ls : nullptr));                                   // du = dr + dqkv.Wattn^T  [raw: rstd_1 o du]
             // dx_in = LN1'(du): no skip connection around LN1; feeds layer i-1's MLP branch (or the embedding for i = 0)
             CHECK_RC(ln_bwd(m, m->tmpE, m->xs[i], m->P + o.ln1_g, a.ln1_mean, a.ln1_rstd, nullptr, m->dx, m->G + o.ln1_g,
-                            m->G + o.ln1_b, M, i > 0 ? m->dmask : nullptr, i > 0 ? m->G + m->lo[i - 1].pr_b : nullptr, pr,
+                            m->G + o.ln1_b, M, i > 0 ? m->dmask : nullptr, i > 0 && !(carry[i - 1] & CB_PR) ? m->G + m->lo[i - 1].pr_b : nullptr, pr,
                             drop_stream(step, i > 0 ? i - 1 : 0, 3), raw));
             dmo_ready = true;
         } else {
@@ -1323,6 +1362,12 @@ extern "C" int cmp_model_path_info(cmp_model* m, int* fused, int64_t* wgrad_tabl
         for (const WgradGroup& g : m->wgrad_groups) n += g.rebuilds;
         *wgrad_table_builds = n;
     }
+    return CMP_OK;
+}
+
+extern "C" int cmp_model_bias_path(cmp_model* m, int* carried) {
+    CMP_REQUIRE(m && carried, "model_bias_path: null argument");
+    *carried = m->bias_carried_last ? 1 : 0;
     return CMP_OK;
 }
 

@@ -724,6 +724,29 @@ int cmp_k_gemm(void* stream, int dtype, int ta, int tb, int M, int N, int K,
  * below 2 GiB.  The model's backward pass uses this launch in bf16 mode. */
 int cmp_k_wgrad_group(void* stream, int nprob, const void* const* A, const int* lda, const void* const* B, const int* ldb,
                       float* const* C, const int* ldc, const int* M, const int* N, int K);
+/* The same launch with the bias gradients riding on it: bias (NULL: as cmp_k_wgrad_group) holds per problem NULL or a vector of N_i
+ * floats that receives, ACCUMULATED with f32 atomics, the column sums of B_i over the K rows -- the bias gradient of the Conv1D whose
+ * weight gradient problem i is (tf.GradientTape through transformer.py:205-209: dy is that B operand).  One more MFMA per B fragment
+ * in the items of a problem's first tile row, no pass of its own.  The last-arriver form (COMPOSER_WGRAD_TAIL=la) refuses a bias. */
+int cmp_k_wgrad_group_bias(void* stream, int nprob, const void* const* A, const int* lda, const void* const* B, const int* ldb,
+                           float* const* C, const int* ldc, const int* M, const int* N, int K, float* const* bias);
+/* Host-only window on the grouped launch's plan (CPU tests; no HIP call, works without a device): whether the problems fit the
+ * kernel, whether the cost model takes the grouped launch, and the item table.  A / B (NULL: aligned) are looked at for 16-byte
+ * alignment only.  flags: 1 = slab split-K asked for (refused), 2 = take the launch whatever the cost model says (as
+ * cmp_k_wgrad_group does).  items (NULL: not wanted): up to max_items rows of 8 int32 {problem, m0, n0, first k-step, end k-step,
+ * index of this K range among the tile's, K ranges of the tile, tile}, in item-table order. */
+typedef struct cmp_wgrad_plan_info {
+    int32_t fits;                /* the problems are in the grouped kernel's domain */
+    int32_t taken;               /* ... and the grouped launch is chosen */
+    int32_t refusal;             /* 0 fits, 1 problem count, 2 K, 3 workgroups, 4 slab workspace, 5 shape, 6 leading dimension,
+                                    7 alignment, 8 operand span, 9 table fields */
+    int32_t wgs, tiles, nk;      /* workgroups the launch may use, output tiles of all problems, k-steps of 32 */
+    int32_t nitems, grid;
+    int32_t max_split, longest;  /* most K ranges of a tile, longest item in k-steps */
+    int32_t nslots;              /* last-arriver form: partial-tile workspace slots */
+} cmp_wgrad_plan_info;
+int cmp_wgrad_group_plan(int nprob, const void* const* A, const int* lda, const void* const* B, const int* ldb, const int* M,
+                         const int* N, int K, int max_wgs, int flags, cmp_wgrad_plan_info* out, int32_t* items, int max_items);
 /* ---- LayerNorm folded into the block's GEMM epilogues (the fused block path of the bf16 train / inference forward) -----------
  * Replaces the stand-alone tf.keras LayerNormalization calls of DecoderBlock.call (transformer.py:583-584 ln_1, :591 ln_2; layers
  * built at :551,563) for large batches: no LayerNorm kernel runs in the forward pass.  Row statistics travel as PARTIALS, fp32
@@ -770,6 +793,12 @@ int cmp_k_wgrad_ln_fix(void* stream, float* G, int rows, int cols, const float* 
  * wgrad_table_builds = item tables of the grouped weight-gradient launches built so far (a steady train loop builds one per
  * decoder block, once). */
 int cmp_model_path_info(cmp_model* m, int* fused, int64_t* wgrad_table_builds);
+/* carried = 1 when the last backward pass took the bias gradients of its decoder blocks from the blocks' grouped weight-gradient
+ * launches (cmp_k_wgrad_group_bias) instead of the producers' own column sums; 0 otherwise (no backward pass yet, fp32, no
+ * LayerNorm, COMPOSER_LN_FUSED=3, COMPOSER_DETERMINISTIC=1, COMPOSER_BIAS_WGRAD=0, or shapes at which the grouped launch is not
+ * taken).  COMPOSER_BIAS_WGRAD is read once per model at cmp_model_create: a mask of the carried bias gradients, 1 mlp c_proj, 2 c_fc,
+ * 4 attention c_proj, 8 c_attn; unset = 10 (c_fc + c_attn: the two whose producers are faster without their sums), 15 = all four. */
+int cmp_model_bias_path(cmp_model* m, int* carried);
 /* Registers a device workspace for split-K reductions: with it, split-K launches write per-split fp32 partial tiles and
  * fold them in a fixed order (reproducible, no float atomics); without it (or if too small: splitk*M*N*4 bytes) they
  * accumulate with f32 atomics.  CMP_GEMM_ATOMICS forces the atomic path. */
