@@ -203,6 +203,7 @@ SIGNATURES = {
     "cmp_model_bias_path": (_i, [_P, C.POINTER(_i)]),
     "cmp_gemm_set_workspace": (_i, [_P, _i64]),
     "cmp_gemm_colsum_next": (_i, [_P]),
+    "cmp_gemm_grid_next": (_i, [_i, _i]),
     "cmp_gemm_set_stamps": (_i, [_P]),
     "cmp_gemm_plan": (_i, [_i, _i, _i, _i, _i, _i, _P, _i, _P, _i, _P, _i, _P, _i, _P, _i, _P, _i, _i, _i, _f, _u64, _u32, _i, C.POINTER(GemmPlanInfo)]),
     "cmp_k_colsum": (_i, [_P, _P, _i, _P, _i, _i, _i]),

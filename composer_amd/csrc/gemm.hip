@@ -2101,6 +2101,18 @@ extern "C" int cmp_gemm_ln_scale_next(const float* in_part, int np, float eps) {
     t_ln_next.scale = 1;
     return CMP_OK;
 }
+// One-shot, like cmp_gemm_colsum_next: the NEXT cmp_k_gemm / cmp_gemm_plan of this thread runs its persistent kernel on at most max_wgs
+// CUs (GemmExtra::max_wgs; 0 = no cap) and, with rev != 0, walks every XCD group's run of tiles from its end (GemmExtra::rev) -- what
+// only the model could ask for, and only under a communicator.  Every grid of 1 .. 256 (512 for the two-per-CU deep pipeline) is
+// inside what ItemPuller handles (nstatic / gcount take any grid, the first-item flags are 512); anything else is refused here.
+static thread_local int t_max_wgs_next = 0;
+static thread_local bool t_rev_next = false;
+extern "C" int cmp_gemm_grid_next(int max_wgs, int rev) {
+    CMP_REQUIRE(max_wgs >= 0 && max_wgs <= 256, "gemm_grid_next: max_wgs is 0 (no cap) .. 256, got %d", max_wgs);
+    t_max_wgs_next = max_wgs;
+    t_rev_next = rev != 0;
+    return CMP_OK;
+}
 static thread_local float* t_slab_ws = nullptr;       // split-K workspace for this thread's cmp_k_gemm calls
 static thread_local size_t t_slab_bytes = 0;
 extern "C" int cmp_gemm_set_workspace(void* ws, int64_t bytes) {
@@ -2447,6 +2459,10 @@ static GemmExtra take_armed() {
     t_colsum_next = nullptr;
     ex.ln = t_ln_next;
     t_ln_next = LnEpi{};
+    ex.max_wgs = t_max_wgs_next;
+    ex.rev = t_rev_next;
+    t_max_wgs_next = 0;
+    t_rev_next = false;
     ex.slab_ws = t_slab_ws;
     ex.slab_bytes = t_slab_bytes;
     return ex;

@@ -807,11 +807,16 @@ int cmp_gemm_set_workspace(void* ws_dev, int64_t bytes);
  * out[0..N) -- the bias gradient that goes with an input-gradient GEMM (transformer.py:916-920 via tf.GradientTape).
  * Fused into the GEMM epilogue where possible, otherwise a cmp_k_colsum pass after it. */
 int cmp_gemm_colsum_next(float* out);
+/* One-shot: the next cmp_k_gemm (or cmp_gemm_plan) of this thread launches its persistent kernel on at most max_wgs CUs
+ * (0 = no cap, up to 256; the 128x256 deep pipeline runs two workgroups per capped CU) and, with rev != 0, the 256x256
+ * two-stage kernel walks every XCD group's tiles from the end -- the model's grid cap under a communicator and its alternating
+ * walk direction, for the kernel-level tests that give a workgroup several items.  Values outside 0..256: CMP_ERR_INVALID. */
+int cmp_gemm_grid_next(int max_wgs, int rev);
 /* diagnostic only: a device buffer of 500 uint64 receives (id, s_memtime) pairs from one workgroup of the next
  * deep-pipeline GEMM launches (tools/gemm_timeline.py); pass NULL to switch it off. */
 int cmp_gemm_set_stamps(void* dev_buf);
 /* Host-only window on the launcher's decision (CPU tests): the plan of the launch that cmp_k_gemm would make of the same
- * arguments.  Consumes the calling thread's armed one-shot state (cmp_gemm_colsum_next, cmp_gemm_ln_next,
+ * arguments.  Consumes the calling thread's armed one-shot state (cmp_gemm_colsum_next, cmp_gemm_grid_next, cmp_gemm_ln_next,
  * cmp_gemm_ln_scale_next; reads cmp_gemm_set_workspace) exactly as the next cmp_k_gemm would, dereferences nothing and calls
  * no HIP function: it works without a device, operand pointers may be any non-null 16-byte-aligned value.  A launch cmp_k_gemm
  * would refuse returns the same status and sets the same cmp_last_error() text. */

@@ -101,6 +101,30 @@ def test_split_k_modes_take_slabs_or_atomics(lib, family):
         assert lib.cmp_gemm_set_workspace(None, 0) == 0
 
 
+@pytest.mark.parametrize("family", G.FAMILIES, ids=G.FAMILY_IDS)
+def test_the_grid_hook_changes_one_plan_and_nothing_when_unarmed(lib, family):
+    """cmp_gemm_grid_next is one-shot: over the case tables, the plan after an armed plan was consumed -- and the plan armed with
+    (0, 0) -- is field for field the plan of a thread that never armed it; the armed plan itself differs in grid_x alone, and only
+    on the persistent kernels (the cap, twice the cap for the 128x256 deep pipeline, or all items when they are fewer)."""
+    dtype, flags = family
+    for (ta, tb, M, N, K, kz, epi) in G.rows_of(dtype, flags):
+        args = G.stage_gemm_case(dtype, flags, ta, tb, M, N, K, kz, epi, True, device="cpu")[4]
+        p0 = plan_args(lib, args)
+        assert lib.cmp_gemm_grid_next(3, 1) == 0
+        p1 = plan_args(lib, args)
+        p2 = plan_args(lib, args)
+        assert lib.cmp_gemm_grid_next(0, 0) == 0
+        p3 = plan_args(lib, args)
+        assert p2 == p0 and p3 == p0, (family, ta, tb, M, N, K, epi)
+        want = dict(p0)
+        if p0["family"] >= TILE256:
+            want["grid_x"] = min(p0["ntiles"] * p0["nsplit"], 6 if p0["family"] == P4_128 else 3)
+        assert p1 == want, (family, ta, tb, M, N, K, epi, p1)
+    assert lib.cmp_gemm_grid_next(257, 0) == INVALID and lib.cmp_gemm_grid_next(-1, 0) == INVALID
+    p = plan(lib, 0, 1, T, 1536, 512, bias=True)            # a refused arming call arms nothing
+    assert p["grid_x"] == 256, p
+
+
 # ------------------------------------------------------------------------------------------ (b) the model's own launches
 T = 131072          # C2: E = 512, 131 072 tokens, V = 390 (logits rows padded to 448)
 

@@ -19,6 +19,7 @@ import torch
 
 from oracle import transformer_oracle as O
 import row_bounds as RB
+import gemm_items_bounds as IB
 
 pytestmark = pytest.mark.gpu
 FP32, BF16 = 0, 1
@@ -170,6 +171,13 @@ def test_fold_epilogue_is_layernorm_then_conv1d(lib, E, offset, act):
         exact, pre = O.gelu(exact), O.gelu(pre)
     assert rel(out.double().cpu().numpy(), exact) < 6e-3
     assert rel(out.double().cpu().numpy(), pre) < 1.2e-2               # ... and it IS LayerNorm + Conv1D within the bf16 weight rounding
+    # ... and every element inside its own limit (tests/gemm_items_bounds.py), on exactly what the kernel was handed
+    case, o = IB.adhoc("fold-gelu" if act else "fold", x64, wt64.T, lnm=1, np_=E // 256, part=part.cpu().numpy(),
+                       cs=cs.double().cpu().numpy(), bias=bo.double().cpu().numpy())
+    outs = {"C": out.double().cpu().numpy()}
+    if act:
+        outs["aux"] = aux.double().cpu().numpy()
+    print(" fold E %d offset %g act %d: worst error / limit %s" % (E, offset, act, IB.check_outputs(case, o, outs)))
 
 
 @pytest.mark.parametrize("E", [512, 768])
@@ -205,6 +213,11 @@ def test_residual_epilogue_emits_partials_and_rebuilds_ln1(lib, E, rebuild, p):
     gp = pout.double().cpu().numpy()
     assert np.abs(gp[..., 0] - sp[..., 0]).max() < 2e-5 * (1 + np.abs(sp[..., 0]).max())
     assert rel(gp[..., 1], sp[..., 1]) < 2e-5
+    # ... and every element, and both statistics of every (row, segment), inside their own limits (tests/gemm_items_bounds.py)
+    extra = dict(part=pin.cpu().numpy(), gamma=g.astype(np.float64), beta=be.astype(np.float64)) if rebuild else {}
+    case, o = IB.adhoc("rebuild" if rebuild else "stats", A.double().cpu().numpy(), W.double().cpu().numpy().T, lnm=3 if rebuild else 2,
+                       np_=E // 256, p=p, seed=21, stream=9, bias=b.double().cpu().numpy(), resid=r64, **extra)      # (_gemm_ln's seed and stream)
+    print(" c_proj E %d rebuild %d p %g: worst error / limit %s" % (E, rebuild, p, IB.check_outputs(case, o, {"C": got, "part": gp.reshape(M, -1)})))
 
 
 def test_a_launch_that_cannot_carry_the_epilogue_fails_loudly(lib):
@@ -255,6 +268,10 @@ def test_scale_epilogues_carry_the_rows_rstd_as_a_factor(lib, E):
     prod = acc * _gelu_grad64(aux.double().cpu().numpy())
     assert rel(Cm.double().cpu().numpy(), rs * prod) < 8e-3
     assert rel(csum.cpu().numpy(), prod.sum(0)) < 2e-4
+    a64, w64 = A.double().cpu().numpy(), W.double().cpu().numpy().T
+    case, o = IB.adhoc("scale-gelugrad", a64, w64, lnm=5, np_=E // 256, colsum=True, part=part.cpu().numpy(), pre=aux.double().cpu().numpy())
+    print(" scale GELU' E %d: worst error / limit %s" % (E, IB.check_outputs(
+        case, o, {"C": Cm.double().cpu().numpy(), "colsum": csum.double().cpu().numpy()}, colsum_start=np.zeros(N))))
     # residual kind
     res = bf(rng.normal(0, 1.0, (M, N)))
     Cm2 = torch.zeros(M, N, dtype=torch.bfloat16, device="cuda")
@@ -262,6 +279,8 @@ def test_scale_epilogues_carry_the_rows_rstd_as_a_factor(lib, E):
     ck(lib, lib.cmp_k_gemm(stream(), BF16, 0, 1, M, N, K, P(A), K, P(W), K, P(Cm2), N, None, 0, None, 0, P(res), N, 0, 1, 0.0, 0, 0, 8))
     torch.cuda.synchronize()
     assert rel(Cm2.double().cpu().numpy(), acc + rs * res.double().cpu().numpy()) < 8e-3
+    case, o = IB.adhoc("scale-resid", a64, w64, lnm=5, np_=E // 256, part=part.cpu().numpy(), resid=res.double().cpu().numpy())
+    print(" scale residual E %d: worst error / limit %s" % (E, IB.check_outputs(case, o, {"C": Cm2.double().cpu().numpy()})))
 
 
 @pytest.mark.parametrize("E", [512, 768])
@@ -517,6 +536,9 @@ def test_fold_epilogue_with_fp32_output_and_a_ragged_last_column(lib, E):
     exact = rs * (x64 @ wt64.T) - rs * mu * wt64.sum(1) + bias.double().cpu().numpy()[:N]
     assert rel(got[:, :N], exact) < 2e-5                              # fp32 output: only the accumulation order is left
     assert np.all(got[:, N:] == -3.0)
+    case, o = IB.adhoc("fold32", x64, wt64.T, lnm=1, np_=E // 256, part=part.cpu().numpy(), cs=cs.double().cpu().numpy(),
+                       bias=bias.double().cpu().numpy())
+    print(" fold fp32 E %d: worst error / limit %s" % (E, IB.check_outputs(case, o, {"C": got[:, :N].astype(np.float64)})))
 
 
 def test_hidden_states_after_a_pass_that_folded_ln_f():
