@@ -2413,7 +2413,15 @@ extern "C" int cmp_k_wgrad_group_bias(void* stream, int nprob, const void* const
     WgradProblem pr[WG_MAXP];
     for (int i = 0; i < nprob; i++) pr[i] = WgradProblem{A[i], lda[i], B[i], ldb[i], C[i], ldc[i], M[i], N[i], bias ? bias[i] : nullptr};
     GemmExtra ex;
+    // this thread's one-shot cmp_gemm_grid_next state is consumed here as cmp_k_gemm consumes it (take_armed): the cap bounds this
+    // launch's workgroups; `rev` has no meaning for the item table and is ignored; both are cleared, so that neither reaches the
+    // next cmp_k_gemm -- also when this call is refused
+    ex.max_wgs = t_max_wgs_next;
+    t_max_wgs_next = 0;
+    t_rev_next = false;
     if (const char* e = getenv("COMPOSER_WGRAD_TAIL")) if (e[0] == 'l') ex.wws = &wws;
+    CMP_REQUIRE(ex.max_wgs == 0 || ex.max_wgs >= 8, "wgrad_group: a cap of %d workgroups (cmp_gemm_grid_next) leaves the grouped launch none: "
+                "it runs on multiples of 8, so the cap is 0 (none) or 8 .. 256", ex.max_wgs);
     bool handled = false;
     CHECK_SCHED(wgrad_group_run(stream, &grp, pr, nprob, K, ex, &handled));
     CMP_REQUIRE(handled, "wgrad_group: these shapes do not fit the grouped kernel (K %% 32, leading dimensions %% 8, 16-byte alignment, < 2 GiB operands)");

@@ -810,7 +810,11 @@ int cmp_gemm_colsum_next(float* out);
 /* One-shot: the next cmp_k_gemm (or cmp_gemm_plan) of this thread launches its persistent kernel on at most max_wgs CUs
  * (0 = no cap, up to 256; the 128x256 deep pipeline runs two workgroups per capped CU) and, with rev != 0, the 256x256
  * two-stage kernel walks every XCD group's tiles from the end -- the model's grid cap under a communicator and its alternating
- * walk direction, for the kernel-level tests that give a workgroup several items.  Values outside 0..256: CMP_ERR_INVALID. */
+ * walk direction, for the kernel-level tests that give a workgroup several items.  Values outside 0..256: CMP_ERR_INVALID.
+ * cmp_k_wgrad_group / cmp_k_wgrad_group_bias consume the same state: the cap becomes the workgroup count of the grouped launch's
+ * plan (cmp_wgrad_group_plan's max_wgs; rounded down to a multiple of 8, so a cap of 1..7 is refused by that call with
+ * CMP_ERR_INVALID and a message that names the cap), `rev` is ignored there, and both are cleared -- by a refused call too -- so
+ * that neither reaches a later cmp_k_gemm. */
 int cmp_gemm_grid_next(int max_wgs, int rev);
 /* diagnostic only: a device buffer of 500 uint64 receives (id, s_memtime) pairs from one workgroup of the next
  * deep-pipeline GEMM launches (tools/gemm_timeline.py); pass NULL to switch it off. */
